@@ -14,13 +14,17 @@ GiB/s counts unencoded blob bytes (criterion Throughput::Bytes, blob_encoding.rs
 Multi-GPU: one process per GPU (torchrun; `--gpus N` without a torchrun environment launches
 it); every rank encodes+decodes its own blob (weak scaling, independent blobs, no collective on
 the data path).  value = all ranks' blob bytes over the max-over-ranks wall time of the timed
-steps.  Beside the metric, at every N: config C3 (128 independent 4 MiB blobs dealt over the
+steps.  A plain run does only that: set-up, warm-up, the timed steps, the line.  With --full,
+beside the metric (its round-trip check, the solo pass, the CPU baseline and the single-GPU side
+legs: see the options), at every N: config C3 (128 independent 4 MiB blobs dealt over the
 ranks, BlobIds all-gathered) and config C4 (one 4 GiB blob row/column-partitioned over the
 ranks with RCCL all-to-alls / all-gather, every rank ending with its assembled sliver pairs;
 decoded from K_p primary slivers scattered from rank 0 and gathered back), each timed
 max-over-ranks.
 
-Output: one JSON line on rank 0 (see the driver contract in the task statement).
+Output: one JSON line on rank 0 (metric, value, unit, higher_is_better, dtype, ms_per_step = the
+milliseconds one timed step took, ...); --dump-outputs DIR also writes the last timed step's
+outputs as DIR/<name>.npy (dump_outputs).
 """
 
 from __future__ import annotations
@@ -140,6 +144,17 @@ def parse():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--blob-mib", type=float, default=256.0)
     ap.add_argument("--n-shards", type=int, default=1000)
+    ap.add_argument("--full", action="store_true",
+                    help="beside the metric, also run everything else this benchmark measures or "
+                         "checks: the decode round-trip check, the solo (kernel-quality) pass, the "
+                         "measured copy bandwidth and the side legs below (each still switched by "
+                         "its own option).  Without it a run sets up, warms up, times the steps "
+                         "and prints the line; the side legs' slots are null")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (primary "
+                         "and secondary slivers, sliver-pair hashes, BlobId, decoded blob) as "
+                         "DIR/<name>.npy in float32; arrays above 2^21 elements as a fixed seeded "
+                         "sample of that many")
     ap.add_argument("--cpu-baseline", choices=["auto", "off"], default="auto")
     ap.add_argument("--cpu-sample-mib", type=float, default=256.0,
                     help="blob size the CPU restatement encodes+decodes once (default: the full "
@@ -359,7 +374,8 @@ def main():
     # --subsets fresh a new one every step (warm-up, timed and solo passes), so the decode's
     # per-erasure-pattern plan never repeats; with fixed the first one every step
     rng = np.random.default_rng(42)
-    n_sub = (args.warmup + args.steps + SOLO_WARM + SOLO_ITERS) if args.subsets == "fresh" else 1
+    n_solo = SOLO_WARM + SOLO_ITERS if args.full else 0
+    n_sub = max(1, args.warmup + args.steps + n_solo) if args.subsets == "fresh" else 1
     subsets = [[int(i) for i in rng.permutation(n)[:kp]] for _ in range(n_sub)]
     idx = subsets[0]
     pl_ = info.primary_sliver_len
@@ -494,7 +510,9 @@ def main():
         elapsed = float(t.item())
     stages = profile_read()
     profile(False)
-    if args.verify:
+    if args.dump_outputs and counter[0]:
+        dump_outputs(args.dump_outputs, sets[(counter[0] - 1) % n_sets], n, info, rank)
+    if args.verify and args.full:
         ok = all(bool(torch.equal(S["decoded"], blob)) for S in sets)
     else:
         ok = None
@@ -505,7 +523,9 @@ def main():
     # region and read the decode 10 % above its isolated launch (1.03-1.09 vs 0.94 ms,
     # VERDICT r05 weak #4); tools/solo_probe.py measured that launch at 0.93-0.95 ms in every
     # isolated setting (after an encode, after a 2 GiB flush, back to back, fresh or cached).
-    solo_stages = stages
+    # (--full only: the solo pass takes runs of its own; without it there is no solo reading)
+    solo = args.overlap == "on" and args.full
+    solo_stages = stages if args.overlap != "on" else {}
     solo_each = []
     if isinstance(clocks, _ClockSampler):
         clocks.phase = "after_timed"
@@ -516,7 +536,7 @@ def main():
         time.sleep(pause)
     if isinstance(clocks, _ClockSampler):
         clocks.phase = "solo_warm"
-    if args.overlap == "on":
+    if solo:
         # the same pairs unmeasured first, back to back: measured one by one right after the
         # timed region, the first solo decodes ran 10-25 % slow and reached the isolated launch
         # time only after ~8 pairs, with or without a 0.5 s pause and at the same graphics clock
@@ -530,7 +550,7 @@ def main():
         torch.cuda.synchronize()
     if isinstance(clocks, _ClockSampler):
         clocks.phase = "solo"
-    if args.overlap == "on":
+    if solo:
         for _ in range(SOLO_ITERS):
             plan.profile(True)
             plan.encode_async(blob.data_ptr(), primary.data_ptr(), secondary.data_ptr(),
@@ -563,7 +583,8 @@ def main():
             f"mean {sum(n_present_all) / len(n_present_all):.1f})" if args.subsets == "fresh"
             else "one seeded random K_p subset for every step")
         if out["roofline"] is not None:
-            out["roofline"]["peak_measured_copy_GBs"] = _guarded(lambda: device_copy_gbs(dev))
+            if args.full:
+                out["roofline"]["peak_measured_copy_GBs"] = _guarded(lambda: device_copy_gbs(dev))
             if isinstance(clocks, _ClockSampler):
                 out["gpu_clocks"] = clocks.summary()
             elif clocks is not None:
@@ -579,13 +600,16 @@ def main():
     # configs C3 and C4 take every rank (reported beside the metric, never as `value`).  With
     # several ranks a leg that failed on one rank could leave the others waiting in a
     # collective: a watchdog then prints the metric line without it and ends every rank.
+    def leg(name):  # a side leg runs with --full, unless its own option turns it off
+        return args.full and getattr(args, name) == "auto"
+
     dog = _LegWatchdog(out, rank, LEG_DEADLINE_S) if world > 1 else None
     c3 = c4 = None
-    if args.c3 == "auto":
+    if leg("c3"):
         c3 = _guarded(lambda: c3_leg(n, dev, rank, world, dist))
         if out is not None:
             out["c3_small_blobs"] = c3
-    if args.c4 == "auto":
+    if leg("c4"):
         c4 = _guarded(lambda: c4_leg(n, dev, rank, world, dist))
         if out is not None:
             out["c4_partitioned"] = c4
@@ -598,15 +622,15 @@ def main():
         return
 
     cpu = None
-    if args.cpu_baseline == "auto" and world == 1:
-        cpu = cpu_baseline(args.cpu_sample_mib, n, node=args.node == "auto",
-                           c3_blobs=128 if args.c3 == "auto" else 0)
+    if leg("cpu_baseline") and world == 1:
+        cpu = cpu_baseline(args.cpu_sample_mib, n, node=leg("node"),
+                           c3_blobs=128 if leg("c3") else 0)
     c1c2 = None
-    if args.c3 == "auto" and world == 1:
+    if leg("c3") and world == 1:
         c1c2 = c1_c2_leg(plan, blob, primary, secondary, hashes, blob_id, decoded, idx, n, kp,
                          info.primary_sliver_len, blob_len, stream)
     node = None
-    if args.node == "auto" and world == 1:
+    if leg("node") and world == 1:
         node = _guarded(lambda: node_leg(plan, blob, primary, secondary, hashes, blob_id, n, kp,
                                          ks, s, blob_len, stream))
         if node is not None and cpu is not None and cpu.get("node_side"):
@@ -619,13 +643,13 @@ def main():
         c3["cpu_twin"] = {k: ct.get(k) for k in ("encode_gibs", "cores", "blobs", "wall_s", "ok",
                                                   "sample", "error") if k in ct}
     host_abi = None
-    if args.host_abi == "auto" and world == 1:
+    if leg("host_abi") and world == 1:
         host_abi = _guarded(lambda: host_abi_leg(n, blob_len))
     quilt = None
-    if args.quilt == "auto" and world == 1:
+    if leg("quilt") and world == 1:
         quilt = quilt_leg(n, dev)
     host_io = None
-    if args.host_io == "auto" and world == 1:
+    if leg("host_io") and world == 1:
         del primary, secondary, decoded
         sets.clear()
         torch.cuda.empty_cache()
@@ -672,6 +696,32 @@ class _LegWatchdog:
 
     def cancel(self):
         self._timer.cancel()
+
+
+DUMP_SAMPLE = 1 << 21  # elements kept of each dumped array (float32: 8 MiB per array)
+
+
+def dump_outputs(path, S, n, info, rank):
+    """--dump-outputs: what the caller of the last timed step received, from that step's buffer
+    set S, as <path>/<name>.npy in float32 (ranks above 0: <name>.rank<r>.npy): every sliver-pair
+    hash and the BlobId, and of the primary slivers, the secondary slivers and the decoded blob
+    DUMP_SAMPLE bytes each at fixed seeded offsets (the same offsets in every run with the same
+    arguments).  The blob and the decode subsets are seeded, so two builds of the library can be
+    compared array for array."""
+    import numpy as np
+    import torch
+
+    os.makedirs(path, exist_ok=True)
+    arrays = {"primary_slivers": S["primary"][:n * info.primary_sliver_len],
+              "secondary_slivers": S["secondary"][:n * info.secondary_sliver_len],
+              "sliver_pair_hashes": S["hashes"], "blob_id": S["blob_id"],
+              "decoded_blob": S["decoded"]}
+    for k, (name, t) in enumerate(arrays.items()):
+        if t.numel() > DUMP_SAMPLE:
+            at = np.sort(np.random.default_rng([2024, k]).integers(0, t.numel(), DUMP_SAMPLE))
+            t = t[torch.from_numpy(at).to(t.device)]
+        np.save(os.path.join(path, name + (f".rank{rank}" if rank else "") + ".npy"),
+                t.to(torch.float32).cpu().numpy())
 
 
 def _main_line(args, world, n, kp, ks, s, blob_len, n_present, elapsed, stages, solo_stages,
@@ -800,8 +850,9 @@ def _main_line(args, world, n, kp, ks, s, blob_len, n_present, elapsed, stages, 
         "step_roofline": step_roof,
         "stages_ms_per_step": {k: round(v[0] / max(v[1], 1), 4) for k, v in stages.items()},
         "stages_ms_solo": ({k: round(v[0] / max(v[1], 1), 4) for k, v in solo_stages.items()}
-                           if args.overlap == "on" else None),
+                           if args.overlap == "on" and solo_stages else None),
         "overlap": args.overlap,
+        "full": args.full,
         "cpu_baseline": None,
         "host_io": None,
         "host_abi": None,

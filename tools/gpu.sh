@@ -47,7 +47,7 @@ run_step() {
       return $rc ;;
     prof)
       timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$tag.d" -o run \
-        -- python3 bench.py $SHORT "$@" > "$tag.json" 2> "$tag.err"
+        -- python3 bench.py --full $SHORT "$@" > "$tag.json" 2> "$tag.err"
       local rc=$?
       [ $rc -ne 0 ] && { tail -20 "$tag.err"; return $rc; }
       find "$tag.d" -name '*kernel_stats.csv' -exec cp {} "$tag.kernel_stats.csv" \;

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Per-kernel mean duration over the bench's TIMED launches, from a rocprofv3 kernel trace.
 
-bench.py runs W warmup steps, K timed steps and (with --overlap on) 8 unmeasured + 9 measured solo steps, so
+bench.py --full runs W warmup steps, K timed steps and (with --overlap on) 8 unmeasured + 9 measured solo steps, so
 rocprof's --stats average mixes overlapped and solo launches of the same kernel.  This splits a
 kernel's launches in order: per_step launches per step, the first W*per_step are warmup, the
 next K*per_step timed, the rest solo.
