@@ -25,6 +25,20 @@
  *  - Metadata layout: `hashes` is n_shards x {primary_hash[32], secondary_hash[32]}
  *    ordered by sliver-pair index (metadata.rs:611-643); `blob_id` is 32 bytes
  *    (lib.rs:159-176).
+ *  - Device pointers (every `d_*` argument and `void*` buffer of the `_device` / `_async`
+ *    calls).  Each call states the exact extent of every buffer; ALIGNMENT is by kind:
+ *      symbol-carrying buffers -- blobs, slivers, decoded blobs, recovery symbols, codec
+ *        sources and destinations -- are 2-byte aligned, and so is every byte offset
+ *        (sliver_off[i], sym_off[i]) and stride (blob / sliver / symbol / line strides) that
+ *        places a symbol;
+ *      digest, proof and node buffers -- d_hashes, d_blob_id(s), d_leaves, d_roots, d_proofs,
+ *        d_nodes -- are 16-byte aligned, their strides multiples of 16.
+ *    A violating pointer, offset or stride is refused on the host with RS2_E_INVALID_ARGUMENT
+ *    before anything is enqueued.  No slack beyond the stated extent is required: nothing
+ *    outside the stated extent of an output is written (stride gaps and bytes at or past an
+ *    out_limit / blob_len included), and no result depends on a byte outside the stated extent
+ *    of an input (tests/test_gpu_guard_*.py hold every call to this inside guard bands, at
+ *    every even placement mod 16).
  */
 #ifndef WALRUS_RS2_H
 #define WALRUS_RS2_H
@@ -191,7 +205,11 @@ int rs2_compute_metadata(rs2_plan* plan, const uint8_t* blob, uint8_t* hashes_ou
  * Device form: blob b at d_blobs + b*blob_stride; its slivers in the single-blob layouts at
  * d_primary + b*primary_stride (>= n*primary_sliver_len) and d_secondary + b*secondary_stride;
  * its n pair hashes at d_hashes + b*64*n, its BlobId at d_blob_ids + b*32.  Same stream rules
- * as rs2_encode_device_async. */
+ * as rs2_encode_device_async.  Extents: d_blobs (n_blobs-1)*blob_stride + the last blob's
+ * length; d_primary (n_blobs-1)*primary_stride + n*K_s*s, d_secondary likewise with n*K_p*s
+ * (the stride padding between two blobs' slivers is not written); d_hashes n_blobs*64*n;
+ * d_blob_ids n_blobs*32.  d_blobs, d_primary, d_secondary and the three strides 2-byte
+ * aligned, d_hashes and d_blob_ids 16-byte aligned. */
 int rs2_encode_batch_device_async(rs2_plan* plan, uint32_t n_blobs, const void* d_blobs,
                                   uint64_t blob_stride, const uint64_t* blob_lens, void* d_primary,
                                   uint64_t primary_stride, void* d_secondary,
@@ -236,7 +254,8 @@ int rs2_decode_and_verify(rs2_plan* plan, int axis, uint32_t count, const uint16
  * Same semantics with device buffers: d_blob (blob_len bytes); d_primary n*K_s*s bytes
  * (primary sliver i at i*K_s*s); d_secondary n*K_p*s bytes (secondary sliver j at j*K_p*s);
  * d_hashes n*64; d_blob_id 32.  Work is enqueued on `stream` (hipStream_t, NULL = the
- * plan's stream); the call returns after enqueueing.                                          */
+ * plan's stream); the call returns after enqueueing.  d_blob, d_primary and d_secondary are
+ * 2-byte aligned, d_hashes and d_blob_id 16-byte aligned (all calls of this section).         */
 int rs2_encode_device_async(rs2_plan* plan, const void* d_blob, void* d_primary, void* d_secondary,
                             void* d_hashes, void* d_blob_id, void* stream);
 
@@ -260,8 +279,10 @@ int rs2_encode_device_split_async(rs2_plan* plan, const void* d_blob, void* d_pr
 
 /* Decode from `count` device slivers of `axis`: sliver i lives at d_slivers_base +
  * sliver_off[i] (bytes) and has index sliver_idx[i].  Host-side validation as in
- * rs2_decode_blob (all given slivers must have the correct length).  d_blob_out:
- * blob_len bytes. */
+ * rs2_decode_blob (all given slivers must have the correct length).  Each sliver is
+ * K_s*s (primary) or K_p*s (secondary) bytes; d_blob_out: blob_len bytes, and nothing at or
+ * past blob_len is written (the last symbols are cut, blob_encoding.rs:970-993).
+ * d_slivers_base, every sliver_off[i] and d_blob_out are 2-byte aligned. */
 int rs2_decode_device_async(rs2_plan* plan, int axis, uint32_t count, const uint16_t* sliver_idx,
                             const void* d_slivers_base, const uint64_t* sliver_off,
                             void* d_blob_out, void* stream);
@@ -320,7 +341,8 @@ int rs2_sliver_merkle_roots(uint16_t n_shards, uint16_t symbol_size, int axis, u
 /* Device-resident batched sliver verification: a verifier binds (n_shards, symbol_size,
  * axis) and owns scratch + a stream; d_slivers holds `count` slivers back to back
  * (K*symbol_size bytes each, K = source symbols of the orthogonal axis' code), d_roots
- * receives count*32 bytes.  Same stream conventions as the plan API. */
+ * receives count*32 bytes.  Same stream conventions as the plan API.  d_slivers 2-byte
+ * aligned (count*K*symbol_size bytes), d_roots 16-byte aligned. */
 typedef struct rs2_verifier rs2_verifier;
 int rs2_verifier_create(uint16_t n_shards, uint16_t symbol_size, int axis, rs2_verifier** out);
 int rs2_verifier_roots_device_async(rs2_verifier* v, uint32_t count, const void* d_slivers,
@@ -348,7 +370,9 @@ int rs2_recovery_symbols(uint16_t n_shards, uint16_t symbol_size, int axis, uint
  * target_sliver_index is a HOST array of `count` entries).  d_nodes (may be NULL) receives each
  * tree's full node array (count * n_nodes * 32 bytes, MerkleTree::nodes order: levels from the
  * leaves, each padded to even with the zero node, root last) -- what the service caches per
- * (blob, source sliver) (recovery_symbol_service.rs:132-159). */
+ * (blob, source sliver) (recovery_symbol_service.rs:132-159).  d_symbols: count*symbol_size
+ * bytes, 2-byte aligned like d_slivers; d_proofs: count*path_len*32 bytes and d_nodes, both
+ * 16-byte aligned. */
 int rs2_verifier_recovery_symbols_device_async(rs2_verifier* v, uint32_t count,
                                                const void* d_slivers,
                                                const uint16_t* target_sliver_index,
@@ -376,7 +400,11 @@ int rs2_merkle_proof_roots(uint32_t count, const uint8_t* leaves, uint32_t leaf_
  * once per row / column inside BlobEncoder (blob_encoding.rs:309-354) and once per sliver in
  * SliverData::recovery_symbols (slivers.rs:100-118); the multi-GPU partitioned encode calls it
  * on a rank's row / column range.  Same stream conventions as the plan API (NULL = default
- * stream); one codec per thread, or serialise its use. */
+ * stream); one codec per thread, or serialise its use.  Symbol strides are >= symbol_size;
+ * only the symbols themselves are read and written, never the gaps a larger symbol or line
+ * stride leaves between them, so a buffer's extent ends with its last line's last symbol:
+ * (lines-1)*line_stride + (symbols-1)*sym_stride + symbol_size.  d_src, d_repair and the
+ * four strides are 2-byte aligned. */
 typedef struct rs2_codec rs2_codec;
 int rs2_codec_create(uint16_t k, uint16_t n_shards, uint16_t symbol_size, rs2_codec** out);
 void rs2_codec_destroy(rs2_codec* codec);
@@ -392,7 +420,10 @@ int rs2_codec_encode_device_async(rs2_codec* codec, uint32_t lines, const void* 
  * d_out + l*out_line_stride + i*out_sym_stride (present ones copied, missing ones decoded);
  * bytes at offsets >= out_limit (relative to d_out) are not written (the BlobDecoder's
  * truncation to the blob length, blob_encoding.rs:970-993).  Fewer than k distinct shards ->
- * RS2_E_NOT_ENOUGH_SHARDS.  Column-partitioned multi-GPU decode runs it on a rank's columns. */
+ * RS2_E_NOT_ENOUGH_SHARDS.  Column-partitioned multi-GPU decode runs it on a rank's columns.
+ * d_base, d_out, every sym_off[i] (ignored entries included), line_stride, out_sym_stride
+ * and out_line_stride are 2-byte aligned; out_limit is any byte count (odd ones cut inside
+ * an element). */
 int rs2_codec_decode_device_async(rs2_codec* codec, uint32_t lines, uint32_t count,
                                   const uint16_t* idx, const void* d_base, const uint64_t* sym_off,
                                   uint64_t line_stride, void* d_out, uint64_t out_sym_stride,
@@ -414,19 +445,22 @@ int rs2_copy_segments_device_async(const void* d_src, void* d_dst, uint32_t coun
                                    uint32_t unit, void* stream);
 
 /* leaf_hash (merkle.rs:313-321) of `count` contiguous symbols of symbol_size bytes ->
- * count*32 bytes of digests (blob_encoding.rs:161-196 hashes every expanded symbol). */
+ * count*32 bytes of digests (blob_encoding.rs:161-196 hashes every expanded symbol).
+ * d_symbols (count*symbol_size bytes) 2-byte aligned, d_leaves 16-byte aligned. */
 int rs2_leaf_hashes_device_async(const void* d_symbols, uint64_t count, uint16_t symbol_size,
                                  void* d_leaves, void* stream);
 
 /* MerkleTree::build_from_leaf_hashes(..).root() (merkle.rs:216-266, inner_hash :323-332) of
  * `n_trees` trees of `n_leaves` (1..65535; above 4,096 through a device scratch buffer) leaf
- * digests: leaf i of tree t at d_leaves + t*tree_stride + i*leaf_stride (strides multiples of
- * 16), root t written to d_roots + t*root_stride. */
+ * digests: leaf i of tree t at d_leaves + t*tree_stride + i*leaf_stride, root t (32 bytes)
+ * written to d_roots + t*root_stride; the gaps a larger root_stride leaves are not written.
+ * d_leaves, d_roots and the three strides are multiples of 16. */
 int rs2_merkle_roots_device_async(const void* d_leaves, uint32_t n_trees, uint32_t n_leaves,
                                   uint64_t tree_stride, uint64_t leaf_stride, void* d_roots,
                                   uint64_t root_stride, void* stream);
 
-/* Device form of rs2_blob_id_from_hashes (metadata.rs:571-578, lib.rs:159-176). */
+/* Device form of rs2_blob_id_from_hashes (metadata.rs:571-578, lib.rs:159-176): d_hashes
+ * n_shards*64 bytes, d_blob_id 32 bytes, both 16-byte aligned. */
 int rs2_blob_id_device_async(const void* d_hashes, uint16_t n_shards, uint64_t blob_len,
                              void* d_blob_id, void* stream);
 

@@ -2765,6 +2765,45 @@ hipStream_t pick_stream(rs2_plan* p, void* stream) {
   return abi_stream(stream, p->stream);
 }
 
+// Alignment contract of the device entry points (include/walrus_rs2.h): symbol-carrying
+// buffers, their offsets and strides are 2-byte aligned (the kernels move symbols with 2-byte
+// and possibly misaligned wider accesses, never single bytes of a full element), digest /
+// proof / node buffers 16-byte aligned (uint4 accesses).  Checked on the host before anything
+// is enqueued; NULL passes (optional outputs; required ones are refused as null arguments).
+bool aligned_to(const void* p, uintptr_t a) { return reinterpret_cast<uintptr_t>(p) % a == 0; }
+int check_symbol_ptr(const void* p, const char* what) {
+  if (aligned_to(p, 2)) return RS2_OK;
+  return fail(RS2_E_INVALID_ARGUMENT, std::string(what) + " must be 2-byte aligned");
+}
+int check_symbol_step(uint64_t v, const char* what) {
+  if (v % 2 == 0) return RS2_OK;
+  return fail(RS2_E_INVALID_ARGUMENT, std::string(what) + " must be a multiple of 2 bytes");
+}
+int check_digest_ptr(const void* p, const char* what) {
+  if (aligned_to(p, 16)) return RS2_OK;
+  return fail(RS2_E_INVALID_ARGUMENT, std::string(what) + " must be 16-byte aligned");
+}
+#define ALIGN_TRY(expr)                 \
+  do {                                  \
+    int rc_ = (expr);                   \
+    if (rc_ != RS2_OK) return rc_;      \
+  } while (0)
+
+int check_encode_ptrs(const void* d_blob, const void* d_primary, const void* d_secondary,
+                      const void* d_hashes, const void* d_blob_id) {
+  ALIGN_TRY(check_symbol_ptr(d_blob, "d_blob"));
+  ALIGN_TRY(check_symbol_ptr(d_primary, "d_primary"));
+  ALIGN_TRY(check_symbol_ptr(d_secondary, "d_secondary"));
+  ALIGN_TRY(check_digest_ptr(d_hashes, "d_hashes"));
+  return check_digest_ptr(d_blob_id, "d_blob_id");
+}
+int check_decode_ptrs(uint32_t count, const void* d_slivers_base, const uint64_t* sliver_off,
+                      const void* d_blob_out) {
+  ALIGN_TRY(check_symbol_ptr(d_slivers_base, "d_slivers_base"));
+  for (uint32_t i = 0; i < count; ++i) ALIGN_TRY(check_symbol_step(sliver_off[i], "sliver_off[i]"));
+  return check_symbol_ptr(d_blob_out, "d_blob_out");
+}
+
 }  // namespace
 
 // =============================================================================================
@@ -2973,6 +3012,7 @@ int rs2_encode_device_async(rs2_plan* plan, const void* d_blob, void* d_primary,
                             void* d_hashes, void* d_blob_id, void* stream) {
   if (!plan || !d_primary || !d_secondary || (!d_blob && plan->blob_len))
     return fail(RS2_E_INVALID_ARGUMENT, "null argument");
+  ALIGN_TRY(check_encode_ptrs(d_blob, d_primary, d_secondary, d_hashes, d_blob_id));
   HIP_TRY(hipSetDevice(plan->ctx->device));
   return encode_device(plan, reinterpret_cast<const uint8_t*>(d_blob),
                        reinterpret_cast<uint8_t*>(d_primary), reinterpret_cast<uint8_t*>(d_secondary),
@@ -2984,6 +3024,7 @@ int rs2_compute_metadata_device_async(rs2_plan* plan, const void* d_blob, void* 
                                       void* d_blob_id, void* stream) {
   if (!plan || !d_hashes || !d_blob_id || (!d_blob && plan->blob_len))
     return fail(RS2_E_INVALID_ARGUMENT, "null argument");
+  ALIGN_TRY(check_encode_ptrs(d_blob, nullptr, nullptr, d_hashes, d_blob_id));
   HIP_TRY(hipSetDevice(plan->ctx->device));
   const int64_t n = plan->n;
   HIP_TRY(plan->int_primary.ensure(size_t(n) * primary_len(plan)));
@@ -2999,6 +3040,7 @@ int rs2_encode_device_split_async(rs2_plan* plan, const void* d_blob, void* d_pr
                                   void* primary_stream) {
   if (!plan || !d_primary || !d_secondary || (!d_blob && plan->blob_len) || !primary_stream)
     return fail(RS2_E_INVALID_ARGUMENT, "null argument");
+  ALIGN_TRY(check_encode_ptrs(d_blob, d_primary, d_secondary, d_hashes, d_blob_id));
   hipStream_t st = pick_stream(plan, stream);
   hipStream_t pst = abi_stream(primary_stream, nullptr);
   if (pst == st || pst == plan->side || pst == plan->side_hi)
@@ -3017,6 +3059,7 @@ int rs2_decode_device_async(rs2_plan* plan, int axis, uint32_t count, const uint
     return fail(RS2_E_INVALID_ARGUMENT, "null argument");
   if (axis != RS2_AXIS_PRIMARY && axis != RS2_AXIS_SECONDARY)
     return fail(RS2_E_INVALID_ARGUMENT, "bad axis");
+  ALIGN_TRY(check_decode_ptrs(count, d_slivers_base, sliver_off, d_blob_out));
   HIP_TRY(hipSetDevice(plan->ctx->device));
   std::vector<std::pair<uint16_t, uint32_t>> chosen;
   int rc = select_slivers(plan, axis, count, sliver_idx, nullptr, nullptr, chosen);
@@ -3135,6 +3178,10 @@ int rs2_encode_batch_device_async(rs2_plan* plan, uint32_t n_blobs, const void* 
                                   uint64_t secondary_stride, void* d_hashes, void* d_blob_ids,
                                   void* stream) {
   if (!plan) return fail(RS2_E_INVALID_ARGUMENT, "null plan");
+  ALIGN_TRY(check_encode_ptrs(d_blobs, d_primary, d_secondary, d_hashes, d_blob_ids));
+  ALIGN_TRY(check_symbol_step(blob_stride, "blob_stride"));
+  ALIGN_TRY(check_symbol_step(primary_stride, "primary_stride"));
+  ALIGN_TRY(check_symbol_step(secondary_stride, "secondary_stride"));
   HIP_TRY(hipSetDevice(plan->ctx->device));
   return encode_batch_device(plan, n_blobs, reinterpret_cast<const uint8_t*>(d_blobs),
                              int64_t(blob_stride), blob_lens, reinterpret_cast<uint8_t*>(d_primary),
@@ -3382,6 +3429,7 @@ int rs2_decode_and_verify_device(rs2_plan* plan, int axis, uint32_t count,
   if (consistency_check != RS2_CHECK_SKIP && consistency_check != RS2_CHECK_DEFAULT &&
       consistency_check != RS2_CHECK_STRICT)
     return fail(RS2_E_INVALID_ARGUMENT, "bad consistency check");
+  ALIGN_TRY(check_decode_ptrs(count, d_slivers_base, sliver_off, d_blob_out));
   HIP_TRY(hipSetDevice(plan->ctx->device));
   std::vector<std::pair<uint16_t, uint32_t>> chosen;
   uint32_t pulled = 0;
@@ -3626,6 +3674,8 @@ int verifier_mark_done(rs2_verifier* v, hipStream_t st) {
 int rs2_verifier_roots_device_async(rs2_verifier* v, uint32_t count, const void* d_slivers,
                                     void* d_roots, void* stream) {
   if (!v || (count && (!d_slivers || !d_roots))) return fail(RS2_E_INVALID_ARGUMENT, "null argument");
+  ALIGN_TRY(check_symbol_ptr(d_slivers, "d_slivers"));
+  ALIGN_TRY(check_digest_ptr(d_roots, "d_roots"));
   if (count == 0) return RS2_OK;
   HIP_TRY(hipSetDevice(v->ctx->device));
   hipStream_t st = abi_stream(stream, v->stream);
@@ -3650,6 +3700,10 @@ int rs2_verifier_recovery_symbols_device_async(rs2_verifier* v, uint32_t count,
                                                void* stream) {
   if (!v || (count && (!d_slivers || !target_sliver_index || !d_symbols || !d_proofs)))
     return fail(RS2_E_INVALID_ARGUMENT, "null argument");
+  ALIGN_TRY(check_symbol_ptr(d_slivers, "d_slivers"));
+  ALIGN_TRY(check_symbol_ptr(d_symbols, "d_symbols"));
+  ALIGN_TRY(check_digest_ptr(d_proofs, "d_proofs"));
+  ALIGN_TRY(check_digest_ptr(d_nodes, "d_nodes"));
   for (uint32_t i = 0; i < count; ++i)
     if (target_sliver_index[i] >= v->n)  // slivers.rs check_index -> RecoverySymbolError::IndexTooLarge
       return fail(RS2_E_INVALID_ARGUMENT, "target index too large");
@@ -3895,6 +3949,12 @@ int rs2_codec_encode_device_async(rs2_codec* c, uint32_t lines, const void* d_sr
                                   void* d_repair, uint64_t repair_sym_stride,
                                   uint64_t repair_line_stride, void* stream) {
   if (!c || (lines && (!d_src || !d_repair))) return fail(RS2_E_INVALID_ARGUMENT, "null argument");
+  ALIGN_TRY(check_symbol_ptr(d_src, "d_src"));
+  ALIGN_TRY(check_symbol_ptr(d_repair, "d_repair"));
+  ALIGN_TRY(check_symbol_step(src_sym_stride, "src_sym_stride"));
+  ALIGN_TRY(check_symbol_step(src_line_stride, "src_line_stride"));
+  ALIGN_TRY(check_symbol_step(repair_sym_stride, "repair_sym_stride"));
+  ALIGN_TRY(check_symbol_step(repair_line_stride, "repair_line_stride"));
   if (lines == 0) return RS2_OK;
   if (src_sym_stride < c->s || repair_sym_stride < c->s)
     return fail(RS2_E_INVALID_ARGUMENT, "symbol stride smaller than the symbol");
@@ -3930,6 +3990,12 @@ int rs2_codec_decode_device_async(rs2_codec* c, uint32_t lines, uint32_t count,
   if (!c || (count && (!idx || !sym_off)) || (lines && (!d_base || !d_out)))
     return fail(RS2_E_INVALID_ARGUMENT, "null argument");
   if (out_sym_stride < c->s) return fail(RS2_E_INVALID_ARGUMENT, "symbol stride smaller than the symbol");
+  ALIGN_TRY(check_symbol_ptr(d_base, "d_base"));
+  ALIGN_TRY(check_symbol_ptr(d_out, "d_out"));
+  ALIGN_TRY(check_symbol_step(line_stride, "line_stride"));
+  ALIGN_TRY(check_symbol_step(out_sym_stride, "out_sym_stride"));
+  ALIGN_TRY(check_symbol_step(out_line_stride, "out_line_stride"));
+  for (uint32_t i = 0; i < count; ++i) ALIGN_TRY(check_symbol_step(sym_off[i], "sym_off[i]"));
   const int64_t K = c->k, N = c->n, s = c->s;
   // the first K distinct valid indices (the crate ignores duplicates and invalid indices)
   std::vector<int64_t> present(N, -1);
@@ -4021,6 +4087,8 @@ int rs2_leaf_hashes_device_async(const void* d_symbols, uint64_t count, uint16_t
                                  void* d_leaves, void* stream) {
   if (count && (!d_symbols || !d_leaves)) return fail(RS2_E_INVALID_ARGUMENT, "null argument");
   if (symbol_size % 2) return fail(RS2_E_INVALID_ARGUMENT, "symbol_size must be even");
+  ALIGN_TRY(check_symbol_ptr(d_symbols, "d_symbols"));
+  ALIGN_TRY(check_digest_ptr(d_leaves, "d_leaves"));
   if (count == 0) return RS2_OK;
   Context* ctx = nullptr;
   int rc = get_context(&ctx);
@@ -4037,8 +4105,10 @@ int rs2_merkle_roots_device_async(const void* d_leaves, uint32_t n_trees, uint32
   if (n_trees && (!d_leaves || !d_roots)) return fail(RS2_E_INVALID_ARGUMENT, "null argument");
   if (n_leaves == 0 || n_leaves > uint32_t(kMaxShards))
     return fail(RS2_E_UNSUPPORTED, "trees of 1..65535 leaves supported by this build");
-  if (leaf_stride % 16 || tree_stride % 16 || root_stride % 4)
-    return fail(RS2_E_INVALID_ARGUMENT, "leaf/tree strides must be multiples of 16 bytes");
+  if (leaf_stride % 16 || tree_stride % 16 || root_stride % 16)
+    return fail(RS2_E_INVALID_ARGUMENT, "leaf/tree/root strides must be multiples of 16 bytes");
+  ALIGN_TRY(check_digest_ptr(d_leaves, "d_leaves"));
+  ALIGN_TRY(check_digest_ptr(d_roots, "d_roots"));
   if (n_trees == 0) return RS2_OK;
   Context* ctx = nullptr;
   int rc = get_context(&ctx);
@@ -4060,6 +4130,8 @@ int rs2_blob_id_device_async(const void* d_hashes, uint16_t n_shards, uint64_t b
                              void* d_blob_id, void* stream) {
   if (!d_blob_id || (n_shards && !d_hashes)) return fail(RS2_E_INVALID_ARGUMENT, "null argument");
   if (n_shards > kMaxShards) return fail(RS2_E_UNSUPPORTED, "n_shards above 65535");
+  ALIGN_TRY(check_digest_ptr(d_hashes, "d_hashes"));
+  ALIGN_TRY(check_digest_ptr(d_blob_id, "d_blob_id"));
   Context* ctx = nullptr;
   int rc = get_context(&ctx);
   if (rc != RS2_OK) return rc;
