@@ -21,6 +21,7 @@
 #include <type_traits>
 
 #include "rs2_device.h"
+#include "rs2_kernels.h"
 
 #ifndef RS2_C
 #error "compile with -DRS2_C=<block size>"

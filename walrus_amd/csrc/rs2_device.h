@@ -1,5 +1,6 @@
-// Device-side job descriptors shared by the HIP kernels (rs2_kernels.hip) and the host
-// planner (rs2_engine.cpp).  Plain structs, no HIP types, so both sides agree on layout.
+// Device-side job descriptors shared by the HIP kernels (rs2_codec.hip, rs2_hash.hip,
+// rs2_copy.hip) and the host planner (rs2_engine.cpp).  Plain structs, no HIP types, so both
+// sides agree on layout.
 #pragma once
 #include <stdint.h>
 

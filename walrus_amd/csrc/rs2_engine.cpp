@@ -30,70 +30,7 @@
 
 #include "../../include/walrus_rs2.h"
 #include "rs2_device.h"
-
-// ---- kernel launchers (rs2_codec.hip per block size, rs2_hash.hip) --------------------------
-extern "C" {
-#define RS2_DECL(CC)                                                                      \
-  hipError_t rs2k_launch_codec_##CC(const rs2::CodecJob* job, int n_tiles, int n_lines, \
-                                    int n_z, int mode, hipStream_t stream);
-RS2_DECL(1)
-RS2_DECL(2)
-RS2_DECL(4)
-RS2_DECL(8)
-RS2_DECL(16)
-RS2_DECL(32)
-RS2_DECL(64)
-RS2_DECL(128)
-RS2_DECL(256)
-RS2_DECL(512)
-#undef RS2_DECL
-hipError_t rs2k_launch_leaf_hash(rs2::SymbolMap map, int mode, int64_t count, int n_blobs,
-                                 uint8_t* d_out, hipStream_t stream);
-hipError_t rs2k_launch_merkle_trees(const uint8_t* d_leaves, int n, int n_row_trees,
-                                    int n_col_trees, int64_t row_base, int64_t row_stride,
-                                    int64_t col_base, int64_t col_stride, uint8_t* d_out,
-                                    int64_t out_stride, hipStream_t stream,
-                                    uint8_t* d_nodes = nullptr, int64_t nodes_stride = 0,
-                                    int n_blobs = 1, int64_t leaves_blob_stride = 0,
-                                    int64_t out_blob_stride = 0, uint8_t* d_scratch = nullptr);
-hipError_t rs2k_launch_batch_blob_copy(const uint8_t* src, int64_t src_stride,
-                                       const uint64_t* d_blob_lens, int64_t msg, uint8_t* dst,
-                                       int64_t dst_stride, int n_blobs, hipStream_t stream);
-hipError_t rs2k_launch_proof_gather(const uint8_t* d_sys, const uint8_t* d_rep, int n, int k,
-                                    int s, const uint8_t* d_nodes, int64_t nodes_stride,
-                                    const uint16_t* d_targets, int count, int path_len,
-                                    uint8_t* d_sym, uint8_t* d_proof, hipStream_t stream);
-hipError_t rs2k_launch_proof_roots(const uint8_t* d_leaf_digests, const uint32_t* d_leaf_index,
-                                   const uint8_t* d_paths, int path_len, int count,
-                                   uint8_t* d_roots, hipStream_t stream);
-hipError_t rs2k_launch_merkle_root(const uint8_t* d_pair_hashes, int n, uint64_t blob_len,
-                                   uint8_t* d_blob_id, hipStream_t stream, int n_blobs = 1,
-                                   const uint64_t* d_blob_lens = nullptr);
-hipError_t rs2k_launch_merkle_level(const uint8_t* d_in, int64_t cnt, uint8_t* d_out,
-                                    hipStream_t stream);
-hipError_t rs2k_launch_symbol_copy(const uint8_t* src, const int64_t* d_src_a, int64_t ssb,
-                                   uint8_t* dst, const int64_t* d_dst_a, int64_t dsb, int count_a,
-                                   int count_b, int s, int64_t dst_limit, hipStream_t stream);
-hipError_t rs2k_launch_segment_copy(const uint8_t* src, uint8_t* dst, uint32_t count_a,
-                                    const int64_t* d_src_a, const int64_t* d_dst_a, uint32_t count_b,
-                                    int64_t ssb, int64_t dsb, uint32_t len, int unit,
-                                    hipStream_t stream);
-hipError_t rs2k_launch_quilt_layout(int n_rows, int n_cols, int s, const uint8_t* payload,
-                                    const int64_t* col_off, const uint32_t* col_len,
-                                    uint8_t* quilt, hipStream_t stream);
-hipError_t rs2k_launch_host_upload(const void* src, void* dst, int64_t n, uint64_t* done,
-                                   uint64_t gen, hipStream_t stream);
-hipError_t rs2k_launch_upload_signal(uint64_t* done, uint64_t gen, hipStream_t stream);
-hipError_t rs2k_launch_codec_big_512(const rs2::CodecJobBig* d_job, int n_tiles, int n_lines,
-                                     int n_z, int mode, hipStream_t stream);
-hipError_t rs2k_launch_tail_rows(const uint8_t* src, int64_t have, uint8_t* dst, int64_t total,
-                                 hipStream_t stream);
-hipError_t rs2k_launch_row_gather(const uint8_t* src, const int64_t* d_src_off, uint8_t* dst,
-                                  int64_t row_bytes, int rows, hipStream_t stream);
-hipError_t rs2k_launch_build_mul_tables(const uint16_t* d_exp, const uint16_t* d_log,
-                                        const uint16_t* d_logs, int count, uint16_t* d_out,
-                                        hipStream_t stream);
-}
+#include "rs2_kernels.h"
 
 namespace rs2 {
 namespace {
@@ -115,6 +52,13 @@ int fail(int code, const std::string& msg) {
       return fail(RS2_E_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_));    \
   } while (0)
 
+// Return the first failing status of a chain of engine calls.
+#define RS2_TRY(expr)                   \
+  do {                                  \
+    int rc_ = (expr);                   \
+    if (rc_ != RS2_OK) return rc_;      \
+  } while (0)
+
 // Diagnostic: RS2_HOST_TRACE=<path> appends one "name ms" line per host-timed section (the
 // decode's per-pattern setup), so the cost of individual calls can be read, not only the mean.
 void host_trace(const char* name, double ms) {
@@ -127,6 +71,13 @@ void host_trace(const char* name, double ms) {
   std::lock_guard<std::mutex> lk(mu);
   std::fprintf(f, "%s %.4f\n", name, ms);
   std::fflush(f);
+}
+
+// An integer A/B knob from the environment (`dflt` when unset).  Callers keep the value in a
+// function-local static, so every knob is read once per process.
+int env_int(const char* name, int dflt) {
+  const char* e = std::getenv(name);
+  return e ? std::atoi(e) : dflt;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -273,6 +224,16 @@ bool rate_supported(uint32_t k, uint32_t r) {
 // double-buffered plans fit, a transient 4 GiB blob's do not stay) go back to hipFree, and
 // rs2_device_memory_trim hands every wholly free segment back on request.
 thread_local bool t_quiesced = false;  // the releasing owner has drained its streams
+
+// For its scope the calling thread's releases count as quiesced: the owner has drained every
+// stream and event its buffers' work ran behind, so their ranges are free at once.
+struct Quiesced {
+  const bool prev = t_quiesced;
+  Quiesced() { t_quiesced = true; }
+  ~Quiesced() { t_quiesced = prev; }
+  Quiesced(const Quiesced&) = delete;
+  Quiesced& operator=(const Quiesced&) = delete;
+};
 
 struct DevArena {
   static constexpr size_t kGrain = 256;
@@ -583,8 +544,7 @@ class HostPool {
   void start() {
     std::call_once(once_, [this] {
       int n = int(std::thread::hardware_concurrency());
-      const char* e = std::getenv("RS2_HOST_THREADS");
-      int want = e ? std::atoi(e) : 16;
+      int want = env_int("RS2_HOST_THREADS", 16);
       want = std::max(1, std::min(want, std::max(n, 1)));
       for (int i = 0; i + 1 < want; ++i) th_.emplace_back([this] { loop(); });
     });
@@ -659,13 +619,13 @@ void par_copy(HostPool& pool, const std::vector<Seg>& segs, bool to_host) {
 // way in every run, whatever its length, from pageable sources (gpurun_out/r05a traces: the
 // 0.6 ms per step the 20-step driver run showed as dec_plan_host) and 15-28 ms from pinned ones
 // (gpurun_out/r05c).  So the data goes into a pinned, device-mapped slot and a copy kernel
-// (rs2_hash.hip host_upload_kernel) moves it in stream order like any other launch.  kSlots
+// (rs2_copy.hip host_upload_kernel) moves it in stream order like any other launch.  kSlots
 // slots of kSlotBytes, pinned once per device at first use and never grown; uploads take them
 // round-robin.
 //
 // Reuse of a slot.  Every use of slot k carries a generation number; the kernel that last reads
 // the slot stores that generation into word k of a coherent, device-mapped host array when it
-// has finished (rs2_hash.hip host_upload_kernel / upload_signal_kernel),
+// has finished (rs2_copy.hip host_upload_kernel / upload_signal_kernel),
 // and the host rewrites the slot only once it reads that generation there.  No HIP event is
 // involved, so the wait depends on nothing but the copy having run -- not on the stream it ran
 // on still existing (plans, verifiers and caller streams come and go between uploads; an event
@@ -698,7 +658,7 @@ class UploadSlots {
     uint8_t* slot = base_ + size_t(k) * kSlotBytes;
     std::memcpy(slot, src, n);
     const uint64_t g = ++gen_counter_;
-    // a copy kernel reading the mapped slot, not hipMemcpyAsync (rs2_hash.hip host_upload_kernel);
+    // a copy kernel reading the mapped slot, not hipMemcpyAsync (rs2_copy.hip host_upload_kernel);
     // its one workgroup reports generation g in word k once every load of the slot has returned
     e = rs2k_launch_host_upload(dev_base_ + size_t(k) * kSlotBytes, dst, int64_t(n),
                                 done_dev_ + k, g, st);
@@ -867,8 +827,7 @@ int get_context(Context** out) {
   if (hipGetDeviceCount(&n) != hipSuccess || n <= g_device)
     return fail(RS2_E_DEVICE, "no HIP device available");
   auto ctx = std::make_unique<Context>();
-  const int rc = ctx->init(g_device);
-  if (rc != RS2_OK) return rc;
+  RS2_TRY(ctx->init(g_device));
   *out = ctx.get();
   g_ctx.emplace(g_device, std::move(ctx));
   return RS2_OK;
@@ -916,9 +875,49 @@ void narrow_job(const CodecJobBig& b, CodecJob& s) {
   std::copy(b.pair_nw, b.pair_nw + kMaxBlocks, s.pair_nw);
 }
 
+// CUs of the current device (0 when it cannot be read)
+int cu_count() {
+  int dev = 0, cus = 0;
+  if (hipGetDevice(&dev) != hipSuccess ||
+      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+    return 0;
+  return cus;
+}
+
+// The per-launch fields of a job over n_blobs blobs: the lines (folded into grid.x with the
+// element pairs) and the blobs' strides.  Returns the launch's tiles, or -1 when they do not
+// fit a grid dimension.
+int set_launch_shape(CodecScalars& job, int n_lines, int n_blobs, int64_t in_bs, int64_t out_bs,
+                     int64_t cp_bs) {
+  job.n_lines = n_lines;
+  const int64_t per_blob = (int64_t(n_lines) * job.pairs_span + 63) / 64;
+  const int64_t tiles64 = per_blob * n_blobs;
+  if (tiles64 > 0x7FFFFFFF) return -1;
+  job.tiles_per_blob = n_blobs > 1 ? int(per_blob) : 0;
+  job.in_blob_stride = in_bs;
+  job.out_blob_stride = out_bs;
+  job.copy_blob_stride = cp_bs;
+  job.stamps = nullptr;
+  return int(tiles64);
+}
+
+// A job of more than kMaxBlocks blocks (C = 512): one-tile kernels reading the job from device
+// memory (no pipelined / persistent variants, no stamps).
 hipError_t launch_codec_big(const CodecJobBig& job_in, int n_lines, int n_z, int mode,
                             hipStream_t st, int n_blobs, int64_t in_bs, int64_t out_bs,
-                            int64_t cp_bs);
+                            int64_t cp_bs) {
+  if (mode != kModeRows && mode != kModeCols && mode != kModeDecode) return hipErrorInvalidValue;
+  auto job = std::make_unique<CodecJobBig>(job_in);
+  const int tiles = set_launch_shape(*job, n_lines, n_blobs, in_bs, out_bs, cp_bs);
+  if (tiles < 0) return hipErrorInvalidValue;
+  job->tile_ctr = nullptr;
+  Context* ctx = nullptr;
+  if (get_context(&ctx) != RS2_OK) return hipErrorInvalidDevice;
+  return ctx->uploads.launch_with_job(job.get(), sizeof(CodecJobBig), st, [&](uint8_t* d) {
+    return rs2k_launch_codec_big_512(reinterpret_cast<const CodecJobBig*>(d), tiles, 1, n_z, mode,
+                                     st);
+  });
+}
 
 hipError_t launch_codec_c(int C, const CodecJobBig& job_big, int n_lines, int n_z, int mode,
                           hipStream_t st, int n_blobs = 1, int64_t in_bs = 0, int64_t out_bs = 0,
@@ -932,17 +931,9 @@ hipError_t launch_codec_c(int C, const CodecJobBig& job_big, int n_lines, int n_
   }
   CodecJob job;
   narrow_job(job_big, job);
-  job.n_lines = n_lines;
-  const int64_t per_blob = (int64_t(n_lines) * job.pairs_span + 63) / 64;
-  const int64_t tiles64 = per_blob * n_blobs;
-  if (tiles64 > 0x7FFFFFFF) return hipErrorInvalidValue;
-  const int tiles = int(tiles64);
-  job.tiles_per_blob = n_blobs > 1 ? int(per_blob) : 0;
-  job.in_blob_stride = in_bs;
-  job.out_blob_stride = out_bs;
-  job.copy_blob_stride = cp_bs;
+  const int tiles = set_launch_shape(job, n_lines, n_blobs, in_bs, out_bs, cp_bs);
+  if (tiles < 0) return hipErrorInvalidValue;
   n_lines = 1;  // lines are folded into grid.x
-  job.stamps = nullptr;
   // Shared-input jobs whose last output block's active waves fit below the input's run as the
   // persistent tile-pipelined kernel (rs2_codec.hip cols_pipe_body): one workgroup per CU, each
   // walking a contiguous tile range.  RS2_PIPE=0: never (A/B knob).
@@ -951,16 +942,11 @@ hipError_t launch_codec_c(int C, const CodecJobBig& job_big, int n_lines, int n_
        (mode == kModeRows && !job.shared_in && job.n_out == 1)) &&
       n_z == 1 && job.n_out >= 1 && C >= 2 * kPpwTarget) {
     static const int pipe_wgs = [] {
-      const char* e = std::getenv("RS2_PIPE");
-      if (e && std::atoi(e) == 0) return 0;
-      int dev = 0, cus = 0;
-      if (hipGetDevice(&dev) != hipSuccess ||
-          hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-        return 0;
-      const int k = e ? std::max(1, std::atoi(e)) : 1;  // RS2_PIPE=k: k workgroups per CU
-      const char* nw_env = std::getenv("RS2_PIPE_WGS");   // A/B: an absolute workgroup count
-      if (nw_env && std::atoi(nw_env) > 0) return std::atoi(nw_env);
-      return cus * k;
+      const int k = env_int("RS2_PIPE", 1);  // RS2_PIPE=k: k workgroups per CU
+      const int cus = k == 0 ? 0 : cu_count();
+      if (cus == 0) return 0;
+      const int wgs = env_int("RS2_PIPE_WGS", 0);  // A/B: an absolute workgroup count
+      return wgs > 0 ? wgs : cus * std::max(1, k);
     }();
     const int nw = C / kPpwTarget;
     auto waves = [](int count) { return (count + kPpwTarget - 1) / kPpwTarget; };
@@ -981,10 +967,7 @@ hipError_t launch_codec_c(int C, const CodecJobBig& job_big, int n_lines, int n_
       grid_tiles = std::min(tiles, pipe_wgs);
       // RS2_PIPE_DYN=1: dynamic tile order (A/B knob; static ranges measured 82.5 vs 81.4 GiB/s,
       // and with a high-priority decode stream 63.0 vs 63.2: profiles/r03/exp/dyn/)
-      static const bool dyn = [] {
-        const char* e = std::getenv("RS2_PIPE_DYN");
-        return e && std::atoi(e) != 0;
-      }();
+      static const bool dyn = env_int("RS2_PIPE_DYN", 0) != 0;
       job.tile_ctr = dyn ? tile_ctr : nullptr;
     }
   }
@@ -992,13 +975,8 @@ hipError_t launch_codec_c(int C, const CodecJobBig& job_big, int n_lines, int n_
   // (k workgroups per CU) is set: A/B knob
   if (mode == kModeDecode && n_z == 1) {
     static const int dec_wgs = [] {
-      const char* e = std::getenv("RS2_DEC_PERSIST");
-      if (!e || std::atoi(e) <= 0) return 0;
-      int dev = 0, cus = 0;
-      if (hipGetDevice(&dev) != hipSuccess ||
-          hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-        return 0;
-      return cus * std::atoi(e);
+      const int k = env_int("RS2_DEC_PERSIST", 0);
+      return k > 0 ? cu_count() * k : 0;
     }();
     if (dec_wgs > 0 && tiles > dec_wgs) {
       mode = kModeDecodePersist;
@@ -1030,34 +1008,6 @@ hipError_t launch_codec_c(int C, const CodecJobBig& job_big, int n_lines, int n_
   }
   if (le != hipSuccess || !stamping) return le;
   return stamp_dump(C, mode, grid_tiles, n_z, job.stamps, st);
-}
-
-int get_context(Context** out);
-
-// A job of more than kMaxBlocks blocks (C = 512): one-tile kernels reading the job from device
-// memory (no pipelined / persistent variants, no stamps).
-hipError_t launch_codec_big(const CodecJobBig& job_in, int n_lines, int n_z, int mode,
-                            hipStream_t st, int n_blobs, int64_t in_bs, int64_t out_bs,
-                            int64_t cp_bs) {
-  if (mode != kModeRows && mode != kModeCols && mode != kModeDecode) return hipErrorInvalidValue;
-  auto job = std::make_unique<CodecJobBig>(job_in);
-  job->n_lines = n_lines;
-  const int64_t per_blob = (int64_t(n_lines) * job->pairs_span + 63) / 64;
-  const int64_t tiles64 = per_blob * n_blobs;
-  if (tiles64 > 0x7FFFFFFF) return hipErrorInvalidValue;
-  job->tiles_per_blob = n_blobs > 1 ? int(per_blob) : 0;
-  job->in_blob_stride = in_bs;
-  job->out_blob_stride = out_bs;
-  job->copy_blob_stride = cp_bs;
-  job->stamps = nullptr;
-  job->tile_ctr = nullptr;
-  Context* ctx = nullptr;
-  if (get_context(&ctx) != RS2_OK) return hipErrorInvalidDevice;
-  const int tiles = int(tiles64);
-  return ctx->uploads.launch_with_job(job.get(), sizeof(CodecJobBig), st, [&](uint8_t* d) {
-    return rs2k_launch_codec_big_512(reinterpret_cast<const CodecJobBig*>(d), tiles, 1, n_z, mode,
-                                     st);
-  });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1148,10 +1098,8 @@ struct Dec1DLease {
     }
     (void)hipStreamSynchronize(d->st);
     (void)hipStreamDestroy(d->st);
-    const bool prev = t_quiesced;
-    t_quiesced = true;  // drained above: its ranges may be reused at once
+    const Quiesced quiesced;  // drained above: its ranges may be reused at once
     delete d;
-    t_quiesced = prev;
   }
 };
 
@@ -1164,8 +1112,7 @@ std::atomic<uint32_t> g_block_max{0};
 uint32_t block_max() {
   uint32_t v = g_block_max.load(std::memory_order_relaxed);
   if (v) return v;
-  const char* e = std::getenv("RS2_BLOCK_MAX");
-  uint32_t x = e ? uint32_t(std::atoi(e)) : uint32_t(kMaxC);
+  uint32_t x = uint32_t(env_int("RS2_BLOCK_MAX", kMaxC));
   if (x < 1 || x > uint32_t(kMaxC) || (x & (x - 1))) x = uint32_t(kMaxC);
   g_block_max.store(x, std::memory_order_relaxed);
   return x;
@@ -1636,10 +1583,7 @@ int plan_decode(const DecodeSpec& sp, PlannedJob& pj) {
     return (count + ppw - 1) / ppw;
   };
   int pair_p = -1, pair_nw = 0;
-  static const bool no_pair = [] {
-    const char* e = std::getenv("RS2_PAIR");  // A/B knob: 0 = never pair
-    return e && std::atoi(e) == 0;
-  }();
+  static const bool no_pair = env_int("RS2_PAIR", 1) == 0;  // A/B knob: 0 = never pair
   if (!no_pair && nw > 1 && out_blocks.size() == 1) {
     const int o = out_blocks[0];
     for (size_t qi = 0; qi < in_blocks.size() && pair_p < 0; ++qi) {
@@ -1750,8 +1694,7 @@ int plan_decode(const DecodeSpec& sp, PlannedJob& pj) {
 // Upload a decode job's arrays and build its per-position tables on the device.
 int bind_decode(Context* ctx, PlannedJob& pj, JobMem& mem, hipStream_t st) {
   CodecJobBig& j = pj.job;
-  const int rc = bind_job(ctx, pj, mem, st);
-  if (rc != RS2_OK) return rc;
+  RS2_TRY(bind_job(ctx, pj, mem, st));
   const size_t npre = pj.pre_logs.size(), npost = pj.post_logs.size();
   std::vector<uint16_t>& logs = pj.logs;
   logs.resize(npre + npost);
@@ -1772,6 +1715,30 @@ int bind_decode(Context* ctx, PlannedJob& pj, JobMem& mem, hipStream_t st) {
     j.out[o].post_tab = mem.pre_tab.as<uint16_t>() + (npre + size_t(o) * pj.C) * kTabU16;
   return RS2_OK;
 }
+
+// One decode slot of a blob plan or a 1D codec.  Each holds two, taken in turn, so back-to-back
+// async decodes never overwrite live arrays: a slot is rewritten only after `done`, the event
+// of its last launch.
+struct DecodeSlot {
+  PlannedJob job;
+  JobMem mem;
+  // present originals copied outside the codec (when not fused into it): offsets on the device
+  // and the host vectors they are uploaded from, alive until `done`
+  DevBuf copy_src, copy_dst;
+  std::vector<int64_t> copy_src_h, copy_dst_h;
+  hipEvent_t done = nullptr;
+  // the erasure pattern / buffers the slot's job was planned for: a repeat decode with the same
+  // key reuses the slot's tables and offsets on the device instead of re-planning (empty: the
+  // slot is never reused that way)
+  std::vector<int64_t> key;
+  bool fused = false;  // the job writes the present originals from its own loads
+  DecodeSlot() = default;
+  DecodeSlot(const DecodeSlot&) = delete;
+  DecodeSlot& operator=(const DecodeSlot&) = delete;
+  ~DecodeSlot() {
+    if (done) (void)hipEventDestroy(done);
+  }
+};
 
 constexpr int kMerkleMaxLeaves = 4096;  // rs2_hash.hip kMerkleMax (one-wave / one-WG trees)
 // n_shards above that: the trees' level L (the first with ceil(n / 2^L) <= 4,096 nodes) is
@@ -1863,8 +1830,7 @@ struct StagerLease {
     std::lock_guard<std::mutex> lk(pool.mu);
     if (!pool.primed) {
       pool.primed = true;
-      const char* e = std::getenv("RS2_STAGING_RINGS");
-      for (int i = 0, k = e ? std::min(16, std::atoi(e)) : 0; i < k; ++i) {
+      for (int i = 0, k = std::min(16, env_int("RS2_STAGING_RINGS", 0)); i < k; ++i) {
         auto sg = std::make_unique<Stager>();
         if (sg->init() != RS2_OK) break;
         pool.free.push_back(std::move(sg));
@@ -2000,8 +1966,7 @@ std::vector<Seg> issue_direct(const std::vector<Seg>& segs, bool to_host, hipStr
 // registered caller memory is read by the DMA itself, which every host-buffer call waits for
 // before it returns)
 int stage_h2d(Context* ctx, Stager& sg, const std::vector<Seg>& segs_all, hipStream_t st) {
-  int rc = sg.init();
-  if (rc != RS2_OK) return rc;
+  RS2_TRY(sg.init());
   hipError_t de;
   bool any;
   const std::vector<Seg> segs = issue_direct(segs_all, false, st, &de, &any);
@@ -2019,8 +1984,7 @@ int stage_h2d(Context* ctx, Stager& sg, const std::vector<Seg>& segs_all, hipStr
 
 // device -> host after the work queued on st; returns when every byte is in the host buffers
 int stage_d2h(Context* ctx, Stager& sg, const std::vector<Seg>& segs_all, hipStream_t st) {
-  int rc = sg.init();
-  if (rc != RS2_OK) return rc;
+  RS2_TRY(sg.init());
   hipError_t de;
   bool any;
   const std::vector<Seg> segs = issue_direct(segs_all, true, st, &de, &any);
@@ -2038,12 +2002,12 @@ int stage_d2h(Context* ctx, Stager& sg, const std::vector<Seg>& segs_all, hipStr
     return RS2_OK;
   };
   for (size_t k = 0; k < pcs.size() && k < size_t(Stager::kSlots); ++k)
-    if ((rc = issue(k)) != RS2_OK) return rc;
+    RS2_TRY(issue(k));
   for (size_t k = 0; k < pcs.size(); ++k) {
     const int sl = int(k % Stager::kSlots);
     HIP_TRY(hipEventSynchronize(sg.ev[sl]));
     par_copy(ctx->pool, slot_view(pcs[k], sg.slot(sl)), true);
-    if (k + Stager::kSlots < pcs.size() && (rc = issue(k + Stager::kSlots)) != RS2_OK) return rc;
+    if (k + Stager::kSlots < pcs.size()) RS2_TRY(issue(k + Stager::kSlots));
   }
   return RS2_OK;
 }
@@ -2096,16 +2060,8 @@ struct rs2_plan {
       batch_hashes, batch_ids;
   std::vector<uint64_t> batch_lens_h;
   // decode (two slots so back-to-back async decodes never overwrite live arrays)
-  PlannedJob dec_job[2];
-  JobMem dec_mem[2];
-  DevBuf dec_copy_src[2], dec_copy_dst[2];
-  std::vector<int64_t> dec_copy_src_h[2], dec_copy_dst_h[2];  // alive until dec_done[slot]
-  hipEvent_t dec_done[2] = {nullptr, nullptr};
+  DecodeSlot dec[2];
   int dec_slot = 0;
-  // the erasure pattern / buffers a slot's decode job was planned for: a repeat decode with the
-  // same key reuses the slot's tables and offsets on the device instead of re-planning
-  std::vector<int64_t> dec_key[2];
-  bool dec_fused[2] = {false, false};
   // host-buffer API: pinned staging ring, a copy stream for the sliver D2H (released by a split
   // encode as soon as the primary slivers are final), row gather offsets of the Default check
   Stager* stage = nullptr;  // the pinned ring leased for the host-buffer call in progress
@@ -2122,8 +2078,6 @@ struct rs2_plan {
     std::vector<std::string> order;
   } prof;
   ~rs2_plan() {
-    for (auto& e : dec_done)
-      if (e) (void)hipEventDestroy(e);
     for (auto& e : prof.free_events) (void)hipEventDestroy(e);
     for (auto& pe : prof.pending) (void)hipEventDestroy(pe.second);
     if (fork_ev) (void)hipEventDestroy(fork_ev);
@@ -2178,16 +2132,10 @@ struct rs2_codec {
   JobMem enc_mem;
   int64_t enc_key[4] = {-1, -1, -1, -1};
   hipEvent_t enc_done = nullptr;
-  PlannedJob dec[2];
-  JobMem dec_mem[2];
-  DevBuf copy_src[2], copy_dst[2];
-  std::vector<int64_t> copy_src_h[2], copy_dst_h[2];
-  hipEvent_t dec_done[2] = {nullptr, nullptr};
+  DecodeSlot dec[2];
   int dec_slot = 0;
   ~rs2_codec() {
     if (enc_done) (void)hipEventDestroy(enc_done);
-    for (auto& e : dec_done)
-      if (e) (void)hipEventDestroy(e);
   }
 };
 
@@ -2209,13 +2157,8 @@ void mark(rs2_plan* p, const char* name, hipStream_t st) {
   pr.pending.emplace_back(name, e);
 }
 
-// host time since t0 under `name` (profiling on): the erasure-pattern planning of a decode
-void prof_host(rs2_plan* p, const char* name, std::chrono::steady_clock::time_point t0) {
-  auto& pr = p->prof;
-  if (!pr.on) return;
-  const double ms =
-      std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  host_trace(name, ms);
+// one more span of `ms` under `name` in the profiler's histogram
+void prof_add(rs2_plan::Prof& pr, const std::string& name, double ms) {
   auto it = pr.acc.find(name);
   if (it == pr.acc.end()) {
     pr.order.push_back(name);
@@ -2225,6 +2168,16 @@ void prof_host(rs2_plan* p, const char* name, std::chrono::steady_clock::time_po
   it->second.second += 1;
 }
 
+// host time since t0 under `name` (profiling on): the erasure-pattern planning of a decode
+void prof_host(rs2_plan* p, const char* name, std::chrono::steady_clock::time_point t0) {
+  auto& pr = p->prof;
+  if (!pr.on) return;
+  const double ms =
+      std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  host_trace(name, ms);
+  prof_add(pr, name, ms);
+}
+
 void prof_collect(rs2_plan* p) {
   auto& pr = p->prof;
   hipEvent_t prev = nullptr;
@@ -2232,15 +2185,7 @@ void prof_collect(rs2_plan* p) {
     (void)hipEventSynchronize(pe.second);
     if (prev && !pe.first.empty()) {
       float ms = 0.f;
-      if (hipEventElapsedTime(&ms, prev, pe.second) == hipSuccess) {
-        auto it = pr.acc.find(pe.first);
-        if (it == pr.acc.end()) {
-          pr.order.push_back(pe.first);
-          it = pr.acc.emplace(pe.first, std::make_pair(0.0, 0u)).first;
-        }
-        it->second.first += ms;
-        it->second.second += 1;
-      }
+      if (hipEventElapsedTime(&ms, prev, pe.second) == hipSuccess) prof_add(pr, pe.first, ms);
     }
     prev = pe.second;
   }
@@ -2264,19 +2209,15 @@ int bind_encode_buffers(rs2_plan* p, uint8_t* d_primary, uint8_t* d_secondary, h
   if (p->enc_done) HIP_TRY(hipEventSynchronize(p->enc_done));
   p->bound_primary = p->bound_secondary = p->bound_both = nullptr;  // valid after a full rebind
   const int64_t s = p->s, n = p->n, kp = p->kp, ks = p->ks;
-  int rc;
   // rows: secondary encoding (K = K_s) of primary slivers 0..K_p -> secondary slivers K_s..n
-  rc = plan_encode(
+  RS2_TRY(plan_encode(
       uint32_t(ks), uint32_t(n - ks), int(s), d_primary, ks * s, [&](uint32_t c) { return int64_t(c) * s; },
-      d_secondary, s, [&](uint32_t j) { return (ks + int64_t(j)) * kp * s; }, INT64_MAX, p->row);
-  if (rc != RS2_OK) return rc;
-  rc = bind_encode(p->ctx, p->row, p->row_mem, st);
-  if (rc != RS2_OK) return rc;
+      d_secondary, s, [&](uint32_t j) { return (ks + int64_t(j)) * kp * s; }, INT64_MAX, p->row));
+  RS2_TRY(bind_encode(p->ctx, p->row, p->row_mem, st));
   // systematic columns c < K_s: primary encoding (K = K_p) -> primary slivers K_p..n, column c
-  rc = plan_encode(
+  RS2_TRY(plan_encode(
       uint32_t(kp), uint32_t(n - kp), int(s), d_primary, s, [&](uint32_t r) { return int64_t(r) * ks * s; },
-      d_primary, s, [&](uint32_t j) { return (kp + int64_t(j)) * ks * s; }, INT64_MAX, p->col_sys);
-  if (rc != RS2_OK) return rc;
+      d_primary, s, [&](uint32_t j) { return (kp + int64_t(j)) * ks * s; }, INT64_MAX, p->col_sys));
   // the column loads are exactly the systematic secondary slivers (secondary c, row r =
   // primary r, column c): write them out from the same loads instead of a transpose pass
   p->sys_fused = false;
@@ -2284,16 +2225,13 @@ int bind_encode_buffers(rs2_plan* p, uint8_t* d_primary, uint8_t* d_secondary, h
     set_copy(p->col_sys, d_secondary, kp * s, INT64_MAX, [&](uint32_t r) { return int64_t(r) * s; });
     p->sys_fused = copy_covered(p->col_sys);
   }
-  rc = bind_encode(p->ctx, p->col_sys, p->col_sys_mem, st);
-  if (rc != RS2_OK) return rc;
+  RS2_TRY(bind_encode(p->ctx, p->col_sys, p->col_sys_mem, st));
   // the column loads are also every byte of the blob: when one shared-input block holds the
   // K_p rows in order (position r at r * K_s * s), col_sys reads the blob in place and writes
   // the systematic primary slivers itself instead of a separate blob copy
   p->prim_fused = false;
-  static const bool fuse_env = [] {  // RS2_FUSE_BLOB=0: the separate blob copy (A/B knob)
-    const char* e = std::getenv("RS2_FUSE_BLOB");
-    return !(e && std::atoi(e) == 0);
-  }();
+  // RS2_FUSE_BLOB=0: the separate blob copy (A/B knob)
+  static const bool fuse_env = env_int("RS2_FUSE_BLOB", 1) != 0;
   if (fuse_env && p->sys_fused && p->col_sys.mode == kModeCols && p->col_sys.job.n_in == 1 &&
       p->col_sys.job.in[0].count == int(kp)) {
     bool in_order = true;
@@ -2303,13 +2241,11 @@ int bind_encode_buffers(rs2_plan* p, uint8_t* d_primary, uint8_t* d_secondary, h
     p->prim_fused = in_order;
   }
   // repair columns c >= K_s: from secondary slivers K_s..n -> the both-repair quadrant
-  rc = plan_encode(
+  RS2_TRY(plan_encode(
       uint32_t(kp), uint32_t(n - kp), int(s), d_secondary + ks * kp * s, kp * s,
       [&](uint32_t r) { return int64_t(r) * s; }, d_both, s,
-      [&](uint32_t j) { return int64_t(j) * (n - ks) * s; }, INT64_MAX, p->col_rep);
-  if (rc != RS2_OK) return rc;
-  rc = bind_encode(p->ctx, p->col_rep, p->col_rep_mem, st);
-  if (rc != RS2_OK) return rc;
+      [&](uint32_t j) { return int64_t(j) * (n - ks) * s; }, INT64_MAX, p->col_rep));
+  RS2_TRY(bind_encode(p->ctx, p->col_rep, p->col_rep_mem, st));
   p->bound_primary = d_primary;
   p->bound_secondary = d_secondary;
   p->bound_both = d_both;
@@ -2325,8 +2261,7 @@ int encode_device(rs2_plan* p, const uint8_t* d_blob, uint8_t* d_primary, uint8_
                   hipStream_t prim_st = nullptr) {
   const int64_t s = p->s, n = p->n, kp = p->kp, ks = p->ks;
   const int64_t msg = kp * ks * s;
-  int rc = bind_encode_buffers(p, d_primary, d_secondary, st);
-  if (rc != RS2_OK) return rc;
+  RS2_TRY(bind_encode_buffers(p, d_primary, d_secondary, st));
   // The plan's buffers (repair quadrant, leaves, tile counters) serve one encode at a time: an
   // encode queued on another stream than the previous one's runs after it on the device.
   if (p->enc_done) HIP_TRY(hipStreamWaitEvent(st, p->enc_done, 0));
@@ -2336,8 +2271,8 @@ int encode_device(rs2_plan* p, const uint8_t* d_blob, uint8_t* d_primary, uint8_
   // waits for the last reader of its buffers) that costs 3.73 -> 4.10 ms per step, so the side
   // stream keeps the default priority unless RS2_SIDE_PRIORITY=1 (A/B knob).
   hipStream_t side = p->side;
-  static const char* pri_env = std::getenv("RS2_SIDE_PRIORITY");
-  if (prim_st && pri_env && std::atoi(pri_env) != 0) {
+  static const bool side_priority = env_int("RS2_SIDE_PRIORITY", 0) != 0;
+  if (prim_st && side_priority) {
     if (!p->side_hi) {
       int lo_pri = 0, hi_pri = 0;
       HIP_TRY(hipDeviceGetStreamPriorityRange(&lo_pri, &hi_pri));
@@ -2415,10 +2350,7 @@ int encode_device(rs2_plan* p, const uint8_t* d_blob, uint8_t* d_primary, uint8_
   // for CUs anyway (the kernel trace shows them finishing with it), and the step is 88.1-88.3
   // vs 87.7-87.9 GiB/s without them on their own stream (five interleaved pairs,
   // profiles/r05/exp/tailaux/)
-  static const bool tail_aux = [] {
-    const char* e = std::getenv("RS2_TAIL_AUX");
-    return e && std::atoi(e) == 1;
-  }();
+  static const bool tail_aux = env_int("RS2_TAIL_AUX", 0) == 1;
   // (large blobs only: for small ones the extra stream and launch cost more than the tail, and
   // many plans encoding at once share the device's few hardware queues: C3's 16 plans on 16
   // streams measured 12.1 vs 13.6 GiB/s with it)
@@ -2465,10 +2397,8 @@ int encode_device(rs2_plan* p, const uint8_t* d_blob, uint8_t* d_primary, uint8_
   // leaves (run A) are hashed on the side stream as soon as the systematic-column codec is done,
   // beside the row / repair-column codecs; the secondary-side runs B and C here after them.
   SymbolMap map{d_primary, d_secondary, p->both.as<uint8_t>(), int(n), int(kp), int(ks), int(s)};
-  static const bool split_leaf = [] {  // RS2_SPLIT_LEAF=0: one leaf launch after the join (A/B)
-    const char* e = std::getenv("RS2_SPLIT_LEAF");
-    return !(e && std::atoi(e) == 0);
-  }();
+  // RS2_SPLIT_LEAF=0: one leaf launch after the join (A/B)
+  static const bool split_leaf = env_int("RS2_SPLIT_LEAF", 1) != 0;
   const bool split = split_leaf && p->sys_fused && big;  // (C3 streams: 11.1 vs 13.6 GiB/s)
   if (meta_only) {
     // run A (rows of K_s symbols, leaf (r, c) at r*n + c) from where the rows are: the blob's
@@ -2556,8 +2486,7 @@ int encode_batch_device(rs2_plan* p, uint32_t n_blobs, const uint8_t* d_blobs, i
   for (uint32_t b = 0; b < n_blobs; ++b) {
     if (lens) lv[b] = lens[b];
     uint16_t sb = 0;
-    int rc = rs2_symbol_size_for_blob(p->n, lv[b], &sb);
-    if (rc != RS2_OK) return rc;
+    RS2_TRY(rs2_symbol_size_for_blob(p->n, lv[b], &sb));
     if (sb != p->s) return fail(RS2_E_INVALID_ARGUMENT, "blob length outside the plan's symbol size");
     max_len = std::max(max_len, lv[b]);
   }
@@ -2567,8 +2496,7 @@ int encode_batch_device(rs2_plan* p, uint32_t n_blobs, const uint8_t* d_blobs, i
   const int64_t both_b = (n - kp) * (n - ks) * s, leaves_b = n * n * 32;
   HIP_TRY(p->batch_both.ensure(size_t(n_blobs) * both_b));
   HIP_TRY(p->batch_leaves.ensure(size_t(n_blobs) * leaves_b));
-  int rc = bind_encode_buffers(p, d_primary, d_secondary, st, p->batch_both.as<uint8_t>());
-  if (rc != RS2_OK) return rc;
+  RS2_TRY(bind_encode_buffers(p, d_primary, d_secondary, st, p->batch_both.as<uint8_t>()));
   if (lv != p->batch_lens_h) {  // upload the lengths (the host copy stays alive until it lands)
     if (p->enc_done) HIP_TRY(hipEventSynchronize(p->enc_done));
     p->batch_lens_h = lv;
@@ -2653,17 +2581,84 @@ int select_slivers(const rs2_plan* p, int axis, uint32_t count, const uint16_t* 
   return RS2_OK;
 }
 
+// The decode sequence of a blob plan and of a 1D codec: wait for the slot, list the present
+// originals, plan the erasure pattern (unless the slot was planned for the same key), copy the
+// present originals that the kernel does not write itself, bind, launch, record the event.
+// The copy runs over the decode's own geometry: `lines` lines sp.src_ls / sp.dst_ls apart,
+// bytes at or past sp.dst_limit not written.  The copy list is built from sp.present in index
+// order (a plan's used to follow the caller's sliver order; the copies are independent, so the
+// bytes written are the same).  A source offset of 2^63 or more is negative in sp.present and
+// so counts as absent here, as it always did for the decode plan itself.
+int run_decode(Context* ctx, DecodeSlot (&slots)[2], int& cursor, DecodeSpec& sp,
+               std::vector<int64_t> key, bool may_fuse, int lines, rs2_plan* prof, hipStream_t st) {
+  DecodeSlot& sl = slots[cursor];
+  cursor ^= 1;
+  const auto wait_t0 = std::chrono::steady_clock::now();
+  if (sl.done) HIP_TRY(hipEventSynchronize(sl.done));
+  if (prof) prof_host(prof, "dec_host_slotwait", wait_t0);
+  std::vector<int64_t>& copy_src = sl.copy_src_h;
+  std::vector<int64_t>& copy_dst = sl.copy_dst_h;
+  copy_src.clear();
+  copy_dst.clear();
+  for (uint32_t i = 0; i < sp.K; ++i)
+    if (sp.present[i] >= 0) {
+      copy_src.push_back(sp.present[i]);
+      copy_dst.push_back(sp.dst[i]);
+    }
+  if (prof) mark(prof, "", st);
+  const bool run_codec = copy_src.size() < sp.K;
+  PlannedJob& pj = sl.job;
+  const bool cached = !key.empty() && key == sl.key;
+  sl.key.clear();  // valid again only once this call has re-planned successfully
+  bool fused = cached && sl.fused;
+  const auto host_t0 = std::chrono::steady_clock::now();
+  if (run_codec && !cached) {
+    // present originals are written by the decode kernel from its own loads when it can
+    sp.copy_present = !copy_src.empty() && sp.symbol_size >= 4 && may_fuse;
+    RS2_TRY(plan_decode(sp, pj));
+    fused = sp.copy_present && copy_covered(pj);
+    if (prof) prof_host(prof, "dec_host_plan", host_t0);
+  }
+  // present originals: straight copies into the output (when not fused into the decode)
+  if (!copy_src.empty() && !fused) {
+    if (!cached) {
+      HIP_TRY(sl.copy_src.ensure(copy_src.size() * 8));
+      HIP_TRY(sl.copy_dst.ensure(copy_dst.size() * 8));
+      HIP_TRY(ctx->upload(sl.copy_src.p, copy_src.data(), copy_src.size() * 8, st));
+      HIP_TRY(ctx->upload(sl.copy_dst.p, copy_dst.data(), copy_dst.size() * 8, st));
+    }
+    HIP_TRY(rs2k_launch_symbol_copy(sp.src_base, sl.copy_src.as<int64_t>(), sp.src_ls, sp.dst_base,
+                                    sl.copy_dst.as<int64_t>(), sp.dst_ls, int(copy_src.size()),
+                                    lines, sp.symbol_size, sp.dst_limit, st));
+    if (prof) mark(prof, "dec_copy_present", st);
+  }
+  if (run_codec) {
+    if (!cached) {
+      const auto bind_t0 = std::chrono::steady_clock::now();
+      // (on st, behind its wait for the slivers: the same setup on a stream of its own, so the
+      // decode starts the moment the primary slivers are final, measured 81.8 vs 87.4 GiB/s --
+      // a decode that takes the CUs earlier delays the encode's chain, DESIGN.md §6.0)
+      RS2_TRY(bind_decode(ctx, pj, sl.mem, st));
+      if (prof) prof_host(prof, "dec_host_bind", bind_t0);
+      if (prof) prof_host(prof, "dec_plan_host", host_t0);
+    }
+    if (prof) mark(prof, "dec_setup", st);
+    HIP_TRY(pj.launch(lines, st));
+    if (prof) mark(prof, "dec_codec", st);
+  }
+  if (!sl.done) HIP_TRY(hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
+  HIP_TRY(hipEventRecord(sl.done, st));
+  sl.key = std::move(key);
+  sl.fused = fused;
+  return RS2_OK;
+}
+
 // Decode from chosen device slivers: sliver i at base + off[i].
 int decode_device(rs2_plan* p, int axis, const std::vector<std::pair<uint16_t, uint32_t>>& chosen,
                   const uint8_t* base, const uint64_t* off, uint8_t* d_out, hipStream_t st) {
   const int64_t s = p->s, n = p->n, kp = p->kp, ks = p->ks;
   const bool prim = axis == RS2_AXIS_PRIMARY;
   const uint32_t K = prim ? uint32_t(kp) : uint32_t(ks);
-  const int slot = p->dec_slot;
-  p->dec_slot ^= 1;
-  const auto wait_t0 = std::chrono::steady_clock::now();
-  if (p->dec_done[slot]) HIP_TRY(hipEventSynchronize(p->dec_done[slot]));
-  prof_host(p, "dec_host_slotwait", wait_t0);
   DecodeSpec sp;
   sp.K = K;
   sp.R = uint32_t(n) - K;
@@ -2676,80 +2671,18 @@ int decode_device(rs2_plan* p, int axis, const std::vector<std::pair<uint16_t, u
   sp.dst.resize(K);
   for (uint32_t i = 0; i < K; ++i) sp.dst[i] = prim ? int64_t(i) * ks * s : int64_t(i) * s;
   sp.dst_ls = prim ? s : ks * s;
-  std::vector<int64_t>& copy_src = p->dec_copy_src_h[slot];
-  std::vector<int64_t>& copy_dst = p->dec_copy_dst_h[slot];
-  copy_src.clear();
-  copy_dst.clear();
-  for (auto& c : chosen) {
-    sp.present[c.first] = int64_t(off[c.second]);
-    if (c.first < K) {
-      copy_src.push_back(int64_t(off[c.second]));
-      copy_dst.push_back(sp.dst[c.first]);
-    }
-  }
-  mark(p, "", st);
-  const bool run_codec = copy_src.size() < K;
-  PlannedJob& pj = p->dec_job[slot];
+  for (auto& c : chosen) sp.present[c.first] = int64_t(off[c.second]);
   std::vector<int64_t> key;
-  key.reserve(size_t(n) + 4);
+  key.reserve(size_t(n) + 5);
   key.push_back(axis);
   key.push_back(int64_t(block_max()));
   key.push_back(int64_t(p->blob_len));  // sp.dst_limit: rebind keeps the plan, not the limit
   key.push_back(int64_t(reinterpret_cast<uintptr_t>(base)));
   key.push_back(int64_t(reinterpret_cast<uintptr_t>(d_out)));
   key.insert(key.end(), sp.present.begin(), sp.present.end());
-  const bool cached = key == p->dec_key[slot];
-  p->dec_key[slot].clear();  // valid again only once this call has re-planned successfully
-  bool fused = cached && p->dec_fused[slot];
-  const auto host_t0 = std::chrono::steady_clock::now();
-  if (run_codec && !cached) {
-    // present originals are written by the decode kernel from its own loads when it can
-    static const bool no_fuse = [] {  // A/B knob: RS2_DEC_NOFUSE=1
-      const char* e = std::getenv("RS2_DEC_NOFUSE");
-      return e && std::atoi(e) != 0;
-    }();
-    sp.copy_present = !copy_src.empty() && s >= 4 && !no_fuse;
-    int rc = plan_decode(sp, pj);
-    if (rc != RS2_OK) return rc;
-    fused = sp.copy_present && copy_covered(pj);
-    prof_host(p, "dec_host_plan", host_t0);
-  }
-  // present originals: straight copies into the blob (when not fused into the decode)
-  if (!copy_src.empty() && !fused) {
-    if (!cached) {
-      HIP_TRY(p->dec_copy_src[slot].ensure(copy_src.size() * 8));
-      HIP_TRY(p->dec_copy_dst[slot].ensure(copy_dst.size() * 8));
-      HIP_TRY(p->ctx->upload(p->dec_copy_src[slot].p, copy_src.data(), copy_src.size() * 8, st));
-      HIP_TRY(p->ctx->upload(p->dec_copy_dst[slot].p, copy_dst.data(), copy_dst.size() * 8, st));
-    }
-    const int count_b = prim ? int(ks) : int(kp);
-    HIP_TRY(rs2k_launch_symbol_copy(base, p->dec_copy_src[slot].as<int64_t>(), s, d_out,
-                                    p->dec_copy_dst[slot].as<int64_t>(), prim ? s : ks * s,
-                                    int(copy_src.size()), count_b, int(s), int64_t(p->blob_len),
-                                    st));
-    mark(p, "dec_copy_present", st);
-  }
-  if (run_codec) {
-    if (!cached) {
-      const auto bind_t0 = std::chrono::steady_clock::now();
-      // (on st, behind its wait for the slivers: the same setup on a stream of its own, so the
-      // decode starts the moment the primary slivers are final, measured 81.8 vs 87.4 GiB/s --
-      // a decode that takes the CUs earlier delays the encode's chain, DESIGN.md §6.0)
-      int rc = bind_decode(p->ctx, pj, p->dec_mem[slot], st);
-      if (rc != RS2_OK) return rc;
-      prof_host(p, "dec_host_bind", bind_t0);
-      prof_host(p, "dec_plan_host", host_t0);
-    }
-    mark(p, "dec_setup", st);
-    const int lines = prim ? int(ks) : int(kp);
-    HIP_TRY(pj.launch(lines, st));
-    mark(p, "dec_codec", st);
-  }
-  if (!p->dec_done[slot]) HIP_TRY(hipEventCreateWithFlags(&p->dec_done[slot], hipEventDisableTiming));
-  HIP_TRY(hipEventRecord(p->dec_done[slot], st));
-  p->dec_key[slot] = std::move(key);
-  p->dec_fused[slot] = fused;
-  return RS2_OK;
+  static const bool no_fuse = env_int("RS2_DEC_NOFUSE", 0) != 0;  // A/B knob: RS2_DEC_NOFUSE=1
+  const int lines = prim ? int(ks) : int(kp);
+  return run_decode(p->ctx, p->dec, p->dec_slot, sp, std::move(key), !no_fuse, lines, p, st);
 }
 
 // Stream argument of the plan / verifier ABI: NULL = the object's own stream,
@@ -2783,24 +2716,18 @@ int check_digest_ptr(const void* p, const char* what) {
   if (aligned_to(p, 16)) return RS2_OK;
   return fail(RS2_E_INVALID_ARGUMENT, std::string(what) + " must be 16-byte aligned");
 }
-#define ALIGN_TRY(expr)                 \
-  do {                                  \
-    int rc_ = (expr);                   \
-    if (rc_ != RS2_OK) return rc_;      \
-  } while (0)
-
 int check_encode_ptrs(const void* d_blob, const void* d_primary, const void* d_secondary,
                       const void* d_hashes, const void* d_blob_id) {
-  ALIGN_TRY(check_symbol_ptr(d_blob, "d_blob"));
-  ALIGN_TRY(check_symbol_ptr(d_primary, "d_primary"));
-  ALIGN_TRY(check_symbol_ptr(d_secondary, "d_secondary"));
-  ALIGN_TRY(check_digest_ptr(d_hashes, "d_hashes"));
+  RS2_TRY(check_symbol_ptr(d_blob, "d_blob"));
+  RS2_TRY(check_symbol_ptr(d_primary, "d_primary"));
+  RS2_TRY(check_symbol_ptr(d_secondary, "d_secondary"));
+  RS2_TRY(check_digest_ptr(d_hashes, "d_hashes"));
   return check_digest_ptr(d_blob_id, "d_blob_id");
 }
 int check_decode_ptrs(uint32_t count, const void* d_slivers_base, const uint64_t* sliver_off,
                       const void* d_blob_out) {
-  ALIGN_TRY(check_symbol_ptr(d_slivers_base, "d_slivers_base"));
-  for (uint32_t i = 0; i < count; ++i) ALIGN_TRY(check_symbol_step(sliver_off[i], "sliver_off[i]"));
+  RS2_TRY(check_symbol_ptr(d_slivers_base, "d_slivers_base"));
+  for (uint32_t i = 0; i < count; ++i) RS2_TRY(check_symbol_step(sliver_off[i], "sliver_off[i]"));
   return check_symbol_ptr(d_blob_out, "d_blob_out");
 }
 
@@ -2822,8 +2749,7 @@ int rs2_source_symbols_for_n_shards(uint16_t n_shards, uint16_t* n_primary, uint
 
 int rs2_symbol_size_for_blob(uint16_t n_shards, uint64_t blob_len, uint16_t* symbol_size) {
   uint16_t kp, ks;
-  int rc = rs2_source_symbols_for_n_shards(n_shards, &kp, &ks);
-  if (rc != RS2_OK) return rc;
+  RS2_TRY(rs2_source_symbols_for_n_shards(n_shards, &kp, &ks));
   const uint64_t n_sym = uint64_t(kp) * ks;
   const uint64_t len = std::max<uint64_t>(blob_len, 1);
   uint64_t sz = (len + n_sym - 1) / n_sym;
@@ -2835,10 +2761,8 @@ int rs2_symbol_size_for_blob(uint16_t n_shards, uint64_t blob_len, uint16_t* sym
 
 int rs2_encoded_blob_length(uint16_t n_shards, uint64_t blob_len, uint64_t* encoded_len) {
   uint16_t kp, ks, s;
-  int rc = rs2_source_symbols_for_n_shards(n_shards, &kp, &ks);
-  if (rc != RS2_OK) return rc;
-  rc = rs2_symbol_size_for_blob(n_shards, blob_len, &s);
-  if (rc != RS2_OK) return rc;
+  RS2_TRY(rs2_source_symbols_for_n_shards(n_shards, &kp, &ks));
+  RS2_TRY(rs2_symbol_size_for_blob(n_shards, blob_len, &s));
   const uint64_t slivers = uint64_t(n_shards) * (uint64_t(kp) + ks) * s;
   const uint64_t meta = uint64_t(n_shards) * (uint64_t(n_shards) * 64 + 32);
   *encoded_len = slivers + meta;
@@ -2868,16 +2792,13 @@ int rs2_plan_create(uint16_t n_shards, uint64_t blob_len, rs2_plan** out) {
   if (!out) return fail(RS2_E_INVALID_ARGUMENT, "null plan pointer");
   *out = nullptr;
   uint16_t kp, ks, s;
-  int rc = rs2_source_symbols_for_n_shards(n_shards, &kp, &ks);
-  if (rc != RS2_OK) return rc;
-  rc = rs2_symbol_size_for_blob(n_shards, blob_len, &s);
-  if (rc != RS2_OK) return rc;
+  RS2_TRY(rs2_source_symbols_for_n_shards(n_shards, &kp, &ks));
+  RS2_TRY(rs2_symbol_size_for_blob(n_shards, blob_len, &s));
   if (kp == n_shards || ks == n_shards)
     return fail(RS2_E_INCOMPATIBLE_PARAMETERS, "n_shards too small for a recovery code");
   if (n_shards > kMaxShards) return fail(RS2_E_UNSUPPORTED, "n_shards above 65535");
   Context* ctx = nullptr;
-  rc = get_context(&ctx);
-  if (rc != RS2_OK) return rc;
+  RS2_TRY(get_context(&ctx));
   auto p = std::make_unique<rs2_plan>();
   p->ctx = ctx;
   p->n = n_shards;
@@ -2930,19 +2851,16 @@ void rs2_plan_destroy(rs2_plan* plan) {
   // its buffers then go straight back to the device arena for the next plan
   for (hipStream_t st : {plan->stream, plan->side, plan->side_hi, plan->aux, plan->io})
     if (st) (void)hipStreamSynchronize(st);
-  for (hipEvent_t ev : {plan->enc_done, plan->dec_done[0], plan->dec_done[1], plan->leaf_ev})
+  for (hipEvent_t ev : {plan->enc_done, plan->dec[0].done, plan->dec[1].done, plan->leaf_ev})
     if (ev) (void)hipEventSynchronize(ev);
-  const bool prev = t_quiesced;
-  t_quiesced = true;
+  const Quiesced quiesced;
   delete plan;
-  t_quiesced = prev;
 }
 
 int rs2_plan_rebind(rs2_plan* plan, uint64_t blob_len) {
   if (!plan) return fail(RS2_E_INVALID_ARGUMENT, "null plan");
   uint16_t s = 0;
-  const int rc = rs2_symbol_size_for_blob(plan->n, blob_len, &s);
-  if (rc != RS2_OK) return rc;
+  RS2_TRY(rs2_symbol_size_for_blob(plan->n, blob_len, &s));
   if (s != plan->s)
     return fail(RS2_E_INCOMPATIBLE_PARAMETERS, "blob length needs another symbol size than the plan's");
   plan->blob_len = blob_len;
@@ -3012,7 +2930,7 @@ int rs2_encode_device_async(rs2_plan* plan, const void* d_blob, void* d_primary,
                             void* d_hashes, void* d_blob_id, void* stream) {
   if (!plan || !d_primary || !d_secondary || (!d_blob && plan->blob_len))
     return fail(RS2_E_INVALID_ARGUMENT, "null argument");
-  ALIGN_TRY(check_encode_ptrs(d_blob, d_primary, d_secondary, d_hashes, d_blob_id));
+  RS2_TRY(check_encode_ptrs(d_blob, d_primary, d_secondary, d_hashes, d_blob_id));
   HIP_TRY(hipSetDevice(plan->ctx->device));
   return encode_device(plan, reinterpret_cast<const uint8_t*>(d_blob),
                        reinterpret_cast<uint8_t*>(d_primary), reinterpret_cast<uint8_t*>(d_secondary),
@@ -3024,7 +2942,7 @@ int rs2_compute_metadata_device_async(rs2_plan* plan, const void* d_blob, void* 
                                       void* d_blob_id, void* stream) {
   if (!plan || !d_hashes || !d_blob_id || (!d_blob && plan->blob_len))
     return fail(RS2_E_INVALID_ARGUMENT, "null argument");
-  ALIGN_TRY(check_encode_ptrs(d_blob, nullptr, nullptr, d_hashes, d_blob_id));
+  RS2_TRY(check_encode_ptrs(d_blob, nullptr, nullptr, d_hashes, d_blob_id));
   HIP_TRY(hipSetDevice(plan->ctx->device));
   const int64_t n = plan->n;
   HIP_TRY(plan->int_primary.ensure(size_t(n) * primary_len(plan)));
@@ -3040,7 +2958,7 @@ int rs2_encode_device_split_async(rs2_plan* plan, const void* d_blob, void* d_pr
                                   void* primary_stream) {
   if (!plan || !d_primary || !d_secondary || (!d_blob && plan->blob_len) || !primary_stream)
     return fail(RS2_E_INVALID_ARGUMENT, "null argument");
-  ALIGN_TRY(check_encode_ptrs(d_blob, d_primary, d_secondary, d_hashes, d_blob_id));
+  RS2_TRY(check_encode_ptrs(d_blob, d_primary, d_secondary, d_hashes, d_blob_id));
   hipStream_t st = pick_stream(plan, stream);
   hipStream_t pst = abi_stream(primary_stream, nullptr);
   if (pst == st || pst == plan->side || pst == plan->side_hi)
@@ -3059,11 +2977,10 @@ int rs2_decode_device_async(rs2_plan* plan, int axis, uint32_t count, const uint
     return fail(RS2_E_INVALID_ARGUMENT, "null argument");
   if (axis != RS2_AXIS_PRIMARY && axis != RS2_AXIS_SECONDARY)
     return fail(RS2_E_INVALID_ARGUMENT, "bad axis");
-  ALIGN_TRY(check_decode_ptrs(count, d_slivers_base, sliver_off, d_blob_out));
+  RS2_TRY(check_decode_ptrs(count, d_slivers_base, sliver_off, d_blob_out));
   HIP_TRY(hipSetDevice(plan->ctx->device));
   std::vector<std::pair<uint16_t, uint32_t>> chosen;
-  int rc = select_slivers(plan, axis, count, sliver_idx, nullptr, nullptr, chosen);
-  if (rc != RS2_OK) return rc;
+  RS2_TRY(select_slivers(plan, axis, count, sliver_idx, nullptr, nullptr, chosen));
   return decode_device(plan, axis, chosen, reinterpret_cast<const uint8_t*>(d_slivers_base),
                        sliver_off, reinterpret_cast<uint8_t*>(d_blob_out), pick_stream(plan, stream));
 }
@@ -3104,6 +3021,8 @@ int rs2_sync(rs2_plan* plan, void* stream) {
   return RS2_OK;
 }
 
+}  // extern "C"
+
 namespace {
 // a pinned ring leased to `plan` for one host-buffer call
 struct RingGuard {
@@ -3123,6 +3042,8 @@ struct RingGuard {
 };
 }  // namespace
 
+extern "C" {
+
 int rs2_encode_with_metadata(rs2_plan* plan, const uint8_t* blob, uint8_t* const* primary_out,
                              uint8_t* const* secondary_out, uint8_t* hashes_out,
                              uint8_t* blob_id_out) {
@@ -3137,31 +3058,28 @@ int rs2_encode_with_metadata(rs2_plan* plan, const uint8_t* blob, uint8_t* const
   HIP_TRY(plan->int_secondary.ensure(size_t(n) * sl));
   if (!plan->io) HIP_TRY(hipStreamCreateWithFlags(&plan->io, hipStreamNonBlocking));
   hipStream_t st = plan->stream, io = plan->io;
-  int rc = RS2_OK;
   // the blob in through the pinned ring (host copies of piece k+1 under the DMA of piece k)
-  if (plan->blob_len &&
-      (rc = stage_h2d(ctx, *plan->stage, {{const_cast<uint8_t*>(blob), plan->dev_blob.as<uint8_t>(),
-                                          size_t(plan->blob_len)}}, st)) != RS2_OK)
-    return rc;
+  if (plan->blob_len)
+    RS2_TRY(stage_h2d(ctx, *plan->stage, {{const_cast<uint8_t*>(blob), plan->dev_blob.as<uint8_t>(),
+                                           size_t(plan->blob_len)}}, st));
   uint8_t* dp = plan->int_primary.as<uint8_t>();
   uint8_t* ds = plan->int_secondary.as<uint8_t>();
   const bool slivers = primary_out || secondary_out;
   // split encode: `io` is released once the primary slivers are final, so their D2H overlaps the
   // secondary codecs and the hashing still running on st
-  rc = encode_device(plan, plan->dev_blob.as<uint8_t>(), dp, ds, plan->pairs.as<uint8_t>(),
-                     plan->blob_id.as<uint8_t>(), st, slivers, slivers ? io : nullptr);
-  if (rc != RS2_OK) return rc;
+  RS2_TRY(encode_device(plan, plan->dev_blob.as<uint8_t>(), dp, ds, plan->pairs.as<uint8_t>(),
+                        plan->blob_id.as<uint8_t>(), st, slivers, slivers ? io : nullptr));
   std::vector<Seg> segs;
   for (int64_t i = 0; primary_out && i < n; ++i)
     if (primary_out[i]) segs.push_back({primary_out[i], dp + i * pl, size_t(pl)});
-  if (!segs.empty() && (rc = stage_d2h(ctx, *plan->stage, segs, io)) != RS2_OK) return rc;
+  if (!segs.empty()) RS2_TRY(stage_d2h(ctx, *plan->stage, segs, io));
   segs.clear();
   for (int64_t i = 0; secondary_out && i < n; ++i)
     if (secondary_out[i]) segs.push_back({secondary_out[i], ds + i * sl, size_t(sl)});
   if (hashes_out) segs.push_back({hashes_out, plan->pairs.as<uint8_t>(), size_t(n) * 64});
   if (blob_id_out) segs.push_back({blob_id_out, plan->blob_id.as<uint8_t>(), 32});
   HIP_TRY(hipStreamWaitEvent(io, plan->enc_done, 0));
-  if (!segs.empty() && (rc = stage_d2h(ctx, *plan->stage, segs, io)) != RS2_OK) return rc;
+  if (!segs.empty()) RS2_TRY(stage_d2h(ctx, *plan->stage, segs, io));
   HIP_TRY(hipStreamSynchronize(io));
   HIP_TRY(hipStreamSynchronize(st));
   return RS2_OK;
@@ -3178,10 +3096,10 @@ int rs2_encode_batch_device_async(rs2_plan* plan, uint32_t n_blobs, const void* 
                                   uint64_t secondary_stride, void* d_hashes, void* d_blob_ids,
                                   void* stream) {
   if (!plan) return fail(RS2_E_INVALID_ARGUMENT, "null plan");
-  ALIGN_TRY(check_encode_ptrs(d_blobs, d_primary, d_secondary, d_hashes, d_blob_ids));
-  ALIGN_TRY(check_symbol_step(blob_stride, "blob_stride"));
-  ALIGN_TRY(check_symbol_step(primary_stride, "primary_stride"));
-  ALIGN_TRY(check_symbol_step(secondary_stride, "secondary_stride"));
+  RS2_TRY(check_encode_ptrs(d_blobs, d_primary, d_secondary, d_hashes, d_blob_ids));
+  RS2_TRY(check_symbol_step(blob_stride, "blob_stride"));
+  RS2_TRY(check_symbol_step(primary_stride, "primary_stride"));
+  RS2_TRY(check_symbol_step(secondary_stride, "secondary_stride"));
   HIP_TRY(hipSetDevice(plan->ctx->device));
   return encode_batch_device(plan, n_blobs, reinterpret_cast<const uint8_t*>(d_blobs),
                              int64_t(blob_stride), blob_lens, reinterpret_cast<uint8_t*>(d_primary),
@@ -3225,10 +3143,8 @@ int rs2_encode_batch_with_metadata(rs2_plan* plan, uint32_t n_blobs, const uint8
     const uint64_t len = blob_lens ? blob_lens[b] : plan->blob_len;
     if (len) segs.push_back({const_cast<uint8_t*>(blobs[b]), db + b * bstride, size_t(len)});
   }
-  int rc = stage_h2d(ctx, *plan->stage, segs, st);
-  if (rc != RS2_OK) return rc;
-  rc = encode_batch_device(plan, n_blobs, db, bstride, blob_lens, dp, n * pl, ds, n * sl, dh, di, st);
-  if (rc != RS2_OK) return rc;
+  RS2_TRY(stage_h2d(ctx, *plan->stage, segs, st));
+  RS2_TRY(encode_batch_device(plan, n_blobs, db, bstride, blob_lens, dp, n * pl, ds, n * sl, dh, di, st));
   segs.clear();
   for (size_t b = 0; b < B; ++b)
     for (int64_t i = 0; i < n; ++i) {
@@ -3239,10 +3155,12 @@ int rs2_encode_batch_with_metadata(rs2_plan* plan, uint32_t n_blobs, const uint8
     }
   if (hashes_out) segs.push_back({hashes_out, dh, B * size_t(n) * 64});
   if (blob_ids_out) segs.push_back({blob_ids_out, di, B * 32});
-  if (!segs.empty() && (rc = stage_d2h(ctx, *plan->stage, segs, st)) != RS2_OK) return rc;
+  if (!segs.empty()) RS2_TRY(stage_d2h(ctx, *plan->stage, segs, st));
   HIP_TRY(hipStreamSynchronize(st));
   return RS2_OK;
 }
+
+}  // extern "C"
 
 namespace {
 
@@ -3258,9 +3176,8 @@ int decode_host(rs2_plan* plan, int axis, uint32_t count, const uint16_t* sliver
     return fail(RS2_E_INVALID_ARGUMENT, "bad axis");
   HIP_TRY(hipSetDevice(plan->ctx->device));
   std::vector<std::pair<uint16_t, uint32_t>> chosen;
-  int rc = select_slivers(plan, axis, count, sliver_idx, sliver_len, sliver_symbol_size, chosen,
-                          pulled);
-  if (rc != RS2_OK) return rc;
+  RS2_TRY(select_slivers(plan, axis, count, sliver_idx, sliver_len, sliver_symbol_size, chosen,
+                         pulled));
   for (const auto& c : chosen)
     if (!slivers[c.second]) return fail(RS2_E_INVALID_ARGUMENT, "null sliver");
   const int64_t len = axis == RS2_AXIS_PRIMARY ? primary_len(plan) : secondary_len(plan);
@@ -3277,7 +3194,7 @@ int decode_host(rs2_plan* plan, int axis, uint32_t count, const uint16_t* sliver
                     stage.as<uint8_t>() + i * len, size_t(len)});
   }
   HIP_TRY(plan->dev_blob.ensure(size_t(std::max<int64_t>(msg, 16))));
-  if ((rc = stage_h2d(plan->ctx, *plan->stage, segs, st)) != RS2_OK) return rc;
+  RS2_TRY(stage_h2d(plan->ctx, *plan->stage, segs, st));
   if (uint64_t(msg) > plan->blob_len)
     HIP_TRY(hipMemsetAsync(plan->dev_blob.as<uint8_t>() + plan->blob_len, 0,
                            size_t(msg - plan->blob_len), st));
@@ -3299,8 +3216,7 @@ int default_check(rs2_plan* plan, const std::vector<uint8_t>& verified, const ui
     if (!verified[size_t(i)]) rows.push_back(uint16_t(i));
   if (rows.empty()) return RS2_OK;
   if (!plan->check_v) {
-    int rc = rs2_verifier_create(plan->n, plan->s, RS2_AXIS_PRIMARY, &plan->check_v);
-    if (rc != RS2_OK) return rc;
+    RS2_TRY(rs2_verifier_create(plan->n, plan->s, RS2_AXIS_PRIMARY, &plan->check_v));
   }
   const uint8_t* src = blob;
   // rows past the written bytes (the zero-padded tail of the message) are rebuilt in the gather
@@ -3331,10 +3247,9 @@ int default_check(rs2_plan* plan, const std::vector<uint8_t>& verified, const ui
   HIP_TRY(plan->check_roots.ensure(rows.size() * 32));
   // (st nullptr is the HIP null stream here; at the ABI NULL would mean the verifier's own
   // stream, unordered with the decode that wrote `blob`)
-  int rc = rs2_verifier_roots_device_async(plan->check_v, uint32_t(rows.size()), src,
-                                           plan->check_roots.p,
-                                           st ? static_cast<void*>(st) : RS2_STREAM_LEGACY);
-  if (rc != RS2_OK) return rc;
+  RS2_TRY(rs2_verifier_roots_device_async(plan->check_v, uint32_t(rows.size()), src,
+                                          plan->check_roots.p,
+                                          st ? static_cast<void*>(st) : RS2_STREAM_LEGACY));
   std::vector<uint8_t> roots(rows.size() * 32);
   HIP_TRY(hipMemcpyAsync(roots.data(), plan->check_roots.p, roots.size(), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
@@ -3350,10 +3265,9 @@ int strict_check(rs2_plan* plan, const uint8_t* blob_id, const uint8_t* blob, hi
   const int64_t n = plan->n;
   HIP_TRY(plan->int_primary.ensure(size_t(n) * primary_len(plan)));
   HIP_TRY(plan->int_secondary.ensure(size_t(n) * secondary_len(plan)));
-  int rc = encode_device(plan, blob, plan->int_primary.as<uint8_t>(),
-                         plan->int_secondary.as<uint8_t>(), plan->pairs.as<uint8_t>(),
-                         plan->blob_id.as<uint8_t>(), st, false);
-  if (rc != RS2_OK) return rc;
+  RS2_TRY(encode_device(plan, blob, plan->int_primary.as<uint8_t>(),
+                        plan->int_secondary.as<uint8_t>(), plan->pairs.as<uint8_t>(),
+                        plan->blob_id.as<uint8_t>(), st, false));
   uint8_t bid[32];
   HIP_TRY(hipMemcpyAsync(bid, plan->blob_id.p, 32, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
@@ -3363,10 +3277,9 @@ int strict_check(rs2_plan* plan, const uint8_t* blob_id, const uint8_t* blob, hi
 
 int blob_to_host(rs2_plan* plan, uint8_t* blob_out) {
   if (plan->blob_len) {
-    int rc = stage_d2h(plan->ctx, *plan->stage,
-                       {{blob_out, plan->dev_blob.as<uint8_t>(), size_t(plan->blob_len)}},
-                       plan->stream);
-    if (rc != RS2_OK) return rc;
+    RS2_TRY(stage_d2h(plan->ctx, *plan->stage,
+                      {{blob_out, plan->dev_blob.as<uint8_t>(), size_t(plan->blob_len)}},
+                      plan->stream));
   }
   HIP_TRY(hipStreamSynchronize(plan->stream));
   return RS2_OK;
@@ -3374,14 +3287,15 @@ int blob_to_host(rs2_plan* plan, uint8_t* blob_out) {
 
 }  // namespace
 
+extern "C" {
+
 int rs2_decode_blob(rs2_plan* plan, int axis, uint32_t count, const uint16_t* sliver_idx,
                     const uint8_t* const* slivers, const uint64_t* sliver_len,
                     const uint16_t* sliver_symbol_size, uint8_t* blob_out) {
   if (!plan || (!blob_out && plan->blob_len)) return fail(RS2_E_INVALID_ARGUMENT, "null argument");
   RingGuard ring(plan);
-  int rc = decode_host(plan, axis, count, sliver_idx, slivers, sliver_len, sliver_symbol_size,
-                       nullptr);
-  if (rc != RS2_OK) return rc;
+  RS2_TRY(decode_host(plan, axis, count, sliver_idx, slivers, sliver_len, sliver_symbol_size,
+                      nullptr));
   return blob_to_host(plan, blob_out);
 }
 
@@ -3396,9 +3310,8 @@ int rs2_decode_and_verify(rs2_plan* plan, int axis, uint32_t count, const uint16
     return fail(RS2_E_INVALID_ARGUMENT, "bad consistency check");
   RingGuard ring(plan);
   uint32_t pulled = 0;
-  int rc = decode_host(plan, axis, count, sliver_idx, slivers, sliver_len, sliver_symbol_size,
-                       &pulled);
-  if (rc != RS2_OK) return rc;
+  RS2_TRY(decode_host(plan, axis, count, sliver_idx, slivers, sliver_len, sliver_symbol_size,
+                      &pulled));
   if (consistency_check == RS2_CHECK_DEFAULT) {
     // config.rs:621-640: with primary slivers, every systematic index the decoder pulled from
     // the input counts as already verified (the caller verified each sliver on receipt); with
@@ -3407,12 +3320,11 @@ int rs2_decode_and_verify(rs2_plan* plan, int axis, uint32_t count, const uint16
     if (axis == RS2_AXIS_PRIMARY)
       for (uint32_t i = 0; i < pulled; ++i)
         if (sliver_idx[i] < plan->kp) verified[sliver_idx[i]] = 1;
-    rc = default_check(plan, verified, hashes, plan->dev_blob.as<uint8_t>(),
-                       int64_t(plan->kp) * plan->ks * plan->s, plan->stream);
+    RS2_TRY(default_check(plan, verified, hashes, plan->dev_blob.as<uint8_t>(),
+                          int64_t(plan->kp) * plan->ks * plan->s, plan->stream));
   } else if (consistency_check == RS2_CHECK_STRICT) {
-    rc = strict_check(plan, blob_id, plan->dev_blob.as<uint8_t>(), plan->stream);
+    RS2_TRY(strict_check(plan, blob_id, plan->dev_blob.as<uint8_t>(), plan->stream));
   }
-  if (rc != RS2_OK) return rc;
   return blob_to_host(plan, blob_out);
 }
 
@@ -3429,27 +3341,24 @@ int rs2_decode_and_verify_device(rs2_plan* plan, int axis, uint32_t count,
   if (consistency_check != RS2_CHECK_SKIP && consistency_check != RS2_CHECK_DEFAULT &&
       consistency_check != RS2_CHECK_STRICT)
     return fail(RS2_E_INVALID_ARGUMENT, "bad consistency check");
-  ALIGN_TRY(check_decode_ptrs(count, d_slivers_base, sliver_off, d_blob_out));
+  RS2_TRY(check_decode_ptrs(count, d_slivers_base, sliver_off, d_blob_out));
   HIP_TRY(hipSetDevice(plan->ctx->device));
   std::vector<std::pair<uint16_t, uint32_t>> chosen;
   uint32_t pulled = 0;
-  int rc = select_slivers(plan, axis, count, sliver_idx, nullptr, nullptr, chosen, &pulled);
-  if (rc != RS2_OK) return rc;
+  RS2_TRY(select_slivers(plan, axis, count, sliver_idx, nullptr, nullptr, chosen, &pulled));
   hipStream_t st = pick_stream(plan, stream);
   uint8_t* out = reinterpret_cast<uint8_t*>(d_blob_out);
-  rc = decode_device(plan, axis, chosen, reinterpret_cast<const uint8_t*>(d_slivers_base),
-                     sliver_off, out, st);
-  if (rc != RS2_OK) return rc;
+  RS2_TRY(decode_device(plan, axis, chosen, reinterpret_cast<const uint8_t*>(d_slivers_base),
+                        sliver_off, out, st));
   if (consistency_check == RS2_CHECK_DEFAULT) {
     std::vector<uint8_t> verified(plan->kp, 0);  // as rs2_decode_and_verify
     if (axis == RS2_AXIS_PRIMARY)
       for (uint32_t i = 0; i < pulled; ++i)
         if (sliver_idx[i] < plan->kp) verified[sliver_idx[i]] = 1;
-    rc = default_check(plan, verified, hashes, out, int64_t(plan->blob_len), st);
+    RS2_TRY(default_check(plan, verified, hashes, out, int64_t(plan->blob_len), st));
   } else if (consistency_check == RS2_CHECK_STRICT) {
-    rc = strict_check(plan, blob_id, out, st);
+    RS2_TRY(strict_check(plan, blob_id, out, st));
   }
-  if (rc != RS2_OK) return rc;
   HIP_TRY(hipStreamSynchronize(st));
   return RS2_OK;
 }
@@ -3462,8 +3371,7 @@ int rs2_encode_1d(uint16_t k, uint16_t n_shards, uint16_t symbol_size, uint32_t 
   if (n_shards < k || k == 0)
     return fail(RS2_E_INCOMPATIBLE_PARAMETERS, "n_shards must be at least n_source_symbols");
   Context* ctx = nullptr;
-  int rc = get_context(&ctx);
-  if (rc != RS2_OK) return rc;
+  RS2_TRY(get_context(&ctx));
   const int64_t s = symbol_size, K = k, N = n_shards;
   const size_t in_bytes = size_t(batch) * K * s, out_bytes = size_t(batch) * N * s;
   for (uint32_t b = 0; b < batch; ++b) std::memcpy(out_all + b * N * s, data + b * K * s, K * s);
@@ -3475,12 +3383,10 @@ int rs2_encode_1d(uint16_t k, uint16_t n_shards, uint16_t symbol_size, uint32_t 
   HIP_TRY(hipMemcpyAsync(din.p, data, in_bytes, hipMemcpyHostToDevice, st));
   PlannedJob pj;
   JobMem mem;
-  rc = plan_encode(uint32_t(K), uint32_t(N - K), int(s), din.as<uint8_t>(), K * s,
-                   [&](uint32_t i) { return int64_t(i) * s; }, dout.as<uint8_t>(), N * s,
-                   [&](uint32_t j) { return (K + int64_t(j)) * s; }, INT64_MAX, pj);
-  if (rc != RS2_OK) return rc;
-  rc = bind_encode(ctx, pj, mem, st);
-  if (rc != RS2_OK) return rc;
+  RS2_TRY(plan_encode(uint32_t(K), uint32_t(N - K), int(s), din.as<uint8_t>(), K * s,
+                      [&](uint32_t i) { return int64_t(i) * s; }, dout.as<uint8_t>(), N * s,
+                      [&](uint32_t j) { return (K + int64_t(j)) * s; }, INT64_MAX, pj));
+  RS2_TRY(bind_encode(ctx, pj, mem, st));
   HIP_TRY(pj.launch(int(batch), st));
   HIP_TRY(hipStreamSynchronize(st));
   for (uint32_t b = 0; b < batch; ++b)
@@ -3495,8 +3401,7 @@ int rs2_decode_1d(uint16_t k, uint16_t n_shards, uint16_t symbol_size, uint32_t 
   if (symbol_size == 0 || symbol_size % 2 || n_shards <= k || k == 0)
     return fail(RS2_E_INCOMPATIBLE_PARAMETERS, "incompatible parameters");
   Context* ctx = nullptr;
-  int rc = get_context(&ctx);
-  if (rc != RS2_OK) return rc;
+  RS2_TRY(get_context(&ctx));
   const int64_t s = symbol_size, K = k, N = n_shards;
   std::vector<int64_t> present(N, -1);
   std::vector<uint32_t> order;
@@ -3544,10 +3449,8 @@ int rs2_decode_1d(uint16_t k, uint16_t n_shards, uint16_t symbol_size, uint32_t 
   sp.dst_ls = 0;
   sp.dst.resize(K);
   for (int64_t i = 0; i < K; ++i) sp.dst[i] = i * s;
-  rc = plan_decode(sp, D.pj);
-  if (rc != RS2_OK) return rc;
-  rc = bind_decode(ctx, D.pj, D.mem, st);
-  if (rc != RS2_OK) return rc;
+  RS2_TRY(plan_decode(sp, D.pj));
+  RS2_TRY(bind_decode(ctx, D.pj, D.mem, st));
   HIP_TRY(D.pj.launch(1, st));
   HIP_TRY(hipMemcpyAsync(D.hout.p, dout.p, size_t(K) * s, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
@@ -3571,12 +3474,10 @@ int rs2_verifier_create(uint16_t n_shards, uint16_t symbol_size, int axis, rs2_v
   if (symbol_size == 0 || symbol_size % 2)
     return fail(RS2_E_INCOMPATIBLE_PARAMETERS, "symbol_size must be a multiple of the required alignment");
   uint16_t kp, ks;
-  int rc = rs2_source_symbols_for_n_shards(n_shards, &kp, &ks);
-  if (rc != RS2_OK) return rc;
+  RS2_TRY(rs2_source_symbols_for_n_shards(n_shards, &kp, &ks));
   if (n_shards > kMaxShards) return fail(RS2_E_UNSUPPORTED, "n_shards above 65535");
   Context* ctx = nullptr;
-  rc = get_context(&ctx);
-  if (rc != RS2_OK) return rc;
+  RS2_TRY(get_context(&ctx));
   auto v = std::make_unique<rs2_verifier>();
   v->ctx = ctx;
   v->n = n_shards;
@@ -3593,11 +3494,11 @@ void rs2_verifier_destroy(rs2_verifier* v) {
   (void)hipSetDevice(v->ctx->device);
   if (v->stream) (void)hipStreamSynchronize(v->stream);
   if (v->done) (void)hipEventSynchronize(v->done);  // work queued on a caller's stream
-  const bool prev = t_quiesced;
-  t_quiesced = true;
+  const Quiesced quiesced;
   delete v;
-  t_quiesced = prev;
 }
+
+}  // extern "C"
 
 namespace {
 // A pooled verifier for one host-buffer call (Context::verifier_pool); returned on scope exit
@@ -3609,8 +3510,7 @@ struct VerifierLease {
   VerifierLease(const VerifierLease&) = delete;
   VerifierLease& operator=(const VerifierLease&) = delete;
   int get(uint16_t n_shards, uint16_t symbol_size, int axis) {
-    int rc = get_context(&ctx);
-    if (rc != RS2_OK) return rc;
+    RS2_TRY(get_context(&ctx));
     {
       std::lock_guard<std::mutex> lk(ctx->pool_mu);
       auto& free_ = ctx->verifier_pool[std::make_tuple(int(n_shards), int(symbol_size), axis)];
@@ -3659,9 +3559,31 @@ uint64_t merkle_n_nodes(uint64_t n) {
   return tot + n;
 }
 
-// Expand `count` back-to-back slivers on the orthogonal axis (their n - k repair symbols each,
-// in v->repair) and leaf-hash all n symbols of each (v->leaves), on st.
-int verifier_leaves(rs2_verifier* v, uint32_t count, const uint8_t* din, hipStream_t st);
+// The n leaf hashes (v->leaves) of `count` back-to-back slivers, on st, without an expanded
+// copy: each sliver's n - k repair symbols on the orthogonal axis go to a compact
+// [count][n - k][s] buffer (v->repair) and the leaf kernel reads its systematic symbols in place
+// (rs2k_launch_leaf_hash mode 4); recovery symbols gather from the same two places
+// (proof_gather_kernel).
+int verifier_leaves(rs2_verifier* v, uint32_t count, const uint8_t* din, hipStream_t st) {
+  const int64_t n = v->n, K = v->k, s = v->s;
+  // a previous call on another stream still owns the scratch buffers: order after it, so the
+  // done event recorded at the end of this call also covers that one
+  if (v->done) HIP_TRY(hipStreamWaitEvent(st, v->done, 0));
+  HIP_TRY(v->leaves.ensure(size_t(count) * n * 32));
+  uint8_t* rep = nullptr;
+  if (n > K) {
+    HIP_TRY(v->repair.ensure(size_t(count) * (n - K) * s));
+    rep = v->repair.as<uint8_t>();
+    RS2_TRY(plan_encode(uint32_t(K), uint32_t(n - K), int(s), din, K * s,
+                        [&](uint32_t i) { return int64_t(i) * s; }, rep, (n - K) * s,
+                        [&](uint32_t j) { return int64_t(j) * s; }, INT64_MAX, v->job));
+    RS2_TRY(bind_encode(v->ctx, v->job, v->mem, st));
+    HIP_TRY(v->job.launch(int(count), st));
+  }
+  SymbolMap map{din, rep, nullptr, int(n), int(count), int(K), int(s)};
+  HIP_TRY(rs2k_launch_leaf_hash(map, 4, int64_t(count) * n, 1, v->leaves.as<uint8_t>(), st));
+  return RS2_OK;
+}
 
 // the verifier's last work on st (any caller stream): rs2_verifier_destroy waits for it
 int verifier_mark_done(rs2_verifier* v, hipStream_t st) {
@@ -3671,16 +3593,17 @@ int verifier_mark_done(rs2_verifier* v, hipStream_t st) {
 }
 }  // namespace
 
+extern "C" {
+
 int rs2_verifier_roots_device_async(rs2_verifier* v, uint32_t count, const void* d_slivers,
                                     void* d_roots, void* stream) {
   if (!v || (count && (!d_slivers || !d_roots))) return fail(RS2_E_INVALID_ARGUMENT, "null argument");
-  ALIGN_TRY(check_symbol_ptr(d_slivers, "d_slivers"));
-  ALIGN_TRY(check_digest_ptr(d_roots, "d_roots"));
+  RS2_TRY(check_symbol_ptr(d_slivers, "d_slivers"));
+  RS2_TRY(check_digest_ptr(d_roots, "d_roots"));
   if (count == 0) return RS2_OK;
   HIP_TRY(hipSetDevice(v->ctx->device));
   hipStream_t st = abi_stream(stream, v->stream);
-  int rc = verifier_leaves(v, count, reinterpret_cast<const uint8_t*>(d_slivers), st);
-  if (rc != RS2_OK) return rc;
+  RS2_TRY(verifier_leaves(v, count, reinterpret_cast<const uint8_t*>(d_slivers), st));
   uint8_t* scratch = nullptr;
   if (const size_t sb = tree_scratch_bytes(count, v->n)) {
     HIP_TRY(v->tree_scratch.ensure(sb));
@@ -3700,18 +3623,17 @@ int rs2_verifier_recovery_symbols_device_async(rs2_verifier* v, uint32_t count,
                                                void* stream) {
   if (!v || (count && (!d_slivers || !target_sliver_index || !d_symbols || !d_proofs)))
     return fail(RS2_E_INVALID_ARGUMENT, "null argument");
-  ALIGN_TRY(check_symbol_ptr(d_slivers, "d_slivers"));
-  ALIGN_TRY(check_symbol_ptr(d_symbols, "d_symbols"));
-  ALIGN_TRY(check_digest_ptr(d_proofs, "d_proofs"));
-  ALIGN_TRY(check_digest_ptr(d_nodes, "d_nodes"));
+  RS2_TRY(check_symbol_ptr(d_slivers, "d_slivers"));
+  RS2_TRY(check_symbol_ptr(d_symbols, "d_symbols"));
+  RS2_TRY(check_digest_ptr(d_proofs, "d_proofs"));
+  RS2_TRY(check_digest_ptr(d_nodes, "d_nodes"));
   for (uint32_t i = 0; i < count; ++i)
     if (target_sliver_index[i] >= v->n)  // slivers.rs check_index -> RecoverySymbolError::IndexTooLarge
       return fail(RS2_E_INVALID_ARGUMENT, "target index too large");
   if (count == 0) return RS2_OK;
   HIP_TRY(hipSetDevice(v->ctx->device));
   hipStream_t st = abi_stream(stream, v->stream);
-  int rc = verifier_leaves(v, count, reinterpret_cast<const uint8_t*>(d_slivers), st);
-  if (rc != RS2_OK) return rc;
+  RS2_TRY(verifier_leaves(v, count, reinterpret_cast<const uint8_t*>(d_slivers), st));
   const int64_t n = v->n, nn = int64_t(merkle_n_nodes(uint64_t(n)));
   uint8_t* nodes = reinterpret_cast<uint8_t*>(d_nodes);
   if (!nodes) {
@@ -3748,8 +3670,7 @@ int rs2_recovery_symbols(uint16_t n_shards, uint16_t symbol_size, int axis, uint
   if (count && (!slivers || !sliver_len || !target_sliver_index || !symbols_out || !proofs_out))
     return fail(RS2_E_INVALID_ARGUMENT, "null argument");
   VerifierLease lease;
-  int rc = lease.get(n_shards, symbol_size, axis);
-  if (rc != RS2_OK) return rc;
+  RS2_TRY(lease.get(n_shards, symbol_size, axis));
   rs2_verifier* v = lease.v;
   const uint64_t len = uint64_t(v->k) * symbol_size;
   for (uint32_t i = 0; i < count; ++i)
@@ -3772,9 +3693,8 @@ int rs2_recovery_symbols(uint16_t n_shards, uint16_t symbol_size, int axis, uint
     std::memcpy(static_cast<uint8_t*>(v->h_in.p) + size_t(i) * len, slivers[i], len);
   HIP_TRY(hipMemcpyAsync(v->input.p, v->h_in.p, size_t(count) * len, hipMemcpyHostToDevice,
                          v->stream));
-  rc = rs2_verifier_recovery_symbols_device_async(v, count, v->input.p, target_sliver_index,
-                                                  v->sym_out.p, v->proof_out.p, nullptr, nullptr);
-  if (rc != RS2_OK) return rc;
+  RS2_TRY(rs2_verifier_recovery_symbols_device_async(v, count, v->input.p, target_sliver_index,
+                                                     v->sym_out.p, v->proof_out.p, nullptr, nullptr));
   uint8_t* ho = static_cast<uint8_t*>(v->h_out.p);
   HIP_TRY(hipMemcpyAsync(ho, v->sym_out.p, sym_b, hipMemcpyDeviceToHost, v->stream));
   if (L) HIP_TRY(hipMemcpyAsync(ho + sym_b, v->proof_out.p, prf_b, hipMemcpyDeviceToHost, v->stream));
@@ -3792,8 +3712,7 @@ int rs2_merkle_proof_roots(uint32_t count, const uint8_t* leaves, uint32_t leaf_
   if (leaf_len % 2) return fail(RS2_E_INVALID_ARGUMENT, "leaf length must be even (symbols are)");
   if (count == 0) return RS2_OK;
   Context* ctx = nullptr;
-  int rc = get_context(&ctx);
-  if (rc != RS2_OK) return rc;
+  RS2_TRY(get_context(&ctx));
   hipStream_t st = ctx->util_stream;
   DevBuf dl, dd, di, dp, dr;
   HIP_TRY(dl.ensure(std::max<size_t>(size_t(count) * leaf_len, 16)));
@@ -3815,44 +3734,13 @@ int rs2_merkle_proof_roots(uint32_t count, const uint8_t* leaves, uint32_t leaf_
   return RS2_OK;
 }
 
-namespace {
-
-// The n leaf hashes of every sliver without an expanded copy: the repair symbols go to a
-// compact [count][n - k][s] buffer (v->repair) and the leaf kernel reads each sliver's
-// systematic symbols in place (rs2k_launch_leaf_hash mode 4); recovery symbols gather from
-// the same two places (proof_gather_kernel).
-int verifier_leaves(rs2_verifier* v, uint32_t count, const uint8_t* din, hipStream_t st) {
-  const int64_t n = v->n, K = v->k, s = v->s;
-  // a previous call on another stream still owns the scratch buffers: order after it, so the
-  // done event recorded at the end of this call also covers that one
-  if (v->done) HIP_TRY(hipStreamWaitEvent(st, v->done, 0));
-  HIP_TRY(v->leaves.ensure(size_t(count) * n * 32));
-  uint8_t* rep = nullptr;
-  if (n > K) {
-    HIP_TRY(v->repair.ensure(size_t(count) * (n - K) * s));
-    rep = v->repair.as<uint8_t>();
-    int rc = plan_encode(uint32_t(K), uint32_t(n - K), int(s), din, K * s,
-                         [&](uint32_t i) { return int64_t(i) * s; }, rep, (n - K) * s,
-                         [&](uint32_t j) { return int64_t(j) * s; }, INT64_MAX, v->job);
-    if (rc != RS2_OK) return rc;
-    rc = bind_encode(v->ctx, v->job, v->mem, st);
-    if (rc != RS2_OK) return rc;
-    HIP_TRY(v->job.launch(int(count), st));
-  }
-  SymbolMap map{din, rep, nullptr, int(n), int(count), int(K), int(s)};
-  HIP_TRY(rs2k_launch_leaf_hash(map, 4, int64_t(count) * n, 1, v->leaves.as<uint8_t>(), st));
-  return RS2_OK;
-}
-}  // namespace
-
 int rs2_sliver_merkle_roots(uint16_t n_shards, uint16_t symbol_size, int axis, uint32_t count,
                             const uint8_t* const* slivers, const uint64_t* sliver_len,
                             uint8_t* roots_out) {
   if (count && (!slivers || !sliver_len || !roots_out))
     return fail(RS2_E_INVALID_ARGUMENT, "null argument");
   VerifierLease lease;
-  int rc = lease.get(n_shards, symbol_size, axis);
-  if (rc != RS2_OK) return rc;
+  RS2_TRY(lease.get(n_shards, symbol_size, axis));
   rs2_verifier* v = lease.v;
   const uint64_t len = uint64_t(v->k) * symbol_size;
   for (uint32_t i = 0; i < count; ++i)
@@ -3869,8 +3757,7 @@ int rs2_sliver_merkle_roots(uint16_t n_shards, uint16_t symbol_size, int axis, u
     std::memcpy(static_cast<uint8_t*>(v->h_in.p) + size_t(i) * len, slivers[i], len);
   HIP_TRY(hipMemcpyAsync(v->input.p, v->h_in.p, size_t(count) * len, hipMemcpyHostToDevice,
                          v->stream));
-  rc = rs2_verifier_roots_device_async(v, count, v->input.p, v->roots.p, nullptr);
-  if (rc != RS2_OK) return rc;
+  RS2_TRY(rs2_verifier_roots_device_async(v, count, v->input.p, v->roots.p, nullptr));
   HIP_TRY(hipMemcpyAsync(v->h_out.p, v->roots.p, size_t(count) * 32, hipMemcpyDeviceToHost,
                          v->stream));
   HIP_TRY(hipStreamSynchronize(v->stream));
@@ -3892,8 +3779,7 @@ int rs2_merkle_root(const uint8_t* leaves, uint32_t n_leaves, uint32_t leaf_len,
   }
   if (leaf_len > 0x7FFFFFFFu / 2) return fail(RS2_E_UNSUPPORTED, "leaf too large");
   Context* ctx = nullptr;
-  int rc = get_context(&ctx);
-  if (rc != RS2_OK) return rc;
+  RS2_TRY(get_context(&ctx));
   hipStream_t st = ctx->util_stream;
   DevBuf din, digests, tmp, root;
   HIP_TRY(din.ensure(size_t(n_leaves) * leaf_len));
@@ -3903,8 +3789,7 @@ int rs2_merkle_root(const uint8_t* leaves, uint32_t n_leaves, uint32_t leaf_len,
     HIP_TRY(hipMemcpyAsync(din.p, leaves, size_t(n_leaves) * leaf_len, hipMemcpyHostToDevice, st));
   SymbolMap map{din.as<uint8_t>(), nullptr, nullptr, 0, 0, 0, int(leaf_len)};
   HIP_TRY(rs2k_launch_leaf_hash(map, 1, n_leaves, 1, digests.as<uint8_t>(), st));
-  rc = device_merkle_root(digests.as<uint8_t>(), n_leaves, tmp, root.as<uint8_t>(), st);
-  if (rc != RS2_OK) return rc;
+  RS2_TRY(device_merkle_root(digests.as<uint8_t>(), n_leaves, tmp, root.as<uint8_t>(), st));
   HIP_TRY(hipMemcpyAsync(root_out, root.p, 32, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   return RS2_OK;
@@ -3921,8 +3806,7 @@ int rs2_codec_create(uint16_t k, uint16_t n_shards, uint16_t symbol_size, rs2_co
   if (!rate_supported(k, uint32_t(n_shards) - k))
     return fail(RS2_E_INCOMPATIBLE_PARAMETERS, "unsupported shard count");
   Context* ctx = nullptr;
-  int rc = get_context(&ctx);
-  if (rc != RS2_OK) return rc;
+  RS2_TRY(get_context(&ctx));
   auto c = std::make_unique<rs2_codec>();
   c->ctx = ctx;
   c->n = n_shards;
@@ -3936,12 +3820,10 @@ void rs2_codec_destroy(rs2_codec* c) {
   if (!c) return;
   (void)hipSetDevice(c->ctx->device);
   if (c->enc_done) (void)hipEventSynchronize(c->enc_done);
-  for (auto& e : c->dec_done)
-    if (e) (void)hipEventSynchronize(e);
-  const bool prev = t_quiesced;
-  t_quiesced = true;
+  for (auto& sl : c->dec)
+    if (sl.done) (void)hipEventSynchronize(sl.done);
+  const Quiesced quiesced;
   delete c;
-  t_quiesced = prev;
 }
 
 int rs2_codec_encode_device_async(rs2_codec* c, uint32_t lines, const void* d_src,
@@ -3949,12 +3831,12 @@ int rs2_codec_encode_device_async(rs2_codec* c, uint32_t lines, const void* d_sr
                                   void* d_repair, uint64_t repair_sym_stride,
                                   uint64_t repair_line_stride, void* stream) {
   if (!c || (lines && (!d_src || !d_repair))) return fail(RS2_E_INVALID_ARGUMENT, "null argument");
-  ALIGN_TRY(check_symbol_ptr(d_src, "d_src"));
-  ALIGN_TRY(check_symbol_ptr(d_repair, "d_repair"));
-  ALIGN_TRY(check_symbol_step(src_sym_stride, "src_sym_stride"));
-  ALIGN_TRY(check_symbol_step(src_line_stride, "src_line_stride"));
-  ALIGN_TRY(check_symbol_step(repair_sym_stride, "repair_sym_stride"));
-  ALIGN_TRY(check_symbol_step(repair_line_stride, "repair_line_stride"));
+  RS2_TRY(check_symbol_ptr(d_src, "d_src"));
+  RS2_TRY(check_symbol_ptr(d_repair, "d_repair"));
+  RS2_TRY(check_symbol_step(src_sym_stride, "src_sym_stride"));
+  RS2_TRY(check_symbol_step(src_line_stride, "src_line_stride"));
+  RS2_TRY(check_symbol_step(repair_sym_stride, "repair_sym_stride"));
+  RS2_TRY(check_symbol_step(repair_line_stride, "repair_line_stride"));
   if (lines == 0) return RS2_OK;
   if (src_sym_stride < c->s || repair_sym_stride < c->s)
     return fail(RS2_E_INVALID_ARGUMENT, "symbol stride smaller than the symbol");
@@ -3967,12 +3849,10 @@ int rs2_codec_encode_device_async(rs2_codec* c, uint32_t lines, const void* d_sr
   if (!std::equal(key, key + 4, c->enc_key)) {
     if (c->enc_done) HIP_TRY(hipEventSynchronize(c->enc_done));  // old arrays may be in use
     const int64_t ss = key[0], rs = key[2];
-    int rc = plan_encode(uint32_t(c->k), uint32_t(c->n - c->k), int(c->s), src, key[1],
-                         [&](uint32_t i) { return int64_t(i) * ss; }, dst, key[3],
-                         [&](uint32_t j) { return int64_t(j) * rs; }, INT64_MAX, c->enc);
-    if (rc != RS2_OK) return rc;
-    rc = bind_encode(c->ctx, c->enc, c->enc_mem, st);
-    if (rc != RS2_OK) return rc;
+    RS2_TRY(plan_encode(uint32_t(c->k), uint32_t(c->n - c->k), int(c->s), src, key[1],
+                        [&](uint32_t i) { return int64_t(i) * ss; }, dst, key[3],
+                        [&](uint32_t j) { return int64_t(j) * rs; }, INT64_MAX, c->enc));
+    RS2_TRY(bind_encode(c->ctx, c->enc, c->enc_mem, st));
     std::copy(key, key + 4, c->enc_key);
   }
   for (int b = 0; b < c->enc.job.n_in; ++b) c->enc.job.in[b].base = src;
@@ -3990,12 +3870,12 @@ int rs2_codec_decode_device_async(rs2_codec* c, uint32_t lines, uint32_t count,
   if (!c || (count && (!idx || !sym_off)) || (lines && (!d_base || !d_out)))
     return fail(RS2_E_INVALID_ARGUMENT, "null argument");
   if (out_sym_stride < c->s) return fail(RS2_E_INVALID_ARGUMENT, "symbol stride smaller than the symbol");
-  ALIGN_TRY(check_symbol_ptr(d_base, "d_base"));
-  ALIGN_TRY(check_symbol_ptr(d_out, "d_out"));
-  ALIGN_TRY(check_symbol_step(line_stride, "line_stride"));
-  ALIGN_TRY(check_symbol_step(out_sym_stride, "out_sym_stride"));
-  ALIGN_TRY(check_symbol_step(out_line_stride, "out_line_stride"));
-  for (uint32_t i = 0; i < count; ++i) ALIGN_TRY(check_symbol_step(sym_off[i], "sym_off[i]"));
+  RS2_TRY(check_symbol_ptr(d_base, "d_base"));
+  RS2_TRY(check_symbol_ptr(d_out, "d_out"));
+  RS2_TRY(check_symbol_step(line_stride, "line_stride"));
+  RS2_TRY(check_symbol_step(out_sym_stride, "out_sym_stride"));
+  RS2_TRY(check_symbol_step(out_line_stride, "out_line_stride"));
+  for (uint32_t i = 0; i < count; ++i) RS2_TRY(check_symbol_step(sym_off[i], "sym_off[i]"));
   const int64_t K = c->k, N = c->n, s = c->s;
   // the first K distinct valid indices (the crate ignores duplicates and invalid indices)
   std::vector<int64_t> present(N, -1);
@@ -4009,59 +3889,20 @@ int rs2_codec_decode_device_async(rs2_codec* c, uint32_t lines, uint32_t count,
   if (lines == 0) return RS2_OK;
   HIP_TRY(hipSetDevice(c->ctx->device));
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int slot = c->dec_slot;
-  c->dec_slot ^= 1;
-  if (c->dec_done[slot]) HIP_TRY(hipEventSynchronize(c->dec_done[slot]));
-  const uint8_t* base = reinterpret_cast<const uint8_t*>(d_base);
-  uint8_t* out = reinterpret_cast<uint8_t*>(d_out);
-  std::vector<int64_t>& cs = c->copy_src_h[slot];
-  std::vector<int64_t>& cd = c->copy_dst_h[slot];
-  cs.clear();
-  cd.clear();
-  for (int64_t i = 0; i < K; ++i)
-    if (present[i] >= 0) {
-      cs.push_back(present[i]);
-      cd.push_back(i * int64_t(out_sym_stride));
-    }
-  const bool run_codec = cs.size() < size_t(K);
-  bool fused = false;
-  PlannedJob& pj = c->dec[slot];
-  if (run_codec) {
-    DecodeSpec sp;
-    sp.K = uint32_t(K);
-    sp.R = uint32_t(N - K);
-    sp.symbol_size = int(s);
-    sp.present = present;
-    sp.src_base = base;
-    sp.src_ls = int64_t(line_stride);
-    sp.dst_base = out;
-    sp.dst_ls = int64_t(out_line_stride);
-    sp.dst_limit = int64_t(std::min<uint64_t>(out_limit, uint64_t(INT64_MAX)));
-    sp.dst.resize(K);
-    for (int64_t i = 0; i < K; ++i) sp.dst[i] = i * int64_t(out_sym_stride);
-    sp.copy_present = !cs.empty() && s >= 4;
-    int rc = plan_decode(sp, pj);
-    if (rc != RS2_OK) return rc;
-    fused = sp.copy_present && copy_covered(pj);
-  }
-  if (!cs.empty() && !fused) {
-    HIP_TRY(c->copy_src[slot].ensure(cs.size() * 8));
-    HIP_TRY(c->copy_dst[slot].ensure(cd.size() * 8));
-    HIP_TRY(c->ctx->upload(c->copy_src[slot].p, cs.data(), cs.size() * 8, st));
-    HIP_TRY(c->ctx->upload(c->copy_dst[slot].p, cd.data(), cd.size() * 8, st));
-    HIP_TRY(rs2k_launch_symbol_copy(base, c->copy_src[slot].as<int64_t>(), int64_t(line_stride), out,
-                                    c->copy_dst[slot].as<int64_t>(), int64_t(out_line_stride),
-                                    int(cs.size()), int(lines), int(s),
-                                    int64_t(std::min<uint64_t>(out_limit, uint64_t(INT64_MAX))), st));
-  }
-  if (run_codec) {
-    int rc = bind_decode(c->ctx, pj, c->dec_mem[slot], st);
-    if (rc != RS2_OK) return rc;
-    HIP_TRY(pj.launch(int(lines), st));
-  }
-  if (!c->dec_done[slot]) HIP_TRY(hipEventCreateWithFlags(&c->dec_done[slot], hipEventDisableTiming));
-  HIP_TRY(hipEventRecord(c->dec_done[slot], st));
-  return RS2_OK;
+  DecodeSpec sp;
+  sp.K = uint32_t(K);
+  sp.R = uint32_t(N - K);
+  sp.symbol_size = int(s);
+  sp.present = present;
+  sp.src_base = reinterpret_cast<const uint8_t*>(d_base);
+  sp.src_ls = int64_t(line_stride);
+  sp.dst_base = reinterpret_cast<uint8_t*>(d_out);
+  sp.dst_ls = int64_t(out_line_stride);
+  sp.dst_limit = int64_t(std::min<uint64_t>(out_limit, uint64_t(INT64_MAX)));
+  sp.dst.resize(K);
+  for (int64_t i = 0; i < K; ++i) sp.dst[i] = i * int64_t(out_sym_stride);
+  // no key: every call plans its erasure pattern anew
+  return run_decode(c->ctx, c->dec, c->dec_slot, sp, {}, true, int(lines), nullptr, st);
 }
 
 int rs2_copy_segments_device_async(const void* d_src, void* d_dst, uint32_t count_a,
@@ -4087,12 +3928,11 @@ int rs2_leaf_hashes_device_async(const void* d_symbols, uint64_t count, uint16_t
                                  void* d_leaves, void* stream) {
   if (count && (!d_symbols || !d_leaves)) return fail(RS2_E_INVALID_ARGUMENT, "null argument");
   if (symbol_size % 2) return fail(RS2_E_INVALID_ARGUMENT, "symbol_size must be even");
-  ALIGN_TRY(check_symbol_ptr(d_symbols, "d_symbols"));
-  ALIGN_TRY(check_digest_ptr(d_leaves, "d_leaves"));
+  RS2_TRY(check_symbol_ptr(d_symbols, "d_symbols"));
+  RS2_TRY(check_digest_ptr(d_leaves, "d_leaves"));
   if (count == 0) return RS2_OK;
   Context* ctx = nullptr;
-  int rc = get_context(&ctx);
-  if (rc != RS2_OK) return rc;
+  RS2_TRY(get_context(&ctx));
   SymbolMap map{reinterpret_cast<const uint8_t*>(d_symbols), nullptr, nullptr, 0, 0, 0, int(symbol_size)};
   HIP_TRY(rs2k_launch_leaf_hash(map, 1, int64_t(count), 1, reinterpret_cast<uint8_t*>(d_leaves),
                                 reinterpret_cast<hipStream_t>(stream)));
@@ -4107,12 +3947,11 @@ int rs2_merkle_roots_device_async(const void* d_leaves, uint32_t n_trees, uint32
     return fail(RS2_E_UNSUPPORTED, "trees of 1..65535 leaves supported by this build");
   if (leaf_stride % 16 || tree_stride % 16 || root_stride % 16)
     return fail(RS2_E_INVALID_ARGUMENT, "leaf/tree/root strides must be multiples of 16 bytes");
-  ALIGN_TRY(check_digest_ptr(d_leaves, "d_leaves"));
-  ALIGN_TRY(check_digest_ptr(d_roots, "d_roots"));
+  RS2_TRY(check_digest_ptr(d_leaves, "d_leaves"));
+  RS2_TRY(check_digest_ptr(d_roots, "d_roots"));
   if (n_trees == 0) return RS2_OK;
   Context* ctx = nullptr;
-  int rc = get_context(&ctx);
-  if (rc != RS2_OK) return rc;
+  RS2_TRY(get_context(&ctx));
   // above 4,096 leaves the folded level goes to scratch; the arena quarantines the range when
   // this buffer is released, so the queued launches keep it until the next device sync
   DevBuf scratch;
@@ -4130,11 +3969,10 @@ int rs2_blob_id_device_async(const void* d_hashes, uint16_t n_shards, uint64_t b
                              void* d_blob_id, void* stream) {
   if (!d_blob_id || (n_shards && !d_hashes)) return fail(RS2_E_INVALID_ARGUMENT, "null argument");
   if (n_shards > kMaxShards) return fail(RS2_E_UNSUPPORTED, "n_shards above 65535");
-  ALIGN_TRY(check_digest_ptr(d_hashes, "d_hashes"));
-  ALIGN_TRY(check_digest_ptr(d_blob_id, "d_blob_id"));
+  RS2_TRY(check_digest_ptr(d_hashes, "d_hashes"));
+  RS2_TRY(check_digest_ptr(d_blob_id, "d_blob_id"));
   Context* ctx = nullptr;
-  int rc = get_context(&ctx);
-  if (rc != RS2_OK) return rc;
+  RS2_TRY(get_context(&ctx));
   HIP_TRY(rs2k_launch_merkle_root(reinterpret_cast<const uint8_t*>(d_hashes), n_shards, blob_len,
                                   reinterpret_cast<uint8_t*>(d_blob_id),
                                   reinterpret_cast<hipStream_t>(stream)));
@@ -4146,8 +3984,7 @@ int rs2_blob_id_from_hashes(const uint8_t* hashes, uint16_t n_shards, uint64_t b
   if (!hashes || !blob_id_out) return fail(RS2_E_INVALID_ARGUMENT, "null argument");
   if (n_shards > kMaxShards) return fail(RS2_E_UNSUPPORTED, "n_shards above 65535");
   Context* ctx = nullptr;
-  int rc = get_context(&ctx);
-  if (rc != RS2_OK) return rc;
+  RS2_TRY(get_context(&ctx));
   hipStream_t st = ctx->util_stream;
   DevBuf dh, bid;
   HIP_TRY(dh.ensure(size_t(n_shards) * 64));
@@ -4168,8 +4005,7 @@ int rs2_quilt_layout_device_async(uint16_t n_rows, uint16_t n_cols, uint16_t sym
   if (!d_payload || !d_col_off || !d_col_len || !d_quilt)
     return fail(RS2_E_INVALID_ARGUMENT, "null argument");
   Context* ctx = nullptr;
-  int rc = get_context(&ctx);
-  if (rc != RS2_OK) return rc;
+  RS2_TRY(get_context(&ctx));
   HIP_TRY(rs2k_launch_quilt_layout(n_rows, n_cols, symbol_size,
                                    reinterpret_cast<const uint8_t*>(d_payload), d_col_off, d_col_len,
                                    reinterpret_cast<uint8_t*>(d_quilt),

@@ -1,0 +1,73 @@
+// Launchers of the HIP kernels, declared once.  The files that define them (rs2_codec.hip per
+// block size, rs2_hash.hip, rs2_copy.hip) and the host file that calls them (rs2_engine.cpp) include this
+// header, so a prototype that drifts on one side is a compile error ("conflicting types"), not
+// a link that succeeds and corrupts the kernel's arguments at run time.  Default arguments are
+// given here only; the definitions repeat none.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "rs2_device.h"
+
+extern "C" {
+#define RS2_DECL(CC)                                                                      \
+  hipError_t rs2k_launch_codec_##CC(const rs2::CodecJob* job, int n_tiles, int n_lines, \
+                                    int n_z, int mode, hipStream_t stream);
+RS2_DECL(1)
+RS2_DECL(2)
+RS2_DECL(4)
+RS2_DECL(8)
+RS2_DECL(16)
+RS2_DECL(32)
+RS2_DECL(64)
+RS2_DECL(128)
+RS2_DECL(256)
+RS2_DECL(512)
+#undef RS2_DECL
+hipError_t rs2k_launch_leaf_hash(rs2::SymbolMap map, int mode, int64_t count, int n_blobs,
+                                 uint8_t* d_out, hipStream_t stream);
+hipError_t rs2k_launch_merkle_trees(const uint8_t* d_leaves, int n, int n_row_trees,
+                                    int n_col_trees, int64_t row_base, int64_t row_stride,
+                                    int64_t col_base, int64_t col_stride, uint8_t* d_out,
+                                    int64_t out_stride, hipStream_t stream,
+                                    uint8_t* d_nodes = nullptr, int64_t nodes_stride = 0,
+                                    int n_blobs = 1, int64_t leaves_blob_stride = 0,
+                                    int64_t out_blob_stride = 0, uint8_t* d_scratch = nullptr);
+hipError_t rs2k_launch_batch_blob_copy(const uint8_t* src, int64_t src_stride,
+                                       const uint64_t* d_blob_lens, int64_t msg, uint8_t* dst,
+                                       int64_t dst_stride, int n_blobs, hipStream_t stream);
+hipError_t rs2k_launch_proof_gather(const uint8_t* d_sys, const uint8_t* d_rep, int n, int k,
+                                    int s, const uint8_t* d_nodes, int64_t nodes_stride,
+                                    const uint16_t* d_targets, int count, int path_len,
+                                    uint8_t* d_sym, uint8_t* d_proof, hipStream_t stream);
+hipError_t rs2k_launch_proof_roots(const uint8_t* d_leaf_digests, const uint32_t* d_leaf_index,
+                                   const uint8_t* d_paths, int path_len, int count,
+                                   uint8_t* d_roots, hipStream_t stream);
+hipError_t rs2k_launch_merkle_root(const uint8_t* d_pair_hashes, int n, uint64_t blob_len,
+                                   uint8_t* d_blob_id, hipStream_t stream, int n_blobs = 1,
+                                   const uint64_t* d_blob_lens = nullptr);
+hipError_t rs2k_launch_merkle_level(const uint8_t* d_in, int64_t cnt, uint8_t* d_out,
+                                    hipStream_t stream);
+hipError_t rs2k_launch_symbol_copy(const uint8_t* src, const int64_t* d_src_a, int64_t ssb,
+                                   uint8_t* dst, const int64_t* d_dst_a, int64_t dsb, int count_a,
+                                   int count_b, int s, int64_t dst_limit, hipStream_t stream);
+hipError_t rs2k_launch_segment_copy(const uint8_t* src, uint8_t* dst, uint32_t count_a,
+                                    const int64_t* d_src_a, const int64_t* d_dst_a, uint32_t count_b,
+                                    int64_t ssb, int64_t dsb, uint32_t len, int unit,
+                                    hipStream_t stream);
+hipError_t rs2k_launch_quilt_layout(int n_rows, int n_cols, int s, const uint8_t* payload,
+                                    const int64_t* col_off, const uint32_t* col_len,
+                                    uint8_t* quilt, hipStream_t stream);
+hipError_t rs2k_launch_host_upload(const void* src, void* dst, int64_t n, uint64_t* done,
+                                   uint64_t gen, hipStream_t stream);
+hipError_t rs2k_launch_upload_signal(uint64_t* done, uint64_t gen, hipStream_t stream);
+hipError_t rs2k_launch_codec_big_512(const rs2::CodecJobBig* d_job, int n_tiles, int n_lines,
+                                     int n_z, int mode, hipStream_t stream);
+hipError_t rs2k_launch_tail_rows(const uint8_t* src, int64_t have, uint8_t* dst, int64_t total,
+                                 hipStream_t stream);
+hipError_t rs2k_launch_row_gather(const uint8_t* src, const int64_t* d_src_off, uint8_t* dst,
+                                  int64_t row_bytes, int rows, hipStream_t stream);
+hipError_t rs2k_launch_build_mul_tables(const uint16_t* d_exp, const uint16_t* d_log,
+                                        const uint16_t* d_logs, int count, uint16_t* d_out,
+                                        hipStream_t stream);
+}
