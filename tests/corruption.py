@@ -1,0 +1,592 @@
+"""Verdicts under corruption: an oracle model and the case generators -- TEST ONLY (a plain
+module, no fixtures, no torch).
+
+The honest-data tests pin what the engine computes; this module pins what it REFUSES.  It holds
+
+  model_decode_and_verify(n, length, axis, slivers, hashes, blob_id, check)
+      decode_and_verify restated from oracle pieces only: O.decode_blob (drops duplicates and
+      surplus, truncates at the blob length), then
+        skip     accept;
+        default  the message is rebuilt from the decoded bytes (zero padding again) and every
+                 systematic primary row i < K_p that is not "verified" must have the Merkle root
+                 hashes[i][0].  "Verified" exists for the primary axis only: every index < K_p
+                 pulled from the input up to and including the one sliver that finds the
+                 workspace full.  Secondary hashes and repair rows are never looked at;
+        strict   the metadata of the decoded bytes must give the blob id passed in; the hashes
+                 are not looked at.
+      The reference sources are not available to this repository; these are the semantics the
+      mirror's docstrings and the existing tests pin (walrus_amd/encoding.py decode_and_verify,
+      tests/test_gpu_checks.py test_default_check_*).  A sliver of the wrong length is dropped by
+      the decode; whether it counts as pulled is pinned by neither and no case here has one.
+      At n >= 100 the blob id and the row roots come from the C restatement (oracle/rs2_cpu.c:
+      rs2cpu_encode, rs2cpu_sliver_root), where numpy takes seconds per verdict; the decode
+      stays O.decode_blob, which is the faster one (rs2cpu_decode_primary re-plans per column).
+      tests/test_corruption_model.py checks the C pieces, rs2cpu_decode_primary included,
+      against the numpy ones.
+
+  GEOMETRIES, cases(geo), groups(cases), materialise(case), expected(case)
+      the geometries and the case families: single-bit flips of sliver bytes (used, surplus and
+      duplicate slivers), flips that land in the zero padding of the message, metadata bytes
+      and a blob length one short.  A case never has an out-of-range index or a wrong size.
+
+  run_sequence(call, cases, honest_every=4)
+      the shared test body: every case against the model, honest calls in between, so that a
+      verdict path that reads state left by the previous call is caught.
+"""
+import ctypes
+import functools
+import hashlib
+import os
+import sys
+from dataclasses import dataclass, replace
+from itertools import groupby
+from typing import Optional, Tuple
+
+import numpy as np
+
+import rs2_oracle as O
+
+PRIMARY, SECONDARY = "primary", "secondary"
+CHECKS = ("skip", "default", "strict")
+C_MODEL_FROM = 100   # n_shards from which the model runs on the C restatement
+
+
+@dataclass(frozen=True)
+class Geometry:
+    id: str
+    n: int
+    length: int
+    symbol_size: int   # asserted against the engine's symbol_size_for_blob in the tests
+    grid: str          # "full": every symbol x offset; "cut": symbols rotate over the targets;
+                       # "few": one byte per family member (n = 1000)
+    what: str
+
+
+GEOMETRIES = {g.id: g for g in (
+    Geometry("G0_0", 10, 0, 2, "full", "empty blob: every row empty"),
+    Geometry("G0_1", 10, 1, 2, "full", "one-byte blob: row 0 partial, the others empty"),
+    Geometry("G1", 10, 150, 6, "full", "row 3 has 24 valid bytes, its symbols 4..6 are padding"),
+    Geometry("G2", 10, 113, 6, "full", "row 2 ends mid-element, row 3 is empty"),
+    Geometry("G3", 13, 2901, 66, "full", "one chunk + 2-byte tail; last row ends in a symbol"),
+    Geometry("G4", 100, 293001, 130, "cut", "LDS-window leaves, C = 64 / 128, partial last row"),
+    Geometry("G5", 1000, 400001, 2, "few", "C = 512, 1000-leaf trees, 1 partial + 33 empty rows"),
+)}
+
+
+# ---------------------------------------------------------------------------------------------
+# model backends
+# ---------------------------------------------------------------------------------------------
+class _Numpy:
+    @staticmethod
+    def encode(blob: bytes, n: int):
+        enc = O.encode_with_metadata(blob, n)
+        return enc.primary, enc.secondary, list(enc.pair_hashes), enc.blob_id
+
+    @staticmethod
+    def decode(n, length, axis, slivers):
+        return O.decode_blob(n, length, axis, slivers)
+
+    @staticmethod
+    def row_root(p: O.Rs2Params, row: bytes) -> bytes:
+        return O.sliver_merkle_root(np.frombuffer(row, np.uint8), PRIMARY, p)
+
+    @staticmethod
+    def blob_id(blob: bytes, n: int) -> bytes:
+        return O.compute_metadata(blob, n)[1]
+
+
+@functools.lru_cache(maxsize=None)
+def _cpu_lib():
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden"))
+    from make_fullsize import load_cpu
+    lib = load_cpu()
+    P = ctypes.c_void_p
+    lib.rs2cpu_sliver_root.argtypes = [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int, P, P]
+    lib.rs2cpu_decode_primary.argtypes = [ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint32, P,
+                                          P, P]
+    return lib
+
+
+class _C:
+    @staticmethod
+    def encode(blob: bytes, n: int):
+        lib = _cpu_lib()
+        p = O.Rs2Params.for_blob(n, len(blob))
+        src = np.frombuffer(bytes(blob) or b"\0", np.uint8)
+        prim = np.empty((n, p.n_secondary * p.symbol_size), np.uint8)
+        sec = np.empty((n, p.n_primary * p.symbol_size), np.uint8)
+        hashes = np.empty(n * 64, np.uint8)
+        bid = np.empty(32, np.uint8)
+        if n >= 1000:   # the threaded restatement: the same bytes (tests/test_cpu_port.py)
+            rc = lib.rs2cpu_encode_mt(n, src.ctypes.data, len(blob), prim.ctypes.data,
+                                      sec.ctypes.data, hashes.ctypes.data, bid.ctypes.data,
+                                      min(16, os.cpu_count() or 1))
+        else:
+            rc = lib.rs2cpu_encode(n, src.ctypes.data, len(blob), prim.ctypes.data,
+                                   sec.ctypes.data, hashes.ctypes.data, bid.ctypes.data)
+        assert rc == 0
+        h = hashes.tobytes()
+        return prim, sec, [(h[64 * i:64 * i + 32], h[64 * i + 32:64 * i + 64])
+                           for i in range(n)], bid.tobytes()
+
+    # the numpy decode handles every column in one pass and is the faster one at these sizes
+    decode = staticmethod(_Numpy.decode)
+
+    @staticmethod
+    def blob_id(blob: bytes, n: int) -> bytes:
+        return _C.encode(blob, n)[3]
+
+
+class _CDecode(_C):
+    """_C with rs2cpu_decode_primary for the primary axis (one decode per column, slower)."""
+
+    @staticmethod
+    def decode(n, length, axis, slivers):
+        if axis != PRIMARY:
+            return O.decode_blob(n, length, axis, slivers)
+        lib = _cpu_lib()
+        slivers = list(slivers)
+        p = O.Rs2Params.for_blob(n, length)
+        want = p.n_secondary * p.symbol_size
+        assert all(len(d) == want and i < n for i, d in slivers)  # the C decode checks neither
+        keep = [np.frombuffer(bytes(d), np.uint8) for _, d in slivers]
+        idx = (ctypes.c_uint16 * len(keep))(*[i for i, _ in slivers])
+        ptrs = (ctypes.c_void_p * len(keep))(*[a.ctypes.data for a in keep])
+        out = np.zeros(max(length, 1), np.uint8)
+        if lib.rs2cpu_decode_primary(n, length, len(keep), idx, ptrs, out.ctypes.data) != 0:
+            raise ValueError("DecodingUnsuccessful")
+        return out[:length].tobytes()
+
+
+def _c_row_root(p: O.Rs2Params, row: bytes) -> bytes:
+    src = np.frombuffer(row, np.uint8)
+    root = np.zeros(32, np.uint8)
+    _cpu_lib().rs2cpu_sliver_root(p.n_shards, p.symbol_size, 0, src.ctypes.data, root.ctypes.data)
+    return root.tobytes()
+
+
+_C.row_root = staticmethod(_c_row_root)
+
+
+def sliver_root(p: O.Rs2Params, axis: str, sliver: bytes) -> bytes:
+    """SliverData::get_merkle_root of any sliver bytes of `axis` (the C restatement from
+    n = 100 on, as in the model)."""
+    src = np.frombuffer(bytes(sliver), np.uint8)
+    if p.n_shards < C_MODEL_FROM:
+        return O.sliver_merkle_root(src, axis, p)
+    root = np.zeros(32, np.uint8)
+    _cpu_lib().rs2cpu_sliver_root(p.n_shards, p.symbol_size, int(axis == SECONDARY),
+                                  src.ctypes.data, root.ctypes.data)
+    return root.tobytes()
+
+
+def sliver_positions(p: O.Rs2Params, axis: str):
+    """(byte of the sliver, mask) at the first, a middle and the last symbol x symbol_offsets,
+    the two masks alternating."""
+    nsym = p.n_secondary if axis == PRIMARY else p.n_primary
+    s = p.symbol_size
+    mask = _masks()
+    return [(sy * s + o, next(mask)) for sy in sorted({0, nsym // 2, nsym - 1})
+            for o in symbol_offsets(s)]
+
+
+def backend(n: int, name: Optional[str] = None):
+    if name is None:
+        name = "c" if n >= C_MODEL_FROM else "numpy"
+    return {"c": _C, "c_decode": _CDecode, "numpy": _Numpy}[name]
+
+
+# verdict pieces are pure functions of their bytes: shared by every case that reaches them
+_ROOTS: dict = {}
+_IDS: dict = {}
+
+
+def _row_root(be, p, row: bytes) -> bytes:
+    key = (be.__name__, p.n_shards, p.symbol_size, row)
+    if key not in _ROOTS:
+        _ROOTS[key] = be.row_root(p, row)
+    return _ROOTS[key]
+
+
+def _blob_id(be, blob: bytes, n: int) -> bytes:
+    key = (be.__name__, n, len(blob), hashlib.sha256(blob).digest())
+    if key not in _IDS:
+        _IDS[key] = be.blob_id(blob, n)
+    return _IDS[key]
+
+
+def model_verify(n, length, axis, slivers, hashes, blob_id, check, decoded: bytes, be=None):
+    """The verdict on `decoded` (the decode of `slivers`); see the module docstring."""
+    be = be or backend(n)
+    if check == "skip":
+        return ("ok", decoded)
+    if check == "strict":
+        return ("ok", decoded) if _blob_id(be, decoded, n) == bytes(blob_id) else ("rejected",)
+    assert check == "default", check
+    p = O.Rs2Params.for_blob(n, length)
+    verified = set()
+    if axis == PRIMARY:
+        taken = set()
+        for idx, _ in slivers:
+            if idx < p.n_primary:
+                verified.add(idx)           # pulled from the input
+            if len(taken) == p.n_primary:
+                break                       # ... this one found the workspace full
+            taken.add(idx)
+    rows = O.message_matrix(decoded, p).reshape(p.n_primary, -1)
+    for i in range(p.n_primary):
+        if i not in verified and _row_root(be, p, rows[i].tobytes()) != bytes(hashes[i][0]):
+            return ("rejected",)
+    return ("ok", decoded)
+
+
+def model_decode_and_verify(n, length, axis, slivers_in_order, hashes, blob_id, check, be=None):
+    """("ok", blob bytes) or ("rejected",) for decode_and_verify of (index, bytes) slivers of one
+    axis against per-pair (primary, secondary) hashes and a blob id."""
+    be = be or backend(n)
+    slivers = [(int(i), bytes(d)) for i, d in slivers_in_order]
+    decoded = be.decode(n, length, axis, slivers)
+    return model_verify(n, length, axis, slivers, hashes, blob_id, check, decoded, be)
+
+
+# ---------------------------------------------------------------------------------------------
+# scenarios: a geometry's blob and its honest encoding
+# ---------------------------------------------------------------------------------------------
+@dataclass
+class Scenario:
+    geo: Geometry
+    name: str
+    blob: bytes
+    params: O.Rs2Params
+    primary: np.ndarray     # (n, K_s * s) by sliver index
+    secondary: np.ndarray   # (n, K_p * s) by sliver index
+    hashes: list            # [(primary hash, secondary hash)] by pair index
+    blob_id: bytes
+
+    def sliver(self, axis: str, index: int) -> bytes:
+        return (self.primary if axis == PRIMARY else self.secondary)[index].tobytes()
+
+    def pair_of(self, axis: str, index: int) -> int:
+        return index if axis == PRIMARY else self.geo.n - 1 - index
+
+
+@functools.lru_cache(maxsize=None)
+def scenario(geo_id: str, name: str = "main") -> Scenario:
+    """"main": no zero byte anywhere, so every flip that reaches the blob changes it and a blob
+    cut short loses a non-zero byte; "ztail": the same blob with its last byte zero."""
+    g = GEOMETRIES[geo_id]
+    blob = bytearray(np.random.default_rng(g.n * 1000 + g.length).integers(
+        1, 256, g.length, dtype=np.uint8).tobytes())
+    if name == "ztail":
+        blob[-1] = 0
+    blob = bytes(blob)
+    p = O.Rs2Params.for_blob(g.n, g.length)
+    assert p.symbol_size == g.symbol_size, (g.id, p.symbol_size)
+    prim, sec, hashes, bid = backend(g.n).encode(blob, g.n)
+    return Scenario(g, name, blob, p, prim, sec, hashes, bid)
+
+
+# ---------------------------------------------------------------------------------------------
+# layouts: which slivers a call passes, in which order
+# ---------------------------------------------------------------------------------------------
+def _std_layout(n: int, k: int) -> Tuple[int, ...]:
+    """K used slivers, systematic (1, 2, ...) and repair (n-1, n-2, ...) alternating, the first
+    systematic and the last a repair; a second copy of the first one at position 2 (dropped as a
+    duplicate); systematic sliver 0 after the K-th (dropped as surplus, yet pulled)."""
+    nrep = min(n - k, (k + 1) // 2)
+    sys_, rep = list(range(1, k - nrep + 1)), list(range(n - 1, n - 1 - nrep, -1))
+    order = []
+    while sys_ or rep:
+        if sys_:
+            order.append(sys_.pop(0))
+        if rep:
+            order.append(rep.pop(0))
+    if order[-1] < k:
+        j = max(i for i, v in enumerate(order) if v >= k)
+        order.append(order.pop(j))
+    assert len(order) == k and len(set(order)) == k and 0 not in order
+    return tuple(order[:2] + [order[0]] + order[2:] + [0])
+
+
+def _end_cells(p: O.Rs2Params):
+    """[(row, column, first padding byte of the symbol)]: the message cell that holds the blob's
+    last byte (when it holds padding too, or else with s) and the wholly padded cell after it."""
+    s, ks, kp = p.symbol_size, p.n_secondary, p.n_primary
+    cells = []
+    nxt = 0
+    if p.blob_len:
+        cell = (p.blob_len - 1) // s
+        cells.append((cell // ks, cell % ks, p.blob_len - cell * s))
+        nxt = cell + 1
+    if nxt < kp * ks:
+        cells.append((nxt // ks, nxt % ks, 0))
+    return cells
+
+
+def layouts(geo_id: str) -> dict:
+    """name -> (axis, sliver indices in input order)."""
+    g = GEOMETRIES[geo_id]
+    p = O.Rs2Params.for_blob(g.n, g.length)
+    kp, ks, n = p.n_primary, p.n_secondary, p.n_shards
+    out = {"pri": (PRIMARY, _std_layout(n, kp)), "sec": (SECONDARY, _std_layout(n, ks))}
+    # every systematic sliver received (nothing is decoded) and one repair sliver as surplus:
+    # on the primary axis every row counts as verified
+    out["pri_sys"] = (PRIMARY, tuple(range(kp)) + (n - 1,))
+    out["sec_sys"] = (SECONDARY, tuple(range(ks)) + (n - 1,))
+    # padding-landing: exactly one systematic sliver erased, the one holding padding
+    for r, c, _ in _end_cells(p):
+        out.setdefault(f"pri_pad{r}", (PRIMARY, tuple(i for i in range(kp) if i != r) + (n - 1,)))
+        out.setdefault(f"sec_pad{c}", (SECONDARY, tuple(i for i in range(ks) if i != c) + (ks,)))
+    return out
+
+
+# ---------------------------------------------------------------------------------------------
+# cases
+# ---------------------------------------------------------------------------------------------
+@dataclass(frozen=True)
+class Case:
+    geo: str
+    scen: str
+    layout: str
+    check: str
+    family: str = "honest"
+    target: str = "-"
+    pos: int = -1                 # position in the input list of the sliver that is changed
+    byte: int = 0                 # byte of that sliver
+    mask: int = 0
+    hash_edit: Optional[Tuple[int, int, int, int]] = None   # (pair, 0 | 1, byte, mask)
+    id_edit: Optional[Tuple[int, int]] = None               # (byte, mask)
+    dlen: int = 0                 # unencoded_length passed = length + dlen
+
+    def honest(self) -> "Case":
+        return Case(self.geo, self.scen, self.layout, self.check)
+
+    def body(self) -> "Case":
+        """The case without its check (what the decode depends on)."""
+        return replace(self, check="")
+
+    def describe(self) -> str:
+        g = GEOMETRIES[self.geo]
+        axis, idx = layouts(self.geo)[self.layout]
+        what = f"{self.geo} (n={g.n}, L={g.length}, s={g.symbol_size}) {self.scen} {axis} " \
+               f"layout {self.layout} check={self.check} family={self.family} " \
+               f"target={self.target}"
+        if self.pos >= 0:
+            s = g.symbol_size
+            what += f" input[{self.pos}]=sliver {idx[self.pos]} byte {self.byte} " \
+                    f"(symbol {self.byte // s} offset {self.byte % s}) mask {self.mask:#04x}"
+        if self.hash_edit:
+            what += " hash (pair %d, %s) byte %d mask %#04x" % (
+                self.hash_edit[0], ("primary", "secondary")[self.hash_edit[1]],
+                self.hash_edit[2], self.hash_edit[3])
+        if self.id_edit:
+            what += " blob id byte %d mask %#04x" % self.id_edit
+        if self.dlen:
+            what += f" length {g.length + self.dlen}"
+        return what
+
+
+def symbol_offsets(s: int):
+    """Offsets in a symbol where the shard layout changes: 0, 1, the last lo byte and the first
+    hi byte of the tail chunk, s - 1, and around the first chunk's lo/hi split."""
+    q, t = divmod(s, 64)
+    offs = [0, 1, s - 1]
+    if t:
+        offs += [64 * q + t // 2 - 1, 64 * q + t // 2]
+    if s > 64:
+        offs += [31, 32, 63, 64]
+    return sorted({o for o in offs if 0 <= o < s})
+
+
+def _elem_bytes(s: int, e: int):
+    """Symbol offsets of the lo and hi byte of GF element e (rs2_oracle.bytes_to_elems)."""
+    q, t = divmod(s, 64)
+    if e < 32 * q:
+        return 64 * (e // 32) + e % 32, 64 * (e // 32) + 32 + e % 32
+    j = e - 32 * q
+    return 64 * q + j, 64 * q + t // 2 + j
+
+
+def _masks():
+    while True:
+        yield 0x01
+        yield 0x80
+
+
+def _base_cases(geo_id: str):
+    """Cases without a check, grouped by (scenario, layout)."""
+    g = GEOMETRIES[geo_id]
+    p = O.Rs2Params.for_blob(g.n, g.length)
+    kp, ks, s, n = p.n_primary, p.n_secondary, p.symbol_size, p.n_shards
+    lay = layouts(geo_id)
+    mask = _masks()
+    offs = symbol_offsets(s)
+    out = []
+    for name in ("pri", "sec"):
+        axis, idx = lay[name]
+        k, nsym = (kp, ks) if axis == PRIMARY else (ks, kp)
+        used = [i for i in range(len(idx)) if i != 2 and i != len(idx) - 1]
+        systematic = [i for i in used[1:-1] if idx[i] < k] or [used[0]]
+        repair = [i for i in used[1:-1] if idx[i] >= k] or [used[-1]]
+        targets = [("systematic", systematic[0]), ("repair", repair[0]), ("first", used[0]),
+                   ("last", used[-1]), ("surplus", len(idx) - 1), ("duplicate", 2)]
+        symbols = [0, nsym // 2, nsym - 1]
+        # ---- sliver bytes --------------------------------------------------------------------
+        for t, (tname, pos) in enumerate(targets):
+            if g.grid == "full":
+                grid = [(sy, o) for sy in sorted(set(symbols)) for o in offs]
+            elif g.grid == "cut":
+                # every second offset, the two halves alternating over the targets
+                grid = [(symbols[(t + j) % 3], o) for j, o in enumerate(offs[t % 2::2])]
+            else:
+                if tname in ("first", "last", "duplicate"):
+                    continue
+                grid = [(symbols[t % 3], offs[-1])]
+            for sy, o in grid:
+                out.append(Case(geo_id, "main", name, "", "sliver", tname, pos, sy * s + o,
+                                next(mask)))
+        # ---- a systematic sliver where all of them were received ------------------------------
+        pos = k // 2
+        if g.grid == "full":
+            grid = [(sy, o) for sy in sorted(set(symbols)) for o in offs]
+        elif g.grid == "cut":
+            grid = [(symbols[j % 3], o) for j, o in enumerate(offs)]
+        else:
+            grid = [(symbols[1], offs[0])]
+        for sy, o in grid:
+            out.append(Case(geo_id, "main", name + "_sys", "", "sliver", "all systematic", pos,
+                            sy * s + o, next(mask)))
+        # ---- metadata ------------------------------------------------------------------------
+        unverified = max(i for i in range(kp) if axis == SECONDARY or i not in idx)
+        edits = [("hash verified row", (idx[0] if idx[0] < kp else 1, 0)),
+                 ("hash surplus row", (0, 0)),
+                 ("hash unverified row", (unverified, 0)),
+                 ("hash repair pair", (kp, 0)),
+                 ("hash secondary", (2, 1))]
+        for b in ((0,) if g.grid == "few" else (0, 31)):
+            for tname, (pair, which) in edits:
+                out.append(Case(geo_id, "main", name, "", "metadata", tname,
+                                hash_edit=(pair, which, b, next(mask))))
+            out.append(Case(geo_id, "main", name, "", "metadata", "blob id",
+                            id_edit=(b, next(mask))))
+        if g.length and O.compute_symbol_size(g.length - 1, kp * ks) == s:
+            out.append(Case(geo_id, "main", name, "", "metadata", "length - 1", dlen=-1))
+    if g.length and O.compute_symbol_size(g.length - 1, kp * ks) == s:
+        for name in ("pri", "sec"):
+            out.append(Case(geo_id, "ztail", name, "", "metadata", "length - 1, zero last byte",
+                            dlen=-1))
+    # ---- padding-landing: flips of the one repair sliver (last in the layout) -----------------
+    for r, c, pad_from in _end_cells(p):
+        bytes_ = {0, s - 1} if pad_from == 0 else {pad_from - 1, min(pad_from, s - 1), s - 1}
+        for e in range(s // 2):          # the first element that lies wholly in the padding
+            lo, hi = _elem_bytes(s, e)
+            if lo >= pad_from and hi >= pad_from:
+                bytes_ |= {lo, hi}
+                break
+        for name, sym, k in ((f"pri_pad{r}", c, kp), (f"sec_pad{c}", r, ks)):
+            for b in sorted(bytes_):
+                out.append(Case(geo_id, "main", name, "", "padding", f"cell ({r}, {c})", k - 1,
+                                sym * s + b, next(mask)))
+    # a flip that lands in valid data of the erased sliver, per padding layout
+    for name in lay:
+        if "_pad" in name and p.blob_len:
+            axis, idx = lay[name]
+            out.append(Case(geo_id, "main", name, "", "padding", "valid data", len(idx) - 1, 0,
+                            next(mask)))
+    out.sort(key=lambda c: (c.scen, c.layout))   # stable: one (scenario, layout) after another
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def cases(geo_id: str) -> tuple:
+    """Every case of the geometry under every check, one (scenario, layout) after another, the
+    three checks of one corruption in a row."""
+    return tuple(replace(c, check=chk) for c in _base_cases(geo_id) for chk in CHECKS)
+
+
+def groups(case_list):
+    """[((scenario name, layout name), [cases])] in order."""
+    return [(k, list(v)) for k, v in groupby(case_list, key=lambda c: (c.scen, c.layout))]
+
+
+def materialise(case: Case) -> dict:
+    """What the call passes: length, axis, slivers [(index, bytes)], hashes [(p, s)], blob_id."""
+    sc = scenario(case.geo, case.scen)
+    axis, idx = layouts(case.geo)[case.layout]
+    slivers = [(i, sc.sliver(axis, i)) for i in idx]
+    if case.pos >= 0:
+        d = bytearray(slivers[case.pos][1])
+        d[case.byte] ^= case.mask
+        slivers[case.pos] = (slivers[case.pos][0], bytes(d))
+    hashes = list(sc.hashes)
+    if case.hash_edit:
+        pair, which, b, m = case.hash_edit
+        h = [bytearray(x) for x in hashes[pair]]
+        h[which][b] ^= m
+        hashes[pair] = (bytes(h[0]), bytes(h[1]))
+    bid = bytearray(sc.blob_id)
+    if case.id_edit:
+        bid[case.id_edit[0]] ^= case.id_edit[1]
+    return dict(n=sc.geo.n, length=sc.geo.length + case.dlen, axis=axis, slivers=slivers,
+                hashes=hashes, blob_id=bytes(bid), check=case.check)
+
+
+_DECODED: dict = {}
+
+
+def expected(case: Case):
+    """The model's answer for the case (decodes shared between the three checks)."""
+    m = materialise(case)
+    be = backend(m["n"])
+    key = replace(case.body(), hash_edit=None, id_edit=None, family="", target="")
+    if key not in _DECODED:
+        _DECODED[key] = be.decode(m["n"], m["length"], m["axis"], m["slivers"])
+    return model_verify(m["n"], m["length"], m["axis"], m["slivers"], m["hashes"], m["blob_id"],
+                        m["check"], _DECODED[key], be)
+
+
+def model_call(case: Case):
+    """The model run as the engine: nothing shared with `expected` but the code."""
+    m = materialise(case)
+    return model_decode_and_verify(m["n"], m["length"], m["axis"], m["slivers"], m["hashes"],
+                                   m["blob_id"], m["check"])
+
+
+# ---------------------------------------------------------------------------------------------
+# the shared test body
+# ---------------------------------------------------------------------------------------------
+def run_sequence(call, case_list, honest_every: int = 4) -> dict:
+    """call(case) -> ("ok", bytes) | ("rejected",), compared with the model for every case:
+    bytes exactly on ok, the verdict alone on reject.  An honest call (same layout and check, no
+    corruption) goes before the first case, after the last and after every `honest_every` cases
+    and must return the blob.  Returns {"ok": accepted, "rejected": rejected, "honest": calls}."""
+    case_list = list(case_list)
+    counts = {"ok": 0, "rejected": 0, "honest": 0}
+
+    def honest(near: Case, where: str):
+        h = near.honest()
+        got = call(h)
+        counts["honest"] += 1
+        if tuple(got) != ("ok", scenario(h.geo, h.scen).blob):
+            raise AssertionError(f"honest call {where} did not return the blob "
+                                 f"(got {got[0]}): {h.describe()} -- {where}: {near.describe()}")
+
+    if not case_list:
+        return counts
+    honest(case_list[0], "before the first case")
+    for i, c in enumerate(case_list):
+        want = expected(c)
+        got = tuple(call(c))
+        if got[0] != want[0]:
+            raise AssertionError(f"verdict {got[0]}, the model says {want[0]}: {c.describe()}")
+        if want[0] == "ok" and got[1] != want[1]:
+            diff = next((j for j, (a, b) in enumerate(zip(got[1], want[1])) if a != b),
+                        min(len(got[1]), len(want[1])))
+            raise AssertionError(f"accepted with other bytes than the model's (first difference "
+                                 f"at byte {diff}, {len(got[1])} vs {len(want[1])} bytes): "
+                                 f"{c.describe()}")
+        counts[want[0]] += 1
+        if (i + 1) % honest_every == 0:
+            honest(c, "after")
+    honest(case_list[-1], "after the last case")
+    return counts
