@@ -1,7 +1,7 @@
 """Structured erasure patterns for the decode tests -- TEST ONLY (a plain module, no fixtures).
 
 The decode is the one path whose host plan and kernel control flow depend on WHICH shards are
-present (rs2_engine.cpp plan_decode): the input and output blocks, each block's fill (`count`,
+present (rs2_planner.cpp plan_decode): the input and output blocks, each block's fill (`count`,
 `trunc`, hence its active waves), the mixing kinds, the fused or separate copy of the present
 originals and the P/Q block pairing all follow from the pattern.  A random k-subset at n = 1000
 erases originals in every block and fills every input block to its end, so it reaches one corner

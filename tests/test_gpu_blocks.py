@@ -1,5 +1,5 @@
 """Block decomposition parity: transforms split into smaller on-chip blocks (block-level mixing
-of the top butterfly layers, rs2_engine.cpp sym_ifft_top / sym_fft_top / mixing_matrices) must
+of the top butterfly layers, rs2_planner.cpp sym_ifft_top / sym_fft_top / mixing_matrices) must
 give byte-identical slivers, metadata and decodes for every block limit."""
 import numpy as np
 import pytest

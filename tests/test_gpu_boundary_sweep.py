@@ -1,7 +1,7 @@
 """Shard counts at the codes' power-of-two edges, against the C restatement.
 
 reed-solomon-simd sizes a code's transforms by powers of two of K and R = n - K
-(basic_encoding.rs:335-337; the engine's chunk and block plan, rs2_engine.cpp plan_encode /
+(basic_encoding.rs:335-337; the engine's chunk and block plan, rs2_planner.h plan_encode /
 plan_decode), so the shard counts at which K_p = n - 2f or K_s = n - f crosses 2^k change the
 number of input / output chunks, the last chunk's fill and which rate path a code takes.  This
 sweep runs the n on both sides of K_p in {256, 512, 1024, 2048} and K_s in {512, 1024, 2048,

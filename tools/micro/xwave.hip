@@ -391,7 +391,7 @@ int main() {
     for (int r = 0; r < 16; ++r) y |= uint32_t(parity(G[slot * 16 + r] & x)) << r;
     return y;
   };
-  // tables (rs2_engine.cpp nib_table layout): bits 0-5, 6-10, 11-15
+  // tables (rs2_planner.cpp nib_table layout): bits 0-5, 6-10, 11-15
   std::vector<uint16_t> tabs(62 * 128);
   for (int t = 0; t < 62; ++t) {
     for (int j = 0; j < 64; ++j) tabs[t * 128 + j] = uint16_t(apply(t, uint32_t(j)));

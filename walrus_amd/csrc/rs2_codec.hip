@@ -470,7 +470,7 @@ __device__ __forceinline__ void fence_regs(uint32_t (&X)[N]) {
 }
 
 // In-wave layers d = 1 .. PPW/2 (A layout).  Table slot of group g at half-distance d:
-// PPW - PPW/d + g  (sd_stream order in rs2_engine.cpp).
+// PPW - PPW/d + g  (sd_stream order in rs2_planner.cpp).
 // kStaged: the wave's layer tables are still arriving by LDS-DMA, 1 KiB chunks issued in slot
 // order for the IFFT (whose first layer, d = 1, reads slots 0 .. PPW/2-1) and in reverse order
 // for the FFT (whose first layer reads the last slot); each layer waits only for the chunks

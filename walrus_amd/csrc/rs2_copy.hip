@@ -190,7 +190,7 @@ __global__ void __launch_bounds__(256)
   }
 }
 
-// Per-position multiplier tables (rs2_engine.cpp nib_table layout): out[i][e] = x(e) * exp(logs[i])
+// Per-position multiplier tables (rs2_planner.cpp nib_table layout): out[i][e] = x(e) * exp(logs[i])
 // with x(e) = e (e < 64), (e - 64) << 6 (e < 96), (e - 96) << 11  (log 65535 == 0).
 __global__ void __launch_bounds__(256)
     build_mul_tables_kernel(const uint16_t* __restrict__ exp_t, const uint16_t* __restrict__ log_t,

@@ -1,5 +1,5 @@
 // Device-side job descriptors shared by the HIP kernels (rs2_codec.hip, rs2_hash.hip,
-// rs2_copy.hip) and the host planner (rs2_engine.cpp).  Plain structs, no HIP types, so both
+// rs2_copy.hip) and the host planner (rs2_planner.cpp).  Plain structs, no HIP types, so both
 // sides agree on layout.
 #pragma once
 #include <stdint.h>
@@ -13,7 +13,7 @@ constexpr int kMaxBlocks = 64;  // input / output blocks of a job passed by valu
 constexpr int kMaxBlocksBig = 128;
 constexpr int kMaxC = 512;      // largest transform block held on chip (positions)
 constexpr int kTabU16 = 128;    // one multiplier table: u16 sub-tables of 64 + 32 + 32 entries
-                                // for operand bits 0-5, 6-10, 11-15 (rs2_engine.cpp nib_table)
+                                // for operand bits 0-5, 6-10, 11-15 (rs2_planner.cpp nib_table)
 // Codeword positions one wave holds in VGPRs; a size-C transform uses C / PPW waves.  The
 // kernel's table consumption order and the host's sd_stream order both derive from it.
 constexpr int kPpwTarget = 32;

@@ -1,12 +1,11 @@
-// Host side of the MI355X Red Stuff engine: GF(2^16) constant tables, codec job planning,
-// blob plans and the C ABI declared in include/walrus_rs2.h.
+// Host side of the MI355X Red Stuff engine: the device runtime, the launch of planned codec
+// jobs, blob plans and the C ABI declared in include/walrus_rs2.h.  The GF(2^16) constant tables
+// and the codec job planner are rs2_planner.cpp, which touches no device.
 //
 // Reference semantics (paths relative to the reference checkout):
 //   encoding/blob_encoding.rs:277-368  encode_with_metadata    -> rs2_encode_device_async
 //   encoding/blob_encoding.rs:888-993  BlobDecoder::decode      -> rs2_decode_device_async
 //   encoding/basic_encoding.rs:107-429 ReedSolomonEncoder/Decoder -> rs2_encode_1d / rs2_decode_1d
-//   reed-solomon-simd 3.1.0 (Cargo.lock:8813): GF tables, skew, rates -- restated in
-//   oracle/rs2_oracle.py, mirrored here.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -31,32 +30,16 @@
 #include "../../include/walrus_rs2.h"
 #include "rs2_device.h"
 #include "rs2_kernels.h"
+#include "rs2_planner.h"
 
 namespace rs2 {
 namespace {
-
-// ---------------------------------------------------------------------------------------------
-// errors
-// ---------------------------------------------------------------------------------------------
-thread_local std::string g_last_error = "ok";
-
-int fail(int code, const std::string& msg) {
-  g_last_error = msg;
-  return code;
-}
 
 #define HIP_TRY(expr)                                                                  \
   do {                                                                                 \
     hipError_t e_ = (expr);                                                            \
     if (e_ != hipSuccess)                                                              \
       return fail(RS2_E_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_));    \
-  } while (0)
-
-// Return the first failing status of a chain of engine calls.
-#define RS2_TRY(expr)                   \
-  do {                                  \
-    int rc_ = (expr);                   \
-    if (rc_ != RS2_OK) return rc_;      \
   } while (0)
 
 // Diagnostic: RS2_HOST_TRACE=<path> appends one "name ms" line per host-timed section (the
@@ -71,139 +54,6 @@ void host_trace(const char* name, double ms) {
   std::lock_guard<std::mutex> lk(mu);
   std::fprintf(f, "%s %.4f\n", name, ms);
   std::fflush(f);
-}
-
-// An integer A/B knob from the environment (`dflt` when unset).  Callers keep the value in a
-// function-local static, so every knob is read once per process.
-int env_int(const char* name, int dflt) {
-  const char* e = std::getenv(name);
-  return e ? std::atoi(e) : dflt;
-}
-
-// ---------------------------------------------------------------------------------------------
-// GF(2^16) tables (reed-solomon-simd engine/tables.rs restated; see oracle/rs2_oracle.py)
-// ---------------------------------------------------------------------------------------------
-constexpr uint32_t kOrder = 65536, kModulus = 65535, kPoly = 0x1002D;
-constexpr uint16_t kCantor[16] = {0x0001, 0xACCA, 0x3C0E, 0x163E, 0xC582, 0xED2E, 0x914C, 0x4012,
-                                  0x6C98, 0x10D8, 0x6A72, 0xB900, 0xFDB8, 0xFB34, 0xFF38, 0x991E};
-
-struct Gf {
-  std::vector<uint16_t> exp, log, skew;
-  Gf() : exp(kOrder), log(kOrder), skew(kModulus) {
-    std::vector<uint32_t> e(kOrder), l(kOrder);
-    uint32_t state = 1;
-    for (uint32_t i = 0; i < kModulus; ++i) {
-      e[state] = i;
-      state <<= 1;
-      if (state >= kOrder) state ^= kPoly;
-    }
-    e[0] = kModulus;
-    l[0] = 0;
-    for (int i = 0; i < 16; ++i) {
-      const uint32_t width = 1u << i;
-      for (uint32_t j = 0; j < width; ++j) l[j + width] = l[j] ^ kCantor[i];
-    }
-    for (uint32_t i = 0; i < kOrder; ++i) l[i] = e[l[i]];
-    for (uint32_t i = 0; i < kOrder; ++i) e[l[i]] = i;
-    e[kModulus] = e[0];
-    for (uint32_t i = 0; i < kOrder; ++i) {
-      exp[i] = uint16_t(e[i]);
-      log[i] = uint16_t(l[i]);
-    }
-    // skew LUT
-    std::vector<uint32_t> sk(kModulus, 0);
-    uint32_t temp[15];
-    for (int i = 1; i < 16; ++i) temp[i - 1] = 1u << i;
-    for (int m = 0; m < 15; ++m) {
-      const uint32_t step = 1u << (m + 1);
-      sk[(1u << m) - 1] = 0;
-      for (int i = m; i < 15; ++i) {
-        const uint32_t s = 1u << (i + 1);
-        for (uint32_t j = (1u << m) - 1; j < s; j += step) sk[j + s] = sk[j] ^ temp[i];
-      }
-      temp[m] = kModulus - log[mul(temp[m], log[temp[m] ^ 1])];
-      for (int i = m + 1; i < 15; ++i) temp[i] = mul(temp[i], add_mod(log[temp[i] ^ 1], temp[m]));
-    }
-    for (uint32_t i = 0; i < kModulus; ++i) skew[i] = log[sk[i]];
-  }
-  static uint32_t add_mod(uint32_t a, uint32_t b) {
-    const uint32_t s = a + b;
-    return (s + (s >> 16)) & 0xFFFFu;
-  }
-  // x * exp(log_m) with the generic semantics (log_m == 65535 is log 0, i.e. times one)
-  uint32_t mul(uint32_t x, uint32_t log_m) const {
-    return x == 0 ? 0 : exp[add_mod(log[x], log_m)];
-  }
-};
-
-const Gf& gf() {
-  static const Gf g;
-  return g;
-}
-
-// 256-byte multiplier table of exp(log_m), one sub-table per bit field of the operand
-// (rs2_device.h kTabU16): out[f] = f * m (bits 0-5, 64 entries), out[64 + f] = (f << 6) * m
-// (bits 6-10), out[96 + f] = (f << 11) * m (bits 11-15).  Multiplication by a constant is
-// GF(2)-linear, so x * m is the XOR of the three entries its fields select.  Each sub-table
-// spans at most 32 dwords, so a wave's lookups into it never bank-conflict.
-// fft_zero: a butterfly constant log_m == 65535 means multiply by ZERO (engine special case).
-void nib_table(uint32_t log_m, bool fft_zero, uint16_t* out) {
-  const Gf& g = gf();
-  const bool zero = fft_zero && log_m == kModulus;
-  for (uint32_t e = 0; e < uint32_t(kTabU16); ++e) {
-    const uint32_t x = e < 64 ? e : (e < 96 ? (e - 64) << 6 : (e - 96) << 11);
-    out[e] = zero ? 0 : uint16_t(g.mul(x, log_m));
-  }
-}
-
-// Constant tables of a size-C transform with skew offset sd, in kernel consumption order
-// (rs2_codec.hip: A slots PPW - PPW/d + g per wave, then B slots NW - C/d + g).
-std::vector<uint16_t> sd_stream(int C, int sd, int ppw = kPpwTarget) {
-  const Gf& g = gf();
-  const int NW = C >= ppw ? C / ppw : 1, PPW = C / NW;
-  std::vector<uint16_t> out;
-  out.reserve(size_t(std::max(C - 1, 0)) * kTabU16);
-  uint16_t t[kTabU16];
-  for (int w = 0; w < NW; ++w)
-    for (int d = 1; d < PPW; d *= 2)
-      for (int gi = 0; gi < PPW / (2 * d); ++gi) {
-        const int r = w * PPW + 2 * d * gi;
-        nib_table(g.skew[r + d + sd - 1], true, t);
-        out.insert(out.end(), t, t + kTabU16);
-      }
-  for (int d = PPW; d < C; d *= 2)
-    for (int gi = 0; gi < C / (2 * d); ++gi) {
-      const int r = 2 * d * gi;
-      nib_table(g.skew[r + d + sd - 1], true, t);
-      out.insert(out.end(), t, t + kTabU16);
-    }
-  return out;
-}
-
-// 1 when group 0 of every cross-wave layer of a size-C transform with skew offset sd multiplies
-// by zero (skew[d + sd - 1] is log 0, which holds for sd = 0): the kernel then skips those
-// multiplies (rs2_codec.hip phase_b).
-int group0_zero(int C, int sd, int ppw = kPpwTarget) {
-  const Gf& g = gf();
-  const int NW = C >= ppw ? C / ppw : 1, PPW = C / NW;
-  if (NW == 1) return 0;
-  for (int d = PPW; d < C; d *= 2)
-    if (g.skew[d + sd - 1] != kModulus) return 0;
-  return 1;
-}
-
-uint32_t next_pow2(uint32_t x) {
-  uint32_t p = 1;
-  while (p < x) p <<= 1;
-  return p;
-}
-
-// reed-solomon-simd DefaultRate: high rate iff pow2(recovery) <= pow2(original)
-bool use_high_rate(uint32_t k, uint32_t r) { return next_pow2(r) <= next_pow2(k); }
-
-bool rate_supported(uint32_t k, uint32_t r) {
-  if (k == 0 || r == 0 || k >= kOrder || r >= kOrder) return false;
-  return std::min(next_pow2(k), next_pow2(r)) + std::max(k, r) <= kOrder;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1010,37 +860,12 @@ hipError_t launch_codec_c(int C, const CodecJobBig& job_big, int n_lines, int n_
   return stamp_dump(C, mode, grid_tiles, n_z, job.stamps, st);
 }
 
-// ---------------------------------------------------------------------------------------------
-// codec job planning
-// ---------------------------------------------------------------------------------------------
-// A planned job: the CodecJob plus host copies of its per-position offset arrays.  Pointer
-// fields that reference per-job device arrays are filled by bind() once those are uploaded.
-struct PlannedJob {
-  CodecJobBig job{};                 // narrowed to CodecJob at launch when it has <= 64 blocks
-  int mix_stride = kMaxBlocks;       // mixing-table row length (kMaxBlocksBig for big jobs)
-  int C = 1;
-  int n_z = 1;
-  int mode = kModeRows;              // kernel variant (rs2_device.h CodecMode)
-  int ppw = kPpwTarget;              // positions per wave of the variant's table stream
-  std::vector<int64_t> offs;         // (n_in + n_out) blocks x C
-  std::vector<int64_t> copy_offs;    // n_in blocks x C fused copy-out offsets, or empty
-  uint8_t* copy_base = nullptr;
-  int64_t copy_ls = 0, copy_limit = INT64_MAX;
-  std::vector<uint16_t> pre_logs;    // per in-block C logs (decode), empty if none
-  std::vector<uint16_t> post_logs;   // per out-block C logs (decode)
-  std::vector<uint16_t> mix;         // mix_stride^2 * 2 tables (block mixing tables)
-  std::vector<uint16_t> logs;        // pre ++ post logs as uploaded (kept alive for async H2D)
-  std::vector<int> in_sd, out_sd;    // skew offset of each block's in-block transform
-  std::vector<uint32_t> in_first;    // code position (source index) of each in-block's slot 0
-  bool has_pre = false, has_post = false, has_mix = false;
-
-  size_t in_off(int b) const { return size_t(b) * C; }
-  size_t out_off(int o) const { return size_t(job.n_in + o) * C; }
-  // lines are folded into grid.x with the element pairs (CodecJob::pairs_span)
-  hipError_t launch(int n_lines, hipStream_t st, uint32_t* tile_ctr = nullptr) const {
-    return launch_codec_c(C, job, n_lines, n_z, mode, st, 1, 0, 0, 0, tile_ctr);
-  }
-};
+// A planned job over n_lines lines of one blob (the lines are folded into grid.x with the element
+// pairs, CodecJob::pairs_span).
+hipError_t launch_job(const PlannedJob& pj, int n_lines, hipStream_t st,
+                      uint32_t* tile_ctr = nullptr) {
+  return launch_codec_c(pj.C, pj.job, n_lines, pj.n_z, pj.mode, st, 1, 0, 0, 0, tile_ctr);
+}
 
 // Device memory holding a planned job's arrays.
 struct JobMem {
@@ -1103,239 +928,10 @@ struct Dec1DLease {
   }
 };
 
-int plan_fail_unsupported(const std::string& what) { return fail(RS2_E_UNSUPPORTED, what); }
-
-// Largest transform block held on chip.  RS2_BLOCK_MAX (a power of two <= kMaxC) lowers it for
-// experiments: smaller blocks mean smaller workgroups (C/32 waves) and more of them per CU, at
-// the price of more block-level mixing.
-std::atomic<uint32_t> g_block_max{0};
-uint32_t block_max() {
-  uint32_t v = g_block_max.load(std::memory_order_relaxed);
-  if (v) return v;
-  uint32_t x = uint32_t(env_int("RS2_BLOCK_MAX", kMaxC));
-  if (x < 1 || x > uint32_t(kMaxC) || (x & (x - 1))) x = uint32_t(kMaxC);
-  g_block_max.store(x, std::memory_order_relaxed);
-  return x;
-}
-
-// Blocks a job of block size C may have: jobs beyond kMaxBlocks run from device memory
-// (CodecJobBig), for which only C = 512 kernels are built.
-int max_blocks(int C) { return C == kMaxC ? kMaxBlocksBig : kMaxBlocks; }
-
-// Symbolic block-level transform layers.  A "slot" is one block of C positions; its value is a
-// linear combination (GF(2^16) coefficients) of the jobs' input blocks after their in-block
-// IFFTs.  Layers whose butterfly distance is >= C have one constant per block pair, so on whole
-// blocks they are scalar operations (same constants as the element-level transforms).
-using Coef = std::vector<uint32_t>;
-
-void coef_xor(Coef& y, const Coef& x) {
-  for (size_t i = 0; i < y.size(); ++i) y[i] ^= x[i];
-}
-void coef_mul_xor(Coef& y, const Coef& x, uint32_t log_c) {
-  const Gf& g = gf();
-  for (size_t i = 0; i < y.size(); ++i) y[i] ^= g.mul(x[i], log_c);
-}
-// IFFT layers d = C .. span/2 of a size-`span` transform with skew offset sd
-void sym_ifft_top(std::vector<Coef>& V, uint32_t C, uint32_t span, uint32_t sd) {
-  const Gf& g = gf();
-  for (uint32_t d = C; d < span; d *= 2)
-    for (uint32_t r = 0; r < span; r += 2 * d) {
-      const uint32_t c = g.skew[r + d + sd - 1];
-      for (uint32_t j = 0; j < d / C; ++j) {
-        const uint32_t x = r / C + j, y = x + d / C;
-        coef_xor(V[y], V[x]);
-        if (c != kModulus) coef_mul_xor(V[x], V[y], c);
-      }
-    }
-}
-// FFT layers d = span/2 .. C of a size-`span` transform with skew offset sd
-void sym_fft_top(std::vector<Coef>& V, uint32_t C, uint32_t span, uint32_t sd) {
-  const Gf& g = gf();
-  for (uint32_t d = span / 2; d >= C && d > 0; d /= 2) {
-    for (uint32_t r = 0; r < span; r += 2 * d) {
-      const uint32_t c = g.skew[r + d + sd - 1];
-      for (uint32_t j = 0; j < d / C; ++j) {
-        const uint32_t x = r / C + j, y = x + d / C;
-        if (c != kModulus) coef_mul_xor(V[x], V[y], c);
-        coef_xor(V[y], V[x]);
-      }
-    }
-    if (d == C) break;
-  }
-}
-
-// Mixing kinds and tables of output block oi from its coefficient vectors (M1 may be empty).
-void set_mixing(PlannedJob& pj, int oi, const Coef* m1, const Coef& m2) {
-  const Gf& g = gf();
-  CodecJobBig& j = pj.job;
-  const size_t ms = size_t(pj.mix_stride);
-  if (pj.mix.empty()) pj.mix.assign(ms * ms * 2 * kTabU16, 0);
-  for (int bi = 0; bi < j.n_in; ++bi) {
-    const uint32_t c1 = m1 ? (*m1)[bi] : 0u, c2 = m2[bi];
-    j.m1_kind[oi][bi] = uint8_t(c1 == 0 ? 0 : (c1 == 1 ? 1 : 2));
-    j.m2_kind[oi][bi] = uint8_t(c2 == 0 ? 0 : (c2 == 1 ? 1 : 2));
-    uint16_t* t = pj.mix.data() + (size_t(oi) * ms + bi) * 2 * kTabU16;
-    if (c1 > 1) {
-      nib_table(g.log[c1], false, t);
-      pj.has_mix = true;
-    }
-    if (c2 > 1) {
-      nib_table(g.log[c2], false, t + kTabU16);
-      pj.has_mix = true;
-    }
-  }
-}
-
-// Encode K source symbols into R recovery symbols for every line (reed-solomon-simd encoders,
-// oracle rs_encode_elems).  src(i) / dst(j): byte offsets relative to the base (before the line
-// stride).  Transforms larger than the block size C are split into blocks of C with the
-// top layers applied as block mixing.
-template <class SrcF, class DstF>
-int plan_encode(uint32_t K, uint32_t R, int symbol_size, const uint8_t* src_base,
-                int64_t src_ls, SrcF src, uint8_t* dst_base, int64_t dst_ls, DstF dst,
-                int64_t dst_limit, PlannedJob& pj) {
-  if (!rate_supported(K, R)) return fail(RS2_E_INCOMPATIBLE_PARAMETERS, "unsupported shard count");
-  CodecJobBig& j = pj.job;
-  j = CodecJobBig{};
-  pj.mix.clear();
-  pj.has_mix = false;
-  pj.in_sd.clear();
-  pj.out_sd.clear();
-  pj.in_first.clear();
-  j.symbol_size = symbol_size;
-  j.n_pairs = (symbol_size + 3) / 4;
-  const bool high = use_high_rate(K, R);
-  const uint32_t cs = high ? next_pow2(R) : next_pow2(K);
-  const uint32_t C = std::min(cs, block_max());
-  const uint32_t nb = cs / C;
-  pj.C = int(C);
-  // input blocks
-  struct Blk { uint32_t first, count; int sd; };
-  std::vector<Blk> in, out;
-  if (high) {
-    for (uint32_t k = 0; k * cs < K; ++k)
-      for (uint32_t b = 0; b < nb && k * cs + b * C < K; ++b)
-        in.push_back({k * cs + b * C, std::min(C, K - k * cs - b * C), int((k + 1) * cs + b * C)});
-  } else {
-    for (uint32_t b = 0; b < nb && b * C < K; ++b)
-      in.push_back({b * C, std::min(C, K - b * C), int(b * C)});
-  }
-  if (in.size() > size_t(max_blocks(C))) return plan_fail_unsupported("too many input blocks");
-  j.n_in = int(in.size());
-  // block mixing: coefficient vectors of each output block's pre-FFT slot
-  std::vector<Coef> outs;
-  const size_t ni = in.size();
-  if (high) {
-    std::vector<Coef> acc(nb, Coef(ni, 0));
-    size_t bi = 0;
-    for (uint32_t k = 0; k * cs < K; ++k) {
-      std::vector<Coef> V(nb, Coef(ni, 0));
-      for (uint32_t b = 0; b < nb && k * cs + b * C < K; ++b) V[b][bi++] = 1;
-      sym_ifft_top(V, C, cs, (k + 1) * cs);
-      for (uint32_t b = 0; b < nb; ++b) coef_xor(acc[b], V[b]);
-    }
-    sym_fft_top(acc, C, cs, 0);
-    for (uint32_t b = 0; b < nb && b * C < R; ++b) {
-      out.push_back({b * C, std::min(C, R - b * C), int(b * C)});
-      outs.push_back(acc[b]);
-    }
-  } else {
-    std::vector<Coef> V(nb, Coef(ni, 0));
-    for (size_t bi = 0; bi < ni; ++bi) V[bi][bi] = 1;
-    sym_ifft_top(V, C, cs, 0);
-    for (uint32_t k = 0; k * cs < R; ++k) {
-      std::vector<Coef> Wk = V;
-      sym_fft_top(Wk, C, cs, (k + 1) * cs);
-      for (uint32_t b = 0; b < nb && k * cs + b * C < R; ++b) {
-        out.push_back({k * cs + b * C, std::min(C, R - k * cs - b * C), int((k + 1) * cs + b * C)});
-        outs.push_back(Wk[b]);
-      }
-    }
-  }
-  if (out.size() > size_t(max_blocks(C))) return plan_fail_unsupported("too many output blocks");
-  j.n_out = int(out.size());
-  pj.mix_stride = std::max(in.size(), out.size()) > size_t(kMaxBlocks) ? kMaxBlocksBig : kMaxBlocks;
-  // one shared IFFT when a single input block feeds every output unmixed (low rate, C == cs)
-  j.shared_in = (!high && nb == 1) ? 1 : 0;
-  pj.n_z = j.shared_in ? 1 : j.n_out;
-  pj.mode = j.shared_in ? kModeCols : kModeRows;
-  pj.ppw = kPpwTarget;
-  pj.copy_offs.clear();
-  pj.offs.assign(size_t(j.n_in + j.n_out) * C, -1);
-  for (int bi = 0; bi < j.n_in; ++bi) {
-    InBlock& ib = j.in[bi];
-    ib.base = src_base;
-    ib.line_stride = src_ls;
-    ib.count = int(in[bi].count);
-    for (uint32_t p = 0; p < in[bi].count; ++p) pj.offs[pj.in_off(bi) + p] = src(in[bi].first + p);
-    pj.in_sd.push_back(in[bi].sd);
-    pj.in_first.push_back(in[bi].first);
-  }
-  for (int oi = 0; oi < j.n_out; ++oi) {
-    OutBlock& ob = j.out[oi];
-    ob.base = dst_base;
-    ob.line_stride = dst_ls;
-    ob.trunc = int(out[oi].count);
-    ob.limit = dst_limit;
-    for (uint32_t p = 0; p < out[oi].count; ++p) pj.offs[pj.out_off(oi) + p] = dst(out[oi].first + p);
-    pj.out_sd.push_back(out[oi].sd);
-    if (!j.shared_in) set_mixing(pj, oi, nullptr, outs[oi]);
-  }
-  return RS2_OK;
-}
-
-// Fused copy-out of a job's loaded source symbols: source index q (a loaded position) is
-// also written to base + line*ls + f(q) (f(q) < 0: not copied).  Needs whole-dword symbol
-// I/O (s >= 4); the caller keeps a separate copy pass otherwise.
-template <class F>
-void set_copy(PlannedJob& pj, uint8_t* base, int64_t ls, int64_t limit, F f) {
-  pj.copy_base = base;
-  pj.copy_ls = ls;
-  pj.copy_limit = limit;
-  pj.copy_offs.assign(size_t(pj.job.n_in) * pj.C, -1);
-  for (int b = 0; b < pj.job.n_in; ++b)
-    for (int p = 0; p < pj.job.in[b].count; ++p)
-      pj.copy_offs[size_t(b) * pj.C + p] = f(pj.in_first[b] + uint32_t(p));
-}
-
-// True when every in-block that carries copy positions is loaded by at least one output
-// block (the kernel skips in-blocks whose mixing coefficients are all zero); otherwise the
-// copy is dropped and the caller falls back to a separate copy pass.
-bool copy_covered(PlannedJob& pj) {
-  if (pj.copy_offs.empty()) return false;
-  if (pj.mode == kModeRows) {  // the mixed-encode kernel has no copy-out (register budget)
-    pj.copy_offs.clear();
-    return false;
-  }
-  const CodecJobBig& j = pj.job;
-  for (int b = 0; b < j.n_in; ++b) {
-    bool any_copy = false;
-    for (int p = 0; p < pj.C; ++p) any_copy |= pj.copy_offs[size_t(b) * pj.C + p] >= 0;
-    if (!any_copy || j.shared_in) continue;
-    bool loaded = false;
-    for (int o = 0; o < j.n_out; ++o)
-      loaded |= j.m2_kind[o][b] != 0 || (pj.mode == kModeDecode && j.m1_kind[o][b] != 0);
-    if (!loaded) {
-      pj.copy_offs.clear();
-      return false;
-    }
-  }
-  return true;
-}
-
 // Attach sd tables, upload the offsets and mixing tables.  Must follow plan_encode / plan_decode.
 int bind_job(Context* ctx, PlannedJob& pj, JobMem& mem, hipStream_t st) {
   CodecJobBig& j = pj.job;
-  // flattened lane space: pairs rounded up to even (lane pairs share a 64-byte chunk); lines may
-  // then share a workgroup, whose per-lane line step must fit the kernel's 32-bit offsets
-  int64_t max_ls = std::max<int64_t>(pj.copy_ls, 0);
-  for (int b = 0; b < j.n_in; ++b) max_ls = std::max(max_ls, std::abs(j.in[b].line_stride));
-  for (int o = 0; o < j.n_out; ++o) max_ls = std::max(max_ls, std::abs(j.out[o].line_stride));
-  j.pairs_span = (j.n_pairs + 1) & ~1;
-  if (64 * max_ls + 65536 >= (int64_t(1) << 31)) j.pairs_span = (j.n_pairs + 63) & ~63;
-  // position offsets, then the fused copy-out offsets (if any), in one upload
-  const size_t n_off = pj.offs.size();
-  if (!pj.copy_offs.empty()) pj.offs.insert(pj.offs.end(), pj.copy_offs.begin(), pj.copy_offs.end());
+  const size_t n_off = finish_plan(pj);  // pairs_span; the copy offsets behind the positions
   auto t0 = std::chrono::steady_clock::now();
   auto lap = [&](const char* name) {
     const auto t1 = std::chrono::steady_clock::now();
@@ -1374,319 +970,6 @@ int bind_job(Context* ctx, PlannedJob& pj, JobMem& mem, hipStream_t st) {
     HIP_TRY(ctx->upload(mem.mix.p, pj.mix.data(), used * 2, st));
     j.mix_tab = mem.mix.as<uint16_t>();
     lap("bind_mix_copy");
-  }
-  return RS2_OK;
-}
-
-int bind_encode(Context* ctx, PlannedJob& pj, JobMem& mem, hipStream_t st) {
-  return bind_job(ctx, pj, mem, st);
-}
-
-// ---------------------------------------------------------------------------------------------
-// decode planning: erasure locator logs (FWHT), per-block IFFTs, block mixing matrices
-// ---------------------------------------------------------------------------------------------
-// XOR-convolution of the erasure indicator with LOG over the decoder's subspace of size W:
-//   L[p] = sum_{e erased} LOG[p ^ e]  (mod 65535),  via FWHT (W^-1 = 2^(16 - log W)).
-// Arithmetic mod 65535 on 16-bit values as reed-solomon-simd does it (65535 aliases 0): the
-// FWHT butterflies are one add and one fold each, no division.
-inline uint32_t add_mod16(uint32_t a, uint32_t b) {
-  const uint32_t t = a + b;
-  return (t + (t >> 16)) & 0xFFFFu;
-}
-inline uint32_t sub_mod16(uint32_t a, uint32_t b) {
-  const uint32_t d = a - b;
-  return (d + (d >> 16)) & 0xFFFFu;
-}
-void fwht16(uint32_t* a, uint32_t W) {
-  for (uint32_t h = 1; h < W; h <<= 1)
-    for (uint32_t i = 0; i < W; i += 2 * h)
-      for (uint32_t j = i; j < i + h; ++j) {
-        const uint32_t x = a[j], y = a[j + h];
-        a[j] = add_mod16(x, y);
-        a[j + h] = sub_mod16(x, y);
-      }
-}
-// FWHT of LOG over the first W entries: the same for every erasure pattern of a size, so it is
-// computed once per W (reed-solomon-simd keeps the 65536-point one, LOG_WALSH, as a table)
-const std::vector<uint32_t>& log_walsh(uint32_t W) {
-  static std::mutex mu;
-  static std::map<uint32_t, std::vector<uint32_t>> cache;
-  std::lock_guard<std::mutex> lk(mu);
-  auto it = cache.find(W);
-  if (it != cache.end()) return it->second;
-  const Gf& g = gf();
-  std::vector<uint32_t> lg(W);
-  for (uint32_t i = 0; i < W; ++i) lg[i] = g.log[i] % kModulus;  // LOG[0] = 65535 == 0
-  fwht16(lg.data(), W);
-  return cache.emplace(W, std::move(lg)).first->second;
-}
-// Erasure locator logs, the decoder's eval_poly restricted to its W-point subspace:
-//   L[p] = sum_{e erased} LOG[p ^ e]  (mod 65535)  = FWHT^-1(FWHT(erased) * FWHT(LOG)),
-// with FWHT^-1 = FWHT / W and 1/W = 2^(16 - log W) mod 65535 (2^16 == 1): a 16-bit rotate.
-std::vector<uint32_t> erasure_logs(const std::vector<uint8_t>& erased, uint32_t W) {
-  const std::vector<uint32_t>& lw = log_walsh(W);
-  std::vector<uint32_t> a(W);
-  for (uint32_t i = 0; i < W; ++i) a[i] = erased[i] ? 1u : 0u;
-  fwht16(a.data(), W);
-  for (uint32_t i = 0; i < W; ++i) {
-    const uint32_t x = a[i] == 0xFFFFu ? 0u : a[i], y = lw[i] == 0xFFFFu ? 0u : lw[i];
-    a[i] = x * y % kModulus;  // < 65535^2 < 2^32
-  }
-  fwht16(a.data(), W);
-  uint32_t logW = 0;
-  while ((1u << logW) < W) ++logW;
-  const uint32_t k = (16 - logW) & 15;
-  for (uint32_t i = 0; i < W; ++i) {
-    uint32_t x = a[i] == 0xFFFFu ? 0u : a[i];
-    x = ((x << k) | (x >> (16 - k))) & 0xFFFFu;  // x * 2^k mod 65535 (k = 0: x)
-    a[i] = x == 0xFFFFu ? 0u : x;
-  }
-  return a;
-}
-
-// Block-level mixing: out block o = FFT_o( sum_b M1[o][b] Dw(X_b) + M2[o][b] X_b ).
-void mixing_matrices(int m, uint32_t cs, uint32_t W, std::vector<std::vector<uint32_t>>& M1,
-                     std::vector<std::vector<uint32_t>>& M2) {
-  const Gf& g = gf();
-  std::vector<std::vector<uint32_t>> Va(m, std::vector<uint32_t>(m, 0)), Vb = Va;
-  for (int i = 0; i < m; ++i) Va[i][i] = 1;
-  auto xor_into = [&](std::vector<uint32_t>& a, const std::vector<uint32_t>& b) {
-    for (int i = 0; i < m; ++i) a[i] ^= b[i];
-  };
-  auto mul_into = [&](std::vector<uint32_t>& a, const std::vector<uint32_t>& b, uint32_t c) {
-    for (int i = 0; i < m; ++i) a[i] ^= g.mul(b[i], c);
-  };
-  for (uint32_t d = cs; d < W; d *= 2)
-    for (uint32_t r = 0; r < W; r += 2 * d) {
-      const uint32_t c = g.skew[r + d - 1];
-      for (uint32_t j = 0; j < d / cs; ++j) {
-        const int x = int(r / cs + j), y = int(x + d / cs);
-        xor_into(Va[y], Va[x]);
-        xor_into(Vb[y], Vb[x]);
-        if (c != kModulus) {
-          mul_into(Va[x], Va[y], c);
-          mul_into(Vb[x], Vb[y], c);
-        }
-      }
-    }
-  // formal derivative: in-block part (Dw) moves alpha to beta; cross-block bits add blocks
-  std::vector<std::vector<uint32_t>> nVa(m, std::vector<uint32_t>(m, 0));
-  for (int i = 0; i < m; ++i)
-    for (int t = 0; (1 << t) < m; ++t)
-      if (!((i >> t) & 1) && (i | (1 << t)) < m) xor_into(nVa[i], Va[i | (1 << t)]);
-  Vb = Va;
-  Va = nVa;
-  for (uint32_t d = W / 2; d >= cs && d > 0; d /= 2) {
-    for (uint32_t r = 0; r < W; r += 2 * d) {
-      const uint32_t c = g.skew[r + d - 1];
-      for (uint32_t j = 0; j < d / cs; ++j) {
-        const int x = int(r / cs + j), y = int(x + d / cs);
-        if (c != kModulus) {
-          mul_into(Va[x], Va[y], c);
-          mul_into(Vb[x], Vb[y], c);
-        }
-        xor_into(Va[y], Va[x]);
-        xor_into(Vb[y], Vb[x]);
-      }
-    }
-    if (d == cs) break;
-  }
-  M1 = Vb;
-  M2 = Va;
-}
-
-// Symbols of a 1D decode: present[q] = source offset (or -1) for shard index q < n;
-// dst(i) = destination offset of source symbol i (only erased originals are written here).
-struct DecodeSpec {
-  uint32_t K = 0, R = 0;
-  std::vector<int64_t> present;        // size K + R
-  const uint8_t* src_base = nullptr;
-  int64_t src_ls = 0;
-  uint8_t* dst_base = nullptr;
-  int64_t dst_ls = 0;
-  std::vector<int64_t> dst;            // size K: destination offset of source symbol i
-  int64_t dst_limit = INT64_MAX;
-  int symbol_size = 0;
-  bool copy_present = false;           // also write present originals to dst (fused copy)
-};
-
-int plan_decode(const DecodeSpec& sp, PlannedJob& pj) {
-  const uint32_t K = sp.K, R = sp.R;
-  if (!rate_supported(K, R)) return fail(RS2_E_INCOMPATIBLE_PARAMETERS, "unsupported shard count");
-  const bool high = use_high_rate(K, R);
-  const uint32_t cs0 = high ? next_pow2(R) : next_pow2(K);
-  const uint32_t end = high ? cs0 + K : cs0 + R;
-  const uint32_t W = next_pow2(end);
-  // blocks of C positions over the whole W-point transform (the chunk size cs0 only fixes
-  // where originals and recovery shards sit)
-  const uint32_t cs = std::min(cs0, block_max());
-  const int m = int(W / cs);
-  pj.in_sd.clear();
-  pj.out_sd.clear();
-  pj.in_first.clear();
-  pj.copy_offs.clear();
-  pj.mix.clear();
-  pj.has_mix = false;
-  pj.mode = kModeDecode;
-  auto opos = [&](uint32_t i) { return high ? cs0 + i : i; };
-  auto rpos = [&](uint32_t j) { return high ? j : cs0 + j; };
-  std::vector<uint8_t> erased(W, 0);
-  std::vector<int64_t> src_at(W, -1);
-  for (uint32_t i = 0; i < K; ++i) {
-    if (sp.present[i] >= 0) src_at[opos(i)] = sp.present[i];
-    else erased[opos(i)] = 1;
-  }
-  for (uint32_t j = 0; j < R; ++j) {
-    if (sp.present[K + j] >= 0) src_at[rpos(j)] = sp.present[K + j];
-    else erased[rpos(j)] = 1;
-  }
-  if (high)
-    for (uint32_t p = R; p < cs0; ++p) erased[p] = 1;
-  else
-    for (uint32_t p = end; p < W; ++p) erased[p] = 1;
-  const std::vector<uint32_t> L = erasure_logs(erased, W);
-  std::vector<std::vector<uint32_t>> M1, M2;
-  mixing_matrices(m, cs, W, M1, M2);
-
-  CodecJobBig& j = pj.job;
-  j = CodecJobBig{};
-  j.symbol_size = sp.symbol_size;
-  j.n_pairs = (sp.symbol_size + 3) / 4;
-  j.shared_in = 0;
-  pj.C = int(cs);
-  // input blocks with at least one present position
-  std::vector<int> in_blocks, out_blocks;
-  for (int b = 0; b < m; ++b) {
-    bool any = false;
-    for (uint32_t p = 0; p < cs; ++p) any |= src_at[b * cs + p] >= 0;
-    if (any) in_blocks.push_back(b);
-  }
-  for (int b = 0; b < m; ++b) {
-    bool any = false;
-    for (uint32_t i = 0; i < K; ++i)
-      any |= sp.present[i] < 0 && opos(i) / cs == uint32_t(b);
-    if (any) out_blocks.push_back(b);
-  }
-  if (in_blocks.size() > size_t(max_blocks(int(cs))) || out_blocks.size() > size_t(max_blocks(int(cs))))
-    return plan_fail_unsupported("too many decode blocks");
-  pj.mix_stride = std::max(in_blocks.size(), out_blocks.size()) > size_t(kMaxBlocks) ? kMaxBlocksBig
-                                                                                     : kMaxBlocks;
-  // Block pair (rs2_codec.hip load_ifft, CodecJob::pair_p): with one output block, an input
-  // block Q mixed with M1 = 0 (coefficient 1 once folded below) and another block P whose
-  // active waves (ceil(count / ppw)) fit the workgroup together run their loads and in-wave
-  // IFFT layers in one pass.  Q moves to the end of the input list (the kernel's convention).
-  const int ppw = std::min<int>(int(cs), kPpwTarget), nw = int(cs) / ppw;
-  auto block_waves = [&](int b) {
-    int count = 0;
-    for (uint32_t p = 0; p < cs; ++p)
-      if (src_at[b * cs + p] >= 0) count = int(p) + 1;
-    return (count + ppw - 1) / ppw;
-  };
-  int pair_p = -1, pair_nw = 0;
-  static const bool no_pair = env_int("RS2_PAIR", 1) == 0;  // A/B knob: 0 = never pair
-  if (!no_pair && nw > 1 && out_blocks.size() == 1) {
-    const int o = out_blocks[0];
-    for (size_t qi = 0; qi < in_blocks.size() && pair_p < 0; ++qi) {
-      const int q = in_blocks[qi];
-      if (M1[o][q] != 0 || M2[o][q] == 0) continue;
-      for (size_t pi = 0; pi < in_blocks.size(); ++pi) {
-        const int p = in_blocks[pi];
-        if (p == q || (M1[o][p] == 0 && M2[o][p] == 0)) continue;
-        if (block_waves(p) + block_waves(q) > nw) continue;
-        in_blocks.erase(in_blocks.begin() + qi);
-        in_blocks.push_back(q);
-        pair_p = int(std::find(in_blocks.begin(), in_blocks.end(), p) - in_blocks.begin());
-        pair_nw = block_waves(p);
-        break;
-      }
-    }
-  }
-  std::fill(std::begin(j.pair_p), std::end(j.pair_p), int8_t(-1));
-  std::fill(std::begin(j.pair_q), std::end(j.pair_q), int8_t(-1));
-  std::fill(std::begin(j.pair_nw), std::end(j.pair_nw), int8_t(0));
-  if (pair_p >= 0) {
-    j.pair_p[0] = int8_t(pair_p);
-    j.pair_q[0] = int8_t(in_blocks.size() - 1);
-    j.pair_nw[0] = int8_t(pair_nw);
-  }
-  j.n_in = int(in_blocks.size());
-  j.n_out = int(out_blocks.size());
-  pj.n_z = j.n_out;
-  pj.offs.assign(size_t(j.n_in + j.n_out) * cs, -1);
-  pj.pre_logs.assign(size_t(j.n_out) * j.n_in * cs, 0);
-  pj.post_logs.assign(size_t(j.n_out) * cs, 0);
-  pj.has_pre = pj.has_post = true;
-  for (int bi = 0; bi < j.n_in; ++bi) {
-    const int b = in_blocks[bi];
-    InBlock& ib = j.in[bi];
-    ib.base = sp.src_base;
-    ib.line_stride = sp.src_ls;
-    int count = 0;
-    for (uint32_t p = 0; p < cs; ++p) {
-      const uint32_t gp = b * cs + p;
-      if (src_at[gp] >= 0) {
-        pj.offs[pj.in_off(bi) + p] = src_at[gp];
-        count = int(p) + 1;
-      }
-    }
-    ib.count = count;
-    pj.in_sd.push_back(int(b * cs));
-    pj.in_first.push_back(uint32_t(b * cs));
-  }
-  if (sp.copy_present) {
-    pj.copy_base = sp.dst_base;
-    pj.copy_ls = sp.dst_ls;
-    pj.copy_limit = sp.dst_limit;
-    pj.copy_offs.assign(size_t(j.n_in) * cs, -1);
-    for (int bi = 0; bi < j.n_in; ++bi)
-      for (uint32_t i = 0; i < K; ++i)
-        if (sp.present[i] >= 0 && opos(i) / cs == uint32_t(in_blocks[bi]))
-          pj.copy_offs[size_t(bi) * cs + opos(i) % cs] = sp.dst[i];
-  }
-  for (int oi = 0; oi < j.n_out; ++oi) {
-    const int o = out_blocks[oi];
-    OutBlock& ob = j.out[oi];
-    ob.base = sp.dst_base;
-    ob.line_stride = sp.dst_ls;
-    ob.limit = sp.dst_limit;
-    int trunc = 0;
-    for (uint32_t i = 0; i < K; ++i) {
-      if (sp.present[i] >= 0) continue;
-      const uint32_t gp = opos(i);
-      if (gp / cs != uint32_t(o)) continue;
-      const uint32_t p = gp % cs;
-      pj.offs[pj.out_off(oi) + p] = sp.dst[i];
-      pj.post_logs[size_t(oi) * cs + p] = uint16_t(kModulus - L[gp]);  // 65535 == times one
-      trunc = std::max(trunc, int(p) + 1);
-    }
-    ob.trunc = trunc;
-    pj.out_sd.push_back(int(o * cs));
-    // Fold one mixing coefficient of every input block into its pre-multiplier (the decoder
-    // scales each loaded symbol by exp(L[p]) anyway).  With f = M1 (or M2 when M1 is zero) and
-    // X'_b = IFFT_b(f * exp(L) * in_b) = f * X_b (IFFT and Dw are GF-linear):
-    //   M1 Dw(X_b) + M2 X_b = Dw(X'_b) + (M2 / M1) X'_b
-    // so the block costs at most one table multiply per position instead of three.  Each output
-    // block folds its own coefficients, hence per-output pre tables (CodecJob::pre_z_stride).
-    const Gf& g = gf();
-    Coef c1(j.n_in), c2(j.n_in);
-    for (int bi = 0; bi < j.n_in; ++bi) {
-      const int b = in_blocks[bi];
-      c1[bi] = M1[o][b];
-      c2[bi] = M2[o][b];
-      const uint32_t f = c1[bi] ? c1[bi] : c2[bi];
-      if (f == 0) continue;  // this output does not use the block
-      const uint32_t lf = g.log[f];
-      if (c1[bi]) {
-        c2[bi] = c2[bi] ? g.mul(c2[bi], kModulus - lf) : 0u;
-        c1[bi] = 1;
-      } else {
-        c2[bi] = 1;
-      }
-      uint16_t* pl = pj.pre_logs.data() + (size_t(oi) * j.n_in + bi) * cs;
-      for (uint32_t p = 0; p < cs; ++p)
-        if (src_at[b * cs + p] >= 0) pl[p] = uint16_t(Gf::add_mod(L[b * cs + p], lf));
-    }
-    set_mixing(pj, oi, &c1, c2);
   }
   return RS2_OK;
 }
@@ -2213,7 +1496,7 @@ int bind_encode_buffers(rs2_plan* p, uint8_t* d_primary, uint8_t* d_secondary, h
   RS2_TRY(plan_encode(
       uint32_t(ks), uint32_t(n - ks), int(s), d_primary, ks * s, [&](uint32_t c) { return int64_t(c) * s; },
       d_secondary, s, [&](uint32_t j) { return (ks + int64_t(j)) * kp * s; }, INT64_MAX, p->row));
-  RS2_TRY(bind_encode(p->ctx, p->row, p->row_mem, st));
+  RS2_TRY(bind_job(p->ctx, p->row, p->row_mem, st));
   // systematic columns c < K_s: primary encoding (K = K_p) -> primary slivers K_p..n, column c
   RS2_TRY(plan_encode(
       uint32_t(kp), uint32_t(n - kp), int(s), d_primary, s, [&](uint32_t r) { return int64_t(r) * ks * s; },
@@ -2225,7 +1508,7 @@ int bind_encode_buffers(rs2_plan* p, uint8_t* d_primary, uint8_t* d_secondary, h
     set_copy(p->col_sys, d_secondary, kp * s, INT64_MAX, [&](uint32_t r) { return int64_t(r) * s; });
     p->sys_fused = copy_covered(p->col_sys);
   }
-  RS2_TRY(bind_encode(p->ctx, p->col_sys, p->col_sys_mem, st));
+  RS2_TRY(bind_job(p->ctx, p->col_sys, p->col_sys_mem, st));
   // the column loads are also every byte of the blob: when one shared-input block holds the
   // K_p rows in order (position r at r * K_s * s), col_sys reads the blob in place and writes
   // the systematic primary slivers itself instead of a separate blob copy
@@ -2245,7 +1528,7 @@ int bind_encode_buffers(rs2_plan* p, uint8_t* d_primary, uint8_t* d_secondary, h
       uint32_t(kp), uint32_t(n - kp), int(s), d_secondary + ks * kp * s, kp * s,
       [&](uint32_t r) { return int64_t(r) * s; }, d_both, s,
       [&](uint32_t j) { return int64_t(j) * (n - ks) * s; }, INT64_MAX, p->col_rep));
-  RS2_TRY(bind_encode(p->ctx, p->col_rep, p->col_rep_mem, st));
+  RS2_TRY(bind_job(p->ctx, p->col_rep, p->col_rep_mem, st));
   p->bound_primary = d_primary;
   p->bound_secondary = d_secondary;
   p->bound_both = d_both;
@@ -2336,7 +1619,7 @@ int encode_device(rs2_plan* p, const uint8_t* d_blob, uint8_t* d_primary, uint8_
       HIP_TRY(hipMemsetAsync(d_primary + p->blob_len, 0, msg - p->blob_len, side));
     mark(p, "enc_blob_copy", side);
     HIP_TRY(hipEventRecord(p->copy_ev, side));
-    HIP_TRY(p->col_sys.launch(int(ks), side, ctr));
+    HIP_TRY(launch_job(p->col_sys, int(ks), side, ctr));
   }
   mark(p, "enc_cols_sys_codec", side);
   HIP_TRY(hipEventRecord(p->join_ev, side));
@@ -2391,7 +1674,7 @@ int encode_device(rs2_plan* p, const uint8_t* d_blob, uint8_t* d_primary, uint8_
                            0, ctr + 2 * kTileCtrWords));
   }
   mark(p, "enc_rows_codec", st);
-  HIP_TRY(p->col_rep.launch(int(n - ks), st, ctr + 3 * kTileCtrWords));
+  HIP_TRY(launch_job(p->col_rep, int(n - ks), st, ctr + 3 * kTileCtrWords));
   mark(p, "enc_cols_rep_codec", st);
   // leaf hashes of all n x n symbols, 2n Merkle trees, root and blob id.  The primary slivers'
   // leaves (run A) are hashed on the side stream as soon as the systematic-column codec is done,
@@ -2643,7 +1926,7 @@ int run_decode(Context* ctx, DecodeSlot (&slots)[2], int& cursor, DecodeSpec& sp
       if (prof) prof_host(prof, "dec_plan_host", host_t0);
     }
     if (prof) mark(prof, "dec_setup", st);
-    HIP_TRY(pj.launch(lines, st));
+    HIP_TRY(launch_job(pj, lines, st));
     if (prof) mark(prof, "dec_codec", st);
   }
   if (!sl.done) HIP_TRY(hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
@@ -2774,7 +2057,7 @@ int rs2_set_device(int device) {
   return RS2_OK;
 }
 
-const char* rs2_last_error(void) { return g_last_error.c_str(); }
+const char* rs2_last_error(void) { return last_error(); }
 
 int rs2_device_available(void) {
   int n = 0;
@@ -2784,7 +2067,7 @@ int rs2_device_available(void) {
 int rs2_set_block_limit(uint32_t max_block) {
   if (max_block < 1 || max_block > uint32_t(kMaxC) || (max_block & (max_block - 1)))
     return fail(RS2_E_INVALID_ARGUMENT, "block limit must be a power of two <= 512");
-  g_block_max.store(max_block, std::memory_order_relaxed);
+  set_block_max(max_block);
   return RS2_OK;
 }
 
@@ -3386,8 +2669,8 @@ int rs2_encode_1d(uint16_t k, uint16_t n_shards, uint16_t symbol_size, uint32_t 
   RS2_TRY(plan_encode(uint32_t(K), uint32_t(N - K), int(s), din.as<uint8_t>(), K * s,
                       [&](uint32_t i) { return int64_t(i) * s; }, dout.as<uint8_t>(), N * s,
                       [&](uint32_t j) { return (K + int64_t(j)) * s; }, INT64_MAX, pj));
-  RS2_TRY(bind_encode(ctx, pj, mem, st));
-  HIP_TRY(pj.launch(int(batch), st));
+  RS2_TRY(bind_job(ctx, pj, mem, st));
+  HIP_TRY(launch_job(pj, int(batch), st));
   HIP_TRY(hipStreamSynchronize(st));
   for (uint32_t b = 0; b < batch; ++b)
     HIP_TRY(hipMemcpy(out_all + b * N * s + K * s, dout.as<uint8_t>() + b * N * s + K * s,
@@ -3451,7 +2734,7 @@ int rs2_decode_1d(uint16_t k, uint16_t n_shards, uint16_t symbol_size, uint32_t 
   for (int64_t i = 0; i < K; ++i) sp.dst[i] = i * s;
   RS2_TRY(plan_decode(sp, D.pj));
   RS2_TRY(bind_decode(ctx, D.pj, D.mem, st));
-  HIP_TRY(D.pj.launch(1, st));
+  HIP_TRY(launch_job(D.pj, 1, st));
   HIP_TRY(hipMemcpyAsync(D.hout.p, dout.p, size_t(K) * s, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   const uint8_t* dec = static_cast<const uint8_t*>(D.hout.p);
@@ -3577,8 +2860,8 @@ int verifier_leaves(rs2_verifier* v, uint32_t count, const uint8_t* din, hipStre
     RS2_TRY(plan_encode(uint32_t(K), uint32_t(n - K), int(s), din, K * s,
                         [&](uint32_t i) { return int64_t(i) * s; }, rep, (n - K) * s,
                         [&](uint32_t j) { return int64_t(j) * s; }, INT64_MAX, v->job));
-    RS2_TRY(bind_encode(v->ctx, v->job, v->mem, st));
-    HIP_TRY(v->job.launch(int(count), st));
+    RS2_TRY(bind_job(v->ctx, v->job, v->mem, st));
+    HIP_TRY(launch_job(v->job, int(count), st));
   }
   SymbolMap map{din, rep, nullptr, int(n), int(count), int(K), int(s)};
   HIP_TRY(rs2k_launch_leaf_hash(map, 4, int64_t(count) * n, 1, v->leaves.as<uint8_t>(), st));
@@ -3852,12 +3135,12 @@ int rs2_codec_encode_device_async(rs2_codec* c, uint32_t lines, const void* d_sr
     RS2_TRY(plan_encode(uint32_t(c->k), uint32_t(c->n - c->k), int(c->s), src, key[1],
                         [&](uint32_t i) { return int64_t(i) * ss; }, dst, key[3],
                         [&](uint32_t j) { return int64_t(j) * rs; }, INT64_MAX, c->enc));
-    RS2_TRY(bind_encode(c->ctx, c->enc, c->enc_mem, st));
+    RS2_TRY(bind_job(c->ctx, c->enc, c->enc_mem, st));
     std::copy(key, key + 4, c->enc_key);
   }
   for (int b = 0; b < c->enc.job.n_in; ++b) c->enc.job.in[b].base = src;
   for (int o = 0; o < c->enc.job.n_out; ++o) c->enc.job.out[o].base = dst;
-  HIP_TRY(c->enc.launch(int(lines), st));
+  HIP_TRY(launch_job(c->enc, int(lines), st));
   if (!c->enc_done) HIP_TRY(hipEventCreateWithFlags(&c->enc_done, hipEventDisableTiming));
   HIP_TRY(hipEventRecord(c->enc_done, st));
   return RS2_OK;

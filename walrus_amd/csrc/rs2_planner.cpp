@@ -1,0 +1,546 @@
+// The codec job planner (rs2_planner.h): GF(2^16) tables, encode / decode job plans.  No device
+// runtime here: everything below is host arithmetic on plain structs.
+//
+// Reference semantics: reed-solomon-simd 3.1.0 (Cargo.lock:8813): GF tables, skew, rates --
+// restated in oracle/rs2_oracle.py, mirrored here.
+#include "rs2_planner.h"
+
+#include <atomic>
+#include <cstdlib>
+#include <iterator>
+#include <map>
+#include <mutex>
+
+namespace rs2 {
+
+namespace {
+thread_local std::string g_last_error = "ok";
+}
+
+int fail(int code, const std::string& msg) {
+  g_last_error = msg;
+  return code;
+}
+
+const char* last_error() { return g_last_error.c_str(); }
+
+int env_int(const char* name, int dflt) {
+  const char* e = std::getenv(name);
+  return e ? std::atoi(e) : dflt;
+}
+
+// ---------------------------------------------------------------------------------------------
+// GF(2^16) tables (reed-solomon-simd engine/tables.rs restated; see oracle/rs2_oracle.py)
+// ---------------------------------------------------------------------------------------------
+namespace {
+constexpr uint32_t kPoly = 0x1002D;
+constexpr uint16_t kCantor[16] = {0x0001, 0xACCA, 0x3C0E, 0x163E, 0xC582, 0xED2E, 0x914C, 0x4012,
+                                  0x6C98, 0x10D8, 0x6A72, 0xB900, 0xFDB8, 0xFB34, 0xFF38, 0x991E};
+}  // namespace
+
+Gf::Gf() : exp(kOrder), log(kOrder), skew(kModulus) {
+  std::vector<uint32_t> e(kOrder), l(kOrder);
+  uint32_t state = 1;
+  for (uint32_t i = 0; i < kModulus; ++i) {
+    e[state] = i;
+    state <<= 1;
+    if (state >= kOrder) state ^= kPoly;
+  }
+  e[0] = kModulus;
+  l[0] = 0;
+  for (int i = 0; i < 16; ++i) {
+    const uint32_t width = 1u << i;
+    for (uint32_t j = 0; j < width; ++j) l[j + width] = l[j] ^ kCantor[i];
+  }
+  for (uint32_t i = 0; i < kOrder; ++i) l[i] = e[l[i]];
+  for (uint32_t i = 0; i < kOrder; ++i) e[l[i]] = i;
+  e[kModulus] = e[0];
+  for (uint32_t i = 0; i < kOrder; ++i) {
+    exp[i] = uint16_t(e[i]);
+    log[i] = uint16_t(l[i]);
+  }
+  // skew LUT
+  std::vector<uint32_t> sk(kModulus, 0);
+  uint32_t temp[15];
+  for (int i = 1; i < 16; ++i) temp[i - 1] = 1u << i;
+  for (int m = 0; m < 15; ++m) {
+    const uint32_t step = 1u << (m + 1);
+    sk[(1u << m) - 1] = 0;
+    for (int i = m; i < 15; ++i) {
+      const uint32_t s = 1u << (i + 1);
+      for (uint32_t j = (1u << m) - 1; j < s; j += step) sk[j + s] = sk[j] ^ temp[i];
+    }
+    temp[m] = kModulus - log[mul(temp[m], log[temp[m] ^ 1])];
+    for (int i = m + 1; i < 15; ++i) temp[i] = mul(temp[i], add_mod(log[temp[i] ^ 1], temp[m]));
+  }
+  for (uint32_t i = 0; i < kModulus; ++i) skew[i] = log[sk[i]];
+}
+
+const Gf& gf() {
+  static const Gf g;
+  return g;
+}
+
+void nib_table(uint32_t log_m, bool fft_zero, uint16_t* out) {
+  const Gf& g = gf();
+  const bool zero = fft_zero && log_m == kModulus;
+  for (uint32_t e = 0; e < uint32_t(kTabU16); ++e) {
+    const uint32_t x = e < 64 ? e : (e < 96 ? (e - 64) << 6 : (e - 96) << 11);
+    out[e] = zero ? 0 : uint16_t(g.mul(x, log_m));
+  }
+}
+
+std::vector<uint16_t> sd_stream(int C, int sd, int ppw) {
+  const Gf& g = gf();
+  const int NW = C >= ppw ? C / ppw : 1, PPW = C / NW;
+  std::vector<uint16_t> out;
+  out.reserve(size_t(std::max(C - 1, 0)) * kTabU16);
+  uint16_t t[kTabU16];
+  for (int w = 0; w < NW; ++w)
+    for (int d = 1; d < PPW; d *= 2)
+      for (int gi = 0; gi < PPW / (2 * d); ++gi) {
+        const int r = w * PPW + 2 * d * gi;
+        nib_table(g.skew[r + d + sd - 1], true, t);
+        out.insert(out.end(), t, t + kTabU16);
+      }
+  for (int d = PPW; d < C; d *= 2)
+    for (int gi = 0; gi < C / (2 * d); ++gi) {
+      const int r = 2 * d * gi;
+      nib_table(g.skew[r + d + sd - 1], true, t);
+      out.insert(out.end(), t, t + kTabU16);
+    }
+  return out;
+}
+
+int group0_zero(int C, int sd, int ppw) {
+  const Gf& g = gf();
+  const int NW = C >= ppw ? C / ppw : 1, PPW = C / NW;
+  if (NW == 1) return 0;
+  for (int d = PPW; d < C; d *= 2)
+    if (g.skew[d + sd - 1] != kModulus) return 0;
+  return 1;
+}
+
+uint32_t next_pow2(uint32_t x) {
+  uint32_t p = 1;
+  while (p < x) p <<= 1;
+  return p;
+}
+
+// reed-solomon-simd DefaultRate: high rate iff pow2(recovery) <= pow2(original)
+bool use_high_rate(uint32_t k, uint32_t r) { return next_pow2(r) <= next_pow2(k); }
+
+bool rate_supported(uint32_t k, uint32_t r) {
+  if (k == 0 || r == 0 || k >= kOrder || r >= kOrder) return false;
+  return std::min(next_pow2(k), next_pow2(r)) + std::max(k, r) <= kOrder;
+}
+
+namespace {
+std::atomic<uint32_t> g_block_max{0};
+}
+uint32_t block_max() {
+  uint32_t v = g_block_max.load(std::memory_order_relaxed);
+  if (v) return v;
+  uint32_t x = uint32_t(env_int("RS2_BLOCK_MAX", kMaxC));
+  if (x < 1 || x > uint32_t(kMaxC) || (x & (x - 1))) x = uint32_t(kMaxC);
+  g_block_max.store(x, std::memory_order_relaxed);
+  return x;
+}
+
+int max_blocks(int C) { return C == kMaxC ? kMaxBlocksBig : kMaxBlocks; }
+
+void set_block_max(uint32_t max_block) { g_block_max.store(max_block, std::memory_order_relaxed); }
+
+void coef_xor(Coef& y, const Coef& x) {
+  for (size_t i = 0; i < y.size(); ++i) y[i] ^= x[i];
+}
+namespace {
+void coef_mul_xor(Coef& y, const Coef& x, uint32_t log_c) {
+  const Gf& g = gf();
+  for (size_t i = 0; i < y.size(); ++i) y[i] ^= g.mul(x[i], log_c);
+}
+}  // namespace
+// IFFT layers d = C .. span/2 of a size-`span` transform with skew offset sd
+void sym_ifft_top(std::vector<Coef>& V, uint32_t C, uint32_t span, uint32_t sd) {
+  const Gf& g = gf();
+  for (uint32_t d = C; d < span; d *= 2)
+    for (uint32_t r = 0; r < span; r += 2 * d) {
+      const uint32_t c = g.skew[r + d + sd - 1];
+      for (uint32_t j = 0; j < d / C; ++j) {
+        const uint32_t x = r / C + j, y = x + d / C;
+        coef_xor(V[y], V[x]);
+        if (c != kModulus) coef_mul_xor(V[x], V[y], c);
+      }
+    }
+}
+// FFT layers d = span/2 .. C of a size-`span` transform with skew offset sd
+void sym_fft_top(std::vector<Coef>& V, uint32_t C, uint32_t span, uint32_t sd) {
+  const Gf& g = gf();
+  for (uint32_t d = span / 2; d >= C && d > 0; d /= 2) {
+    for (uint32_t r = 0; r < span; r += 2 * d) {
+      const uint32_t c = g.skew[r + d + sd - 1];
+      for (uint32_t j = 0; j < d / C; ++j) {
+        const uint32_t x = r / C + j, y = x + d / C;
+        if (c != kModulus) coef_mul_xor(V[x], V[y], c);
+        coef_xor(V[y], V[x]);
+      }
+    }
+    if (d == C) break;
+  }
+}
+
+// Mixing kinds and tables of output block oi from its coefficient vectors (M1 may be empty).
+void set_mixing(PlannedJob& pj, int oi, const Coef* m1, const Coef& m2) {
+  const Gf& g = gf();
+  CodecJobBig& j = pj.job;
+  const size_t ms = size_t(pj.mix_stride);
+  if (pj.mix.empty()) pj.mix.assign(ms * ms * 2 * kTabU16, 0);
+  for (int bi = 0; bi < j.n_in; ++bi) {
+    const uint32_t c1 = m1 ? (*m1)[bi] : 0u, c2 = m2[bi];
+    j.m1_kind[oi][bi] = uint8_t(c1 == 0 ? 0 : (c1 == 1 ? 1 : 2));
+    j.m2_kind[oi][bi] = uint8_t(c2 == 0 ? 0 : (c2 == 1 ? 1 : 2));
+    uint16_t* t = pj.mix.data() + (size_t(oi) * ms + bi) * 2 * kTabU16;
+    if (c1 > 1) {
+      nib_table(g.log[c1], false, t);
+      pj.has_mix = true;
+    }
+    if (c2 > 1) {
+      nib_table(g.log[c2], false, t + kTabU16);
+      pj.has_mix = true;
+    }
+  }
+}
+
+bool copy_covered(PlannedJob& pj) {
+  if (pj.copy_offs.empty()) return false;
+  if (pj.mode == kModeRows) {  // the mixed-encode kernel has no copy-out (register budget)
+    pj.copy_offs.clear();
+    return false;
+  }
+  const CodecJobBig& j = pj.job;
+  for (int b = 0; b < j.n_in; ++b) {
+    bool any_copy = false;
+    for (int p = 0; p < pj.C; ++p) any_copy |= pj.copy_offs[size_t(b) * pj.C + p] >= 0;
+    if (!any_copy || j.shared_in) continue;
+    bool loaded = false;
+    for (int o = 0; o < j.n_out; ++o)
+      loaded |= j.m2_kind[o][b] != 0 || (pj.mode == kModeDecode && j.m1_kind[o][b] != 0);
+    if (!loaded) {
+      pj.copy_offs.clear();
+      return false;
+    }
+  }
+  return true;
+}
+
+size_t finish_plan(PlannedJob& pj) {
+  CodecJobBig& j = pj.job;
+  // flattened lane space: pairs rounded up to even (lane pairs share a 64-byte chunk); lines may
+  // then share a workgroup, whose per-lane line step must fit the kernel's 32-bit offsets
+  int64_t max_ls = std::max<int64_t>(pj.copy_ls, 0);
+  for (int b = 0; b < j.n_in; ++b) max_ls = std::max(max_ls, std::abs(j.in[b].line_stride));
+  for (int o = 0; o < j.n_out; ++o) max_ls = std::max(max_ls, std::abs(j.out[o].line_stride));
+  j.pairs_span = (j.n_pairs + 1) & ~1;
+  if (64 * max_ls + 65536 >= (int64_t(1) << 31)) j.pairs_span = (j.n_pairs + 63) & ~63;
+  const size_t n_off = pj.offs.size();
+  if (!pj.copy_offs.empty()) pj.offs.insert(pj.offs.end(), pj.copy_offs.begin(), pj.copy_offs.end());
+  return n_off;
+}
+
+// ---------------------------------------------------------------------------------------------
+// decode planning: erasure locator logs (FWHT), per-block IFFTs, block mixing matrices
+// ---------------------------------------------------------------------------------------------
+// XOR-convolution of the erasure indicator with LOG over the decoder's subspace of size W:
+//   L[p] = sum_{e erased} LOG[p ^ e]  (mod 65535),  via FWHT (W^-1 = 2^(16 - log W)).
+// Arithmetic mod 65535 on 16-bit values as reed-solomon-simd does it (65535 aliases 0): the
+// FWHT butterflies are one add and one fold each, no division.
+namespace {
+inline uint32_t add_mod16(uint32_t a, uint32_t b) {
+  const uint32_t t = a + b;
+  return (t + (t >> 16)) & 0xFFFFu;
+}
+inline uint32_t sub_mod16(uint32_t a, uint32_t b) {
+  const uint32_t d = a - b;
+  return (d + (d >> 16)) & 0xFFFFu;
+}
+void fwht16(uint32_t* a, uint32_t W) {
+  for (uint32_t h = 1; h < W; h <<= 1)
+    for (uint32_t i = 0; i < W; i += 2 * h)
+      for (uint32_t j = i; j < i + h; ++j) {
+        const uint32_t x = a[j], y = a[j + h];
+        a[j] = add_mod16(x, y);
+        a[j + h] = sub_mod16(x, y);
+      }
+}
+// FWHT of LOG over the first W entries: the same for every erasure pattern of a size, so it is
+// computed once per W (reed-solomon-simd keeps the 65536-point one, LOG_WALSH, as a table)
+const std::vector<uint32_t>& log_walsh(uint32_t W) {
+  static std::mutex mu;
+  static std::map<uint32_t, std::vector<uint32_t>> cache;
+  std::lock_guard<std::mutex> lk(mu);
+  auto it = cache.find(W);
+  if (it != cache.end()) return it->second;
+  const Gf& g = gf();
+  std::vector<uint32_t> lg(W);
+  for (uint32_t i = 0; i < W; ++i) lg[i] = g.log[i] % kModulus;  // LOG[0] = 65535 == 0
+  fwht16(lg.data(), W);
+  return cache.emplace(W, std::move(lg)).first->second;
+}
+// Erasure locator logs, the decoder's eval_poly restricted to its W-point subspace:
+//   L[p] = sum_{e erased} LOG[p ^ e]  (mod 65535)  = FWHT^-1(FWHT(erased) * FWHT(LOG)),
+// with FWHT^-1 = FWHT / W and 1/W = 2^(16 - log W) mod 65535 (2^16 == 1): a 16-bit rotate.
+std::vector<uint32_t> erasure_logs(const std::vector<uint8_t>& erased, uint32_t W) {
+  const std::vector<uint32_t>& lw = log_walsh(W);
+  std::vector<uint32_t> a(W);
+  for (uint32_t i = 0; i < W; ++i) a[i] = erased[i] ? 1u : 0u;
+  fwht16(a.data(), W);
+  for (uint32_t i = 0; i < W; ++i) {
+    const uint32_t x = a[i] == 0xFFFFu ? 0u : a[i], y = lw[i] == 0xFFFFu ? 0u : lw[i];
+    a[i] = x * y % kModulus;  // < 65535^2 < 2^32
+  }
+  fwht16(a.data(), W);
+  uint32_t logW = 0;
+  while ((1u << logW) < W) ++logW;
+  const uint32_t k = (16 - logW) & 15;
+  for (uint32_t i = 0; i < W; ++i) {
+    uint32_t x = a[i] == 0xFFFFu ? 0u : a[i];
+    x = ((x << k) | (x >> (16 - k))) & 0xFFFFu;  // x * 2^k mod 65535 (k = 0: x)
+    a[i] = x == 0xFFFFu ? 0u : x;
+  }
+  return a;
+}
+
+// Block-level mixing: out block o = FFT_o( sum_b M1[o][b] Dw(X_b) + M2[o][b] X_b ).
+void mixing_matrices(int m, uint32_t cs, uint32_t W, std::vector<std::vector<uint32_t>>& M1,
+                     std::vector<std::vector<uint32_t>>& M2) {
+  const Gf& g = gf();
+  std::vector<std::vector<uint32_t>> Va(m, std::vector<uint32_t>(m, 0)), Vb = Va;
+  for (int i = 0; i < m; ++i) Va[i][i] = 1;
+  auto xor_into = [&](std::vector<uint32_t>& a, const std::vector<uint32_t>& b) {
+    for (int i = 0; i < m; ++i) a[i] ^= b[i];
+  };
+  auto mul_into = [&](std::vector<uint32_t>& a, const std::vector<uint32_t>& b, uint32_t c) {
+    for (int i = 0; i < m; ++i) a[i] ^= g.mul(b[i], c);
+  };
+  for (uint32_t d = cs; d < W; d *= 2)
+    for (uint32_t r = 0; r < W; r += 2 * d) {
+      const uint32_t c = g.skew[r + d - 1];
+      for (uint32_t j = 0; j < d / cs; ++j) {
+        const int x = int(r / cs + j), y = int(x + d / cs);
+        xor_into(Va[y], Va[x]);
+        xor_into(Vb[y], Vb[x]);
+        if (c != kModulus) {
+          mul_into(Va[x], Va[y], c);
+          mul_into(Vb[x], Vb[y], c);
+        }
+      }
+    }
+  // formal derivative: in-block part (Dw) moves alpha to beta; cross-block bits add blocks
+  std::vector<std::vector<uint32_t>> nVa(m, std::vector<uint32_t>(m, 0));
+  for (int i = 0; i < m; ++i)
+    for (int t = 0; (1 << t) < m; ++t)
+      if (!((i >> t) & 1) && (i | (1 << t)) < m) xor_into(nVa[i], Va[i | (1 << t)]);
+  Vb = Va;
+  Va = nVa;
+  for (uint32_t d = W / 2; d >= cs && d > 0; d /= 2) {
+    for (uint32_t r = 0; r < W; r += 2 * d) {
+      const uint32_t c = g.skew[r + d - 1];
+      for (uint32_t j = 0; j < d / cs; ++j) {
+        const int x = int(r / cs + j), y = int(x + d / cs);
+        if (c != kModulus) {
+          mul_into(Va[x], Va[y], c);
+          mul_into(Vb[x], Vb[y], c);
+        }
+        xor_into(Va[y], Va[x]);
+        xor_into(Vb[y], Vb[x]);
+      }
+    }
+    if (d == cs) break;
+  }
+  M1 = Vb;
+  M2 = Va;
+}
+}  // namespace
+
+int plan_decode(const DecodeSpec& sp, PlannedJob& pj) {
+  const uint32_t K = sp.K, R = sp.R;
+  if (!rate_supported(K, R)) return fail(RS2_E_INCOMPATIBLE_PARAMETERS, "unsupported shard count");
+  const bool high = use_high_rate(K, R);
+  const uint32_t cs0 = high ? next_pow2(R) : next_pow2(K);
+  const uint32_t end = high ? cs0 + K : cs0 + R;
+  const uint32_t W = next_pow2(end);
+  // blocks of C positions over the whole W-point transform (the chunk size cs0 only fixes
+  // where originals and recovery shards sit)
+  const uint32_t cs = std::min(cs0, block_max());
+  const int m = int(W / cs);
+  pj.in_sd.clear();
+  pj.out_sd.clear();
+  pj.in_first.clear();
+  pj.copy_offs.clear();
+  pj.mix.clear();
+  pj.has_mix = false;
+  pj.mode = kModeDecode;
+  auto opos = [&](uint32_t i) { return high ? cs0 + i : i; };
+  auto rpos = [&](uint32_t j) { return high ? j : cs0 + j; };
+  std::vector<uint8_t> erased(W, 0);
+  std::vector<int64_t> src_at(W, -1);
+  for (uint32_t i = 0; i < K; ++i) {
+    if (sp.present[i] >= 0) src_at[opos(i)] = sp.present[i];
+    else erased[opos(i)] = 1;
+  }
+  for (uint32_t j = 0; j < R; ++j) {
+    if (sp.present[K + j] >= 0) src_at[rpos(j)] = sp.present[K + j];
+    else erased[rpos(j)] = 1;
+  }
+  if (high)
+    for (uint32_t p = R; p < cs0; ++p) erased[p] = 1;
+  else
+    for (uint32_t p = end; p < W; ++p) erased[p] = 1;
+  const std::vector<uint32_t> L = erasure_logs(erased, W);
+  std::vector<std::vector<uint32_t>> M1, M2;
+  mixing_matrices(m, cs, W, M1, M2);
+
+  CodecJobBig& j = pj.job;
+  j = CodecJobBig{};
+  j.symbol_size = sp.symbol_size;
+  j.n_pairs = (sp.symbol_size + 3) / 4;
+  j.shared_in = 0;
+  pj.C = int(cs);
+  // input blocks with at least one present position
+  std::vector<int> in_blocks, out_blocks;
+  for (int b = 0; b < m; ++b) {
+    bool any = false;
+    for (uint32_t p = 0; p < cs; ++p) any |= src_at[b * cs + p] >= 0;
+    if (any) in_blocks.push_back(b);
+  }
+  for (int b = 0; b < m; ++b) {
+    bool any = false;
+    for (uint32_t i = 0; i < K; ++i)
+      any |= sp.present[i] < 0 && opos(i) / cs == uint32_t(b);
+    if (any) out_blocks.push_back(b);
+  }
+  if (in_blocks.size() > size_t(max_blocks(int(cs))) || out_blocks.size() > size_t(max_blocks(int(cs))))
+    return fail(RS2_E_UNSUPPORTED, "too many decode blocks");
+  pj.mix_stride = std::max(in_blocks.size(), out_blocks.size()) > size_t(kMaxBlocks) ? kMaxBlocksBig
+                                                                                     : kMaxBlocks;
+  // Block pair (rs2_codec.hip load_ifft, CodecJob::pair_p): with one output block, an input
+  // block Q mixed with M1 = 0 (coefficient 1 once folded below) and another block P whose
+  // active waves (ceil(count / ppw)) fit the workgroup together run their loads and in-wave
+  // IFFT layers in one pass.  Q moves to the end of the input list (the kernel's convention).
+  const int ppw = std::min<int>(int(cs), kPpwTarget), nw = int(cs) / ppw;
+  auto block_waves = [&](int b) {
+    int count = 0;
+    for (uint32_t p = 0; p < cs; ++p)
+      if (src_at[b * cs + p] >= 0) count = int(p) + 1;
+    return (count + ppw - 1) / ppw;
+  };
+  int pair_p = -1, pair_nw = 0;
+  static const bool no_pair = env_int("RS2_PAIR", 1) == 0;  // A/B knob: 0 = never pair
+  if (!no_pair && nw > 1 && out_blocks.size() == 1) {
+    const int o = out_blocks[0];
+    for (size_t qi = 0; qi < in_blocks.size() && pair_p < 0; ++qi) {
+      const int q = in_blocks[qi];
+      if (M1[o][q] != 0 || M2[o][q] == 0) continue;
+      for (size_t pi = 0; pi < in_blocks.size(); ++pi) {
+        const int p = in_blocks[pi];
+        if (p == q || (M1[o][p] == 0 && M2[o][p] == 0)) continue;
+        if (block_waves(p) + block_waves(q) > nw) continue;
+        in_blocks.erase(in_blocks.begin() + qi);
+        in_blocks.push_back(q);
+        pair_p = int(std::find(in_blocks.begin(), in_blocks.end(), p) - in_blocks.begin());
+        pair_nw = block_waves(p);
+        break;
+      }
+    }
+  }
+  std::fill(std::begin(j.pair_p), std::end(j.pair_p), int8_t(-1));
+  std::fill(std::begin(j.pair_q), std::end(j.pair_q), int8_t(-1));
+  std::fill(std::begin(j.pair_nw), std::end(j.pair_nw), int8_t(0));
+  if (pair_p >= 0) {
+    j.pair_p[0] = int8_t(pair_p);
+    j.pair_q[0] = int8_t(in_blocks.size() - 1);
+    j.pair_nw[0] = int8_t(pair_nw);
+  }
+  j.n_in = int(in_blocks.size());
+  j.n_out = int(out_blocks.size());
+  pj.n_z = j.n_out;
+  pj.offs.assign(size_t(j.n_in + j.n_out) * cs, -1);
+  pj.pre_logs.assign(size_t(j.n_out) * j.n_in * cs, 0);
+  pj.post_logs.assign(size_t(j.n_out) * cs, 0);
+  pj.has_pre = pj.has_post = true;
+  for (int bi = 0; bi < j.n_in; ++bi) {
+    const int b = in_blocks[bi];
+    InBlock& ib = j.in[bi];
+    ib.base = sp.src_base;
+    ib.line_stride = sp.src_ls;
+    int count = 0;
+    for (uint32_t p = 0; p < cs; ++p) {
+      const uint32_t gp = b * cs + p;
+      if (src_at[gp] >= 0) {
+        pj.offs[pj.in_off(bi) + p] = src_at[gp];
+        count = int(p) + 1;
+      }
+    }
+    ib.count = count;
+    pj.in_sd.push_back(int(b * cs));
+    pj.in_first.push_back(uint32_t(b * cs));
+  }
+  if (sp.copy_present) {
+    pj.copy_base = sp.dst_base;
+    pj.copy_ls = sp.dst_ls;
+    pj.copy_limit = sp.dst_limit;
+    pj.copy_offs.assign(size_t(j.n_in) * cs, -1);
+    for (int bi = 0; bi < j.n_in; ++bi)
+      for (uint32_t i = 0; i < K; ++i)
+        if (sp.present[i] >= 0 && opos(i) / cs == uint32_t(in_blocks[bi]))
+          pj.copy_offs[size_t(bi) * cs + opos(i) % cs] = sp.dst[i];
+  }
+  for (int oi = 0; oi < j.n_out; ++oi) {
+    const int o = out_blocks[oi];
+    OutBlock& ob = j.out[oi];
+    ob.base = sp.dst_base;
+    ob.line_stride = sp.dst_ls;
+    ob.limit = sp.dst_limit;
+    int trunc = 0;
+    for (uint32_t i = 0; i < K; ++i) {
+      if (sp.present[i] >= 0) continue;
+      const uint32_t gp = opos(i);
+      if (gp / cs != uint32_t(o)) continue;
+      const uint32_t p = gp % cs;
+      pj.offs[pj.out_off(oi) + p] = sp.dst[i];
+      pj.post_logs[size_t(oi) * cs + p] = uint16_t(kModulus - L[gp]);  // 65535 == times one
+      trunc = std::max(trunc, int(p) + 1);
+    }
+    ob.trunc = trunc;
+    pj.out_sd.push_back(int(o * cs));
+    // Fold one mixing coefficient of every input block into its pre-multiplier (the decoder
+    // scales each loaded symbol by exp(L[p]) anyway).  With f = M1 (or M2 when M1 is zero) and
+    // X'_b = IFFT_b(f * exp(L) * in_b) = f * X_b (IFFT and Dw are GF-linear):
+    //   M1 Dw(X_b) + M2 X_b = Dw(X'_b) + (M2 / M1) X'_b
+    // so the block costs at most one table multiply per position instead of three.  Each output
+    // block folds its own coefficients, hence per-output pre tables (CodecJob::pre_z_stride).
+    const Gf& g = gf();
+    Coef c1(j.n_in), c2(j.n_in);
+    for (int bi = 0; bi < j.n_in; ++bi) {
+      const int b = in_blocks[bi];
+      c1[bi] = M1[o][b];
+      c2[bi] = M2[o][b];
+      const uint32_t f = c1[bi] ? c1[bi] : c2[bi];
+      if (f == 0) continue;  // this output does not use the block
+      const uint32_t lf = g.log[f];
+      if (c1[bi]) {
+        c2[bi] = c2[bi] ? g.mul(c2[bi], kModulus - lf) : 0u;
+        c1[bi] = 1;
+      } else {
+        c2[bi] = 1;
+      }
+      uint16_t* pl = pj.pre_logs.data() + (size_t(oi) * j.n_in + bi) * cs;
+      for (uint32_t p = 0; p < cs; ++p)
+        if (src_at[b * cs + p] >= 0) pl[p] = uint16_t(Gf::add_mod(L[b * cs + p], lf));
+    }
+    set_mixing(pj, oi, &c1, c2);
+  }
+  return RS2_OK;
+}
+
+}  // namespace rs2

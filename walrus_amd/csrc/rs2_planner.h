@@ -1,0 +1,270 @@
+// The codec job planner: GF(2^16) constant tables and the plans of encode / decode jobs, i.e.
+// every offset, table and mixing coefficient the codec kernels consume.  Pure host arithmetic:
+// this unit includes no device runtime header and calls no device function, so it builds with a
+// plain host compiler and is checked without a GPU (tests/capi/planner_check.cpp).
+// rs2_engine.cpp uploads a planned job's arrays (bind_job) and launches it.
+#pragma once
+#include <algorithm>
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "../../include/walrus_rs2.h"
+#include "rs2_device.h"
+
+namespace rs2 {
+
+// ---------------------------------------------------------------------------------------------
+// errors: the calling thread's last message (rs2_last_error).  The string itself stays local to
+// rs2_planner.cpp: a thread_local std::string declared extern would make the library export its
+// initialisation function, a name outside the prefixes the ABI allows.
+// ---------------------------------------------------------------------------------------------
+int fail(int code, const std::string& msg);
+const char* last_error();
+
+// Return the first failing status of a chain of engine calls.
+#define RS2_TRY(expr)                   \
+  do {                                  \
+    int rc_ = (expr);                   \
+    if (rc_ != RS2_OK) return rc_;      \
+  } while (0)
+
+// An integer A/B knob from the environment (`dflt` when unset).  Callers keep the value in a
+// function-local static, so every knob is read once per process.
+int env_int(const char* name, int dflt);
+
+// ---------------------------------------------------------------------------------------------
+// GF(2^16) tables (reed-solomon-simd engine/tables.rs restated; see oracle/rs2_oracle.py)
+// ---------------------------------------------------------------------------------------------
+constexpr uint32_t kOrder = 65536, kModulus = 65535;
+
+struct Gf {
+  std::vector<uint16_t> exp, log, skew;
+  Gf();
+  static uint32_t add_mod(uint32_t a, uint32_t b) {
+    const uint32_t s = a + b;
+    return (s + (s >> 16)) & 0xFFFFu;
+  }
+  // x * exp(log_m) with the generic semantics (log_m == 65535 is log 0, i.e. times one)
+  uint32_t mul(uint32_t x, uint32_t log_m) const {
+    return x == 0 ? 0 : exp[add_mod(log[x], log_m)];
+  }
+};
+
+const Gf& gf();
+
+// 256-byte multiplier table of exp(log_m), one sub-table per bit field of the operand
+// (rs2_device.h kTabU16): out[f] = f * m (bits 0-5, 64 entries), out[64 + f] = (f << 6) * m
+// (bits 6-10), out[96 + f] = (f << 11) * m (bits 11-15).  Multiplication by a constant is
+// GF(2)-linear, so x * m is the XOR of the three entries its fields select.  Each sub-table
+// spans at most 32 dwords, so a wave's lookups into it never bank-conflict.
+// fft_zero: a butterfly constant log_m == 65535 means multiply by ZERO (engine special case).
+void nib_table(uint32_t log_m, bool fft_zero, uint16_t* out);
+
+// Constant tables of a size-C transform with skew offset sd, in kernel consumption order
+// (rs2_codec.hip: A slots PPW - PPW/d + g per wave, then B slots NW - C/d + g).
+std::vector<uint16_t> sd_stream(int C, int sd, int ppw = kPpwTarget);
+
+// 1 when group 0 of every cross-wave layer of a size-C transform with skew offset sd multiplies
+// by zero (skew[d + sd - 1] is log 0, which holds for sd = 0): the kernel then skips those
+// multiplies (rs2_codec.hip phase_b).
+int group0_zero(int C, int sd, int ppw = kPpwTarget);
+
+uint32_t next_pow2(uint32_t x);
+// reed-solomon-simd DefaultRate: high rate iff pow2(recovery) <= pow2(original)
+bool use_high_rate(uint32_t k, uint32_t r);
+bool rate_supported(uint32_t k, uint32_t r);
+
+// Largest transform block held on chip.  RS2_BLOCK_MAX (a power of two <= kMaxC) lowers it for
+// experiments: smaller blocks mean smaller workgroups (C/32 waves) and more of them per CU, at
+// the price of more block-level mixing.
+uint32_t block_max();
+void set_block_max(uint32_t max_block);  // rs2_set_block_limit: overrides RS2_BLOCK_MAX
+
+// Blocks a job of block size C may have: jobs beyond kMaxBlocks run from device memory
+// (CodecJobBig), for which only C = 512 kernels are built.
+int max_blocks(int C);
+
+// ---------------------------------------------------------------------------------------------
+// codec job planning
+// ---------------------------------------------------------------------------------------------
+// A planned job: the CodecJob plus host copies of its per-position offset arrays.  Pointer
+// fields that reference per-job device arrays are filled by bind_job (rs2_engine.cpp) once those
+// are uploaded.
+struct PlannedJob {
+  CodecJobBig job{};                 // narrowed to CodecJob at launch when it has <= 64 blocks
+  int mix_stride = kMaxBlocks;       // mixing-table row length (kMaxBlocksBig for big jobs)
+  int C = 1;
+  int n_z = 1;
+  int mode = kModeRows;              // kernel variant (rs2_device.h CodecMode)
+  int ppw = kPpwTarget;              // positions per wave of the variant's table stream
+  std::vector<int64_t> offs;         // (n_in + n_out) blocks x C
+  std::vector<int64_t> copy_offs;    // n_in blocks x C fused copy-out offsets, or empty
+  uint8_t* copy_base = nullptr;
+  int64_t copy_ls = 0, copy_limit = INT64_MAX;
+  std::vector<uint16_t> pre_logs;    // per in-block C logs (decode), empty if none
+  std::vector<uint16_t> post_logs;   // per out-block C logs (decode)
+  std::vector<uint16_t> mix;         // mix_stride^2 * 2 tables (block mixing tables)
+  std::vector<uint16_t> logs;        // pre ++ post logs as uploaded (kept alive for async H2D)
+  std::vector<int> in_sd, out_sd;    // skew offset of each block's in-block transform
+  std::vector<uint32_t> in_first;    // code position (source index) of each in-block's slot 0
+  bool has_pre = false, has_post = false, has_mix = false;
+
+  size_t in_off(int b) const { return size_t(b) * C; }
+  size_t out_off(int o) const { return size_t(job.n_in + o) * C; }
+};
+
+// Symbolic block-level transform layers.  A "slot" is one block of C positions; its value is a
+// linear combination (GF(2^16) coefficients) of the jobs' input blocks after their in-block
+// IFFTs.  Layers whose butterfly distance is >= C have one constant per block pair, so on whole
+// blocks they are scalar operations (same constants as the element-level transforms).
+using Coef = std::vector<uint32_t>;
+void coef_xor(Coef& y, const Coef& x);
+// IFFT layers d = C .. span/2 of a size-`span` transform with skew offset sd
+void sym_ifft_top(std::vector<Coef>& V, uint32_t C, uint32_t span, uint32_t sd);
+// FFT layers d = span/2 .. C of a size-`span` transform with skew offset sd
+void sym_fft_top(std::vector<Coef>& V, uint32_t C, uint32_t span, uint32_t sd);
+// Mixing kinds and tables of output block oi from its coefficient vectors (M1 may be empty).
+void set_mixing(PlannedJob& pj, int oi, const Coef* m1, const Coef& m2);
+
+// Encode K source symbols into R recovery symbols for every line (reed-solomon-simd encoders,
+// oracle rs_encode_elems).  src(i) / dst(j): byte offsets relative to the base (before the line
+// stride).  Transforms larger than the block size C are split into blocks of C with the
+// top layers applied as block mixing.
+template <class SrcF, class DstF>
+int plan_encode(uint32_t K, uint32_t R, int symbol_size, const uint8_t* src_base,
+                int64_t src_ls, SrcF src, uint8_t* dst_base, int64_t dst_ls, DstF dst,
+                int64_t dst_limit, PlannedJob& pj) {
+  if (!rate_supported(K, R)) return fail(RS2_E_INCOMPATIBLE_PARAMETERS, "unsupported shard count");
+  CodecJobBig& j = pj.job;
+  j = CodecJobBig{};
+  pj.mix.clear();
+  pj.has_mix = false;
+  pj.in_sd.clear();
+  pj.out_sd.clear();
+  pj.in_first.clear();
+  j.symbol_size = symbol_size;
+  j.n_pairs = (symbol_size + 3) / 4;
+  const bool high = use_high_rate(K, R);
+  const uint32_t cs = high ? next_pow2(R) : next_pow2(K);
+  const uint32_t C = std::min(cs, block_max());
+  const uint32_t nb = cs / C;
+  pj.C = int(C);
+  // input blocks
+  struct Blk { uint32_t first, count; int sd; };
+  std::vector<Blk> in, out;
+  if (high) {
+    for (uint32_t k = 0; k * cs < K; ++k)
+      for (uint32_t b = 0; b < nb && k * cs + b * C < K; ++b)
+        in.push_back({k * cs + b * C, std::min(C, K - k * cs - b * C), int((k + 1) * cs + b * C)});
+  } else {
+    for (uint32_t b = 0; b < nb && b * C < K; ++b)
+      in.push_back({b * C, std::min(C, K - b * C), int(b * C)});
+  }
+  if (in.size() > size_t(max_blocks(C))) return fail(RS2_E_UNSUPPORTED, "too many input blocks");
+  j.n_in = int(in.size());
+  // block mixing: coefficient vectors of each output block's pre-FFT slot
+  std::vector<Coef> outs;
+  const size_t ni = in.size();
+  if (high) {
+    std::vector<Coef> acc(nb, Coef(ni, 0));
+    size_t bi = 0;
+    for (uint32_t k = 0; k * cs < K; ++k) {
+      std::vector<Coef> V(nb, Coef(ni, 0));
+      for (uint32_t b = 0; b < nb && k * cs + b * C < K; ++b) V[b][bi++] = 1;
+      sym_ifft_top(V, C, cs, (k + 1) * cs);
+      for (uint32_t b = 0; b < nb; ++b) coef_xor(acc[b], V[b]);
+    }
+    sym_fft_top(acc, C, cs, 0);
+    for (uint32_t b = 0; b < nb && b * C < R; ++b) {
+      out.push_back({b * C, std::min(C, R - b * C), int(b * C)});
+      outs.push_back(acc[b]);
+    }
+  } else {
+    std::vector<Coef> V(nb, Coef(ni, 0));
+    for (size_t bi = 0; bi < ni; ++bi) V[bi][bi] = 1;
+    sym_ifft_top(V, C, cs, 0);
+    for (uint32_t k = 0; k * cs < R; ++k) {
+      std::vector<Coef> Wk = V;
+      sym_fft_top(Wk, C, cs, (k + 1) * cs);
+      for (uint32_t b = 0; b < nb && k * cs + b * C < R; ++b) {
+        out.push_back({k * cs + b * C, std::min(C, R - k * cs - b * C), int((k + 1) * cs + b * C)});
+        outs.push_back(Wk[b]);
+      }
+    }
+  }
+  if (out.size() > size_t(max_blocks(C))) return fail(RS2_E_UNSUPPORTED, "too many output blocks");
+  j.n_out = int(out.size());
+  pj.mix_stride = std::max(in.size(), out.size()) > size_t(kMaxBlocks) ? kMaxBlocksBig : kMaxBlocks;
+  // one shared IFFT when a single input block feeds every output unmixed (low rate, C == cs)
+  j.shared_in = (!high && nb == 1) ? 1 : 0;
+  pj.n_z = j.shared_in ? 1 : j.n_out;
+  pj.mode = j.shared_in ? kModeCols : kModeRows;
+  pj.ppw = kPpwTarget;
+  pj.copy_offs.clear();
+  pj.offs.assign(size_t(j.n_in + j.n_out) * C, -1);
+  for (int bi = 0; bi < j.n_in; ++bi) {
+    InBlock& ib = j.in[bi];
+    ib.base = src_base;
+    ib.line_stride = src_ls;
+    ib.count = int(in[bi].count);
+    for (uint32_t p = 0; p < in[bi].count; ++p) pj.offs[pj.in_off(bi) + p] = src(in[bi].first + p);
+    pj.in_sd.push_back(in[bi].sd);
+    pj.in_first.push_back(in[bi].first);
+  }
+  for (int oi = 0; oi < j.n_out; ++oi) {
+    OutBlock& ob = j.out[oi];
+    ob.base = dst_base;
+    ob.line_stride = dst_ls;
+    ob.trunc = int(out[oi].count);
+    ob.limit = dst_limit;
+    for (uint32_t p = 0; p < out[oi].count; ++p) pj.offs[pj.out_off(oi) + p] = dst(out[oi].first + p);
+    pj.out_sd.push_back(out[oi].sd);
+    if (!j.shared_in) set_mixing(pj, oi, nullptr, outs[oi]);
+  }
+  return RS2_OK;
+}
+
+// Fused copy-out of a job's loaded source symbols: source index q (a loaded position) is
+// also written to base + line*ls + f(q) (f(q) < 0: not copied).  Needs whole-dword symbol
+// I/O (s >= 4); the caller keeps a separate copy pass otherwise.
+template <class F>
+void set_copy(PlannedJob& pj, uint8_t* base, int64_t ls, int64_t limit, F f) {
+  pj.copy_base = base;
+  pj.copy_ls = ls;
+  pj.copy_limit = limit;
+  pj.copy_offs.assign(size_t(pj.job.n_in) * pj.C, -1);
+  for (int b = 0; b < pj.job.n_in; ++b)
+    for (int p = 0; p < pj.job.in[b].count; ++p)
+      pj.copy_offs[size_t(b) * pj.C + p] = f(pj.in_first[b] + uint32_t(p));
+}
+
+// True when every in-block that carries copy positions is loaded by at least one output
+// block (the kernel skips in-blocks whose mixing coefficients are all zero); otherwise the
+// copy is dropped and the caller falls back to a separate copy pass.
+bool copy_covered(PlannedJob& pj);
+
+// The last planning step, after plan_encode / plan_decode (and set_copy / copy_covered): the
+// job's flattened lane space (CodecScalars::pairs_span, from its largest line stride) and the
+// fused copy-out offsets appended to the position offsets, so both go up in one upload.
+// Returns the number of position offsets, i.e. where the copy offsets start in pj.offs.
+size_t finish_plan(PlannedJob& pj);
+
+// Symbols of a 1D decode: present[q] = source offset (or -1) for shard index q < n;
+// dst(i) = destination offset of source symbol i (only erased originals are written here).
+struct DecodeSpec {
+  uint32_t K = 0, R = 0;
+  std::vector<int64_t> present;        // size K + R
+  const uint8_t* src_base = nullptr;
+  int64_t src_ls = 0;
+  uint8_t* dst_base = nullptr;
+  int64_t dst_ls = 0;
+  std::vector<int64_t> dst;            // size K: destination offset of source symbol i
+  int64_t dst_limit = INT64_MAX;
+  int symbol_size = 0;
+  bool copy_present = false;           // also write present originals to dst (fused copy)
+};
+
+int plan_decode(const DecodeSpec& sp, PlannedJob& pj);
+
+}  // namespace rs2
