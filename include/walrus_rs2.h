@@ -287,6 +287,39 @@ int rs2_decode_device_async(rs2_plan* plan, int axis, uint32_t count, const uint
                             const void* d_slivers_base, const uint64_t* sliver_off,
                             void* d_blob_out, void* stream);
 
+/* ---- decode batches -------------------------------------------------------------------------
+ * Many blobs of the plan's symbol size decoded together, each from its own set of slivers (an
+ * aggregator's or client's read of many small blobs, each a BlobDecoder::decode,
+ * blob_encoding.rs:888-993): the blobs' decode jobs are planned on the host's worker threads and
+ * run as one launch per chunk of a few hundred blobs.  A blob whose decode does not fit a batch
+ * job (no erased original, a 2-byte symbol, more than 8 transform blocks) is decoded like
+ * rs2_decode_device_async on the same stream, so the call serves every n_shards.
+ *
+ * Blob b: counts[b] slivers of `axis`, their indices / byte offsets consecutive in sliver_idx /
+ * sliver_off (relative to d_slivers_base); length blob_lens[b] (NULL: the plan's), which must
+ * give the plan's symbol size; decoded to d_blobs_out + b*out_stride, nothing at or past its
+ * length written, the stride padding not written.  Per-blob rules as rs2_decode_device_async.
+ * status_out NULL: the first failing blob's code is returned and nothing is enqueued;
+ * non-NULL: failing blobs get their code and are skipped, the rest are decoded, RS2_OK.
+ * n_blobs 0: RS2_OK, nothing enqueued.  At most 65535 blobs.  Alignment as the decode's
+ * (d_slivers_base, every offset, d_blobs_out and out_stride 2-byte aligned; a misaligned base
+ * or stride fails the call, a misaligned offset its blob). */
+int rs2_decode_batch_device_async(rs2_plan* plan, int axis, uint32_t n_blobs,
+                                  const uint64_t* blob_lens, const uint32_t* counts,
+                                  const uint16_t* sliver_idx, const void* d_slivers_base,
+                                  const uint64_t* sliver_off, void* d_blobs_out,
+                                  uint64_t out_stride, int* status_out, void* stream);
+/* Host form (blocking): slivers[] / sliver_len[] / sliver_symbol_size[] concatenated likewise
+ * (per-sliver rules as rs2_decode_blob), blobs_out[b] receives blob b (blob_lens[b] bytes). */
+int rs2_decode_batch(rs2_plan* plan, int axis, uint32_t n_blobs, const uint64_t* blob_lens,
+                     const uint32_t* counts, const uint16_t* sliver_idx,
+                     const uint8_t* const* slivers, const uint64_t* sliver_len,
+                     const uint16_t* sliver_symbol_size, uint8_t* const* blobs_out,
+                     int* status_out);
+/* Process-wide counters, stats_out[3]: batched launches, blobs decoded inside them, blobs that
+ * took the per-blob path.  No reference counterpart. */
+int rs2_decode_batch_stats(uint64_t* stats_out);
+
 /* EncodingFactory::decode_and_verify (config.rs:613-658) on device-resident slivers (as
  * rs2_decode_device_async) into the device buffer d_blob_out (blob_len bytes); `hashes` /
  * `blob_id` are host copies of the metadata.  The checks are those of rs2_decode_and_verify and

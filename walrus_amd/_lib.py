@@ -92,6 +92,15 @@ SIGNATURES = {
                                                      ctypes.c_uint16, _vp, _vp, _vp, _vp, _vp]),
     "rs2_decode_device_async": (
         ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_uint32, _u16p, _vp, _u64p, _vp, _vp]),
+    "rs2_decode_batch_device_async": (
+        ctypes.c_int,
+        [_vp, ctypes.c_int, ctypes.c_uint32, _u64p, ctypes.POINTER(ctypes.c_uint32), _u16p, _vp,
+         _u64p, _vp, ctypes.c_uint64, ctypes.POINTER(ctypes.c_int), _vp]),
+    "rs2_decode_batch": (
+        ctypes.c_int,
+        [_vp, ctypes.c_int, ctypes.c_uint32, _u64p, ctypes.POINTER(ctypes.c_uint32), _u16p,
+         ctypes.POINTER(_vp), _u64p, _u16p, ctypes.POINTER(_vp), ctypes.POINTER(ctypes.c_int)]),
+    "rs2_decode_batch_stats": (ctypes.c_int, [ctypes.POINTER(ctypes.c_uint64)]),
     "rs2_decode_and_verify_device": (
         ctypes.c_int,
         [_vp, ctypes.c_int, ctypes.c_uint32, _u16p, _vp, _u64p, _vp, _vp, ctypes.c_int, _vp, _vp]),

@@ -749,8 +749,10 @@ __device__ __forceinline__ void mul_present(uint32_t (&X)[PPW], uint32_t pw, uin
 //   kModeRows    mixing path, no per-position multipliers (high-rate encode)
 //   kModeCols    shared-input path: one IFFT, every output block an FFT of it (low rate)
 //   kModeDecode  mixing path with formal derivative and per-position pre/post multipliers
-template <int C, int MODE, bool kPersist = false, class Job = CodecJob>
-__device__ __forceinline__ void codec_body(const Job& job) {
+// kTileArg: the caller names the workgroup's tile (`tile_arg`; the decode batch kernel, whose
+// tile -> blob map picks the job), instead of the launch's XCD order over gridDim.x
+template <int C, int MODE, bool kPersist = false, class Job = CodecJob, bool kTileArg = false>
+__device__ __forceinline__ void codec_body(const Job& job, uint32_t tile_arg = 0) {
   using G = Geo<C>;
   constexpr int PPW = G::PPW;
   // the decode kernel is instantiated as kDecodeRt: decode plus a (never taken) runtime
@@ -1328,6 +1330,8 @@ __device__ __forceinline__ void codec_body(const Job& job) {
     const uint32_t t_end = x_start + q_t + (xcd < r_t ? 1u : 0u);
 #pragma clang loop unroll(disable)
     for (uint32_t t = x_start + k_in_xcd; t < t_end; t += nx) tile_body(t);
+  } else if constexpr (kTileArg) {
+    tile_body(tile_arg);
   } else {
     tile_body(xcd_tile(blockIdx.x, gridDim.x));
   }
@@ -1815,6 +1819,20 @@ __global__ void __launch_bounds__(Geo<C>::THREADS, 4)
   codec_body<C, 3, false, CodecJobBig>(*job);
 }
 
+// Decode batch: one job per blob in a device table, every blob `tiles_per_blob` tiles of the
+// grid (XCD order over the whole launch, then tile -> blob as the encode batch maps it).
+// grid.z is the chunk's largest n_out; a workgroup past its own blob's n_out leaves before any
+// barrier or LDS use (blockIdx and the job are workgroup-uniform, so every wave takes the exit).
+template <int C>
+__global__ void __launch_bounds__(Geo<C>::THREADS, 4)
+    rs2_decode_batch_kernel(const CodecJobBatch* __restrict__ jobs, int tiles_per_blob) {
+  const uint32_t tile = xcd_tile(blockIdx.x, gridDim.x);
+  const uint32_t blob = tile / uint32_t(tiles_per_blob);
+  const CodecJobBatch& job = jobs[blob];
+  if (int(blockIdx.z) >= job.n_out) return;
+  codec_body<C, 3, false, CodecJobBatch, true>(job, tile - blob * uint32_t(tiles_per_blob));
+}
+
 }  // namespace rs2
 
 #define RS2_CAT2(a, b) a##b
@@ -1854,6 +1872,20 @@ extern "C" hipError_t RS2_CAT(rs2k_launch_codec_, RS2_C)(const rs2::CodecJob* jo
     default:
       return hipErrorInvalidValue;
   }
+  return hipGetLastError();
+}
+
+// A decode batch: n_blobs jobs at d_jobs, tiles_per_blob tiles each, n_z = the largest n_out
+extern "C" hipError_t RS2_CAT(rs2k_launch_decode_batch_, RS2_C)(const rs2::CodecJobBatch* d_jobs,
+                                                                int n_blobs, int tiles_per_blob,
+                                                                int n_z, hipStream_t stream) {
+  if (n_blobs < 1 || tiles_per_blob < 1 || n_z < 1 || n_z > rs2::kBatchBlocks ||
+      int64_t(n_blobs) * tiles_per_blob > 0x7FFFFFFF)
+    return hipErrorInvalidValue;
+  const dim3 grid(uint32_t(n_blobs) * uint32_t(tiles_per_blob), 1, n_z);
+  const dim3 block(rs2::Geo<RS2_C>::THREADS);
+  hipLaunchKernelGGL(rs2::rs2_decode_batch_kernel<RS2_C>, grid, block, 0, stream, d_jobs,
+                     tiles_per_blob);
   return hipGetLastError();
 }
 

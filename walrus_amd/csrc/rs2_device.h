@@ -11,6 +11,10 @@ constexpr int kMaxBlocks = 64;  // input / output blocks of a job passed by valu
 // device memory and reach the kernel by pointer (CodecJobBig, C = 512 only); their block arrays
 // and mixing kinds would not fit the kernel argument.
 constexpr int kMaxBlocksBig = 128;
+// Jobs of a decode batch (one job per blob, a table of them in device memory, CodecJobBatch):
+// 8 blocks cover every decode up to n_shards of about 3100 at C = 512 and n_shards = 1000 at a
+// block limit of 256, and keep a job near 1.5 KiB, so a few hundred fit one upload slot.
+constexpr int kBatchBlocks = 8;
 constexpr int kMaxC = 512;      // largest transform block held on chip (positions)
 constexpr int kTabU16 = 128;    // one multiplier table: u16 sub-tables of 64 + 32 + 32 entries
                                 // for operand bits 0-5, 6-10, 11-15 (rs2_planner.cpp nib_table)
@@ -133,10 +137,15 @@ struct CodecJobT : CodecScalars {
 };
 using CodecJob = CodecJobT<kMaxBlocks>;
 using CodecJobBig = CodecJobT<kMaxBlocksBig>;
+// One blob's job in a decode batch's device job table (rs2_decode_batch_kernel): every pointer,
+// the absolute bases of that blob's buffers included, is its own; tiles_per_blob is 0.
+using CodecJobBatch = CodecJobT<kBatchBlocks>;
 static_assert(sizeof(CodecJob) ==
                   (sizeof(CodecScalars) + CodecJob::kArrayBytes + 7) / 8 * 8 &&
               sizeof(CodecJobBig) ==
-                  (sizeof(CodecScalars) + CodecJobBig::kArrayBytes + 7) / 8 * 8,
+                  (sizeof(CodecScalars) + CodecJobBig::kArrayBytes + 7) / 8 * 8 &&
+              sizeof(CodecJobBatch) ==
+                  (sizeof(CodecScalars) + CodecJobBatch::kArrayBytes + 7) / 8 * 8,
               "a CodecJobT field outside CodecScalars and kArrayBytes: narrow_job would drop it");
 constexpr int kTileCtrWords = 16;
 constexpr int kStamps = 64;

@@ -1023,6 +1023,25 @@ struct DecodeSlot {
   }
 };
 
+// One chunk of a decode batch: the concatenated position (and copy) offsets, multiplier logs,
+// per-position tables, mixing tables and the job table of its blobs.  A plan holds two, taken
+// in turn; a slot is rewritten only after `done`, the event of its last launch.
+struct BatchDecodeSlot {
+  DevBuf offs, logs, tabs, mix, jobs;
+  hipEvent_t done = nullptr;
+  BatchDecodeSlot() = default;
+  BatchDecodeSlot(const BatchDecodeSlot&) = delete;
+  BatchDecodeSlot& operator=(const BatchDecodeSlot&) = delete;
+  ~BatchDecodeSlot() {
+    if (done) (void)hipEventDestroy(done);
+  }
+};
+// Jobs of one chunk: what fits one upload slot; and the per-position tables of one chunk
+// (256 bytes per multiplier log), so the device memory of a call does not grow with n_blobs.
+constexpr size_t kBatchChunkJobs = UploadSlots::kSlotBytes / sizeof(CodecJobBatch);
+constexpr size_t kBatchTableBytes = size_t(256) << 20;
+std::atomic<uint64_t> g_batch_launches{0}, g_batch_blobs{0}, g_batch_single{0};
+
 constexpr int kMerkleMaxLeaves = 4096;  // rs2_hash.hip kMerkleMax (one-wave / one-WG trees)
 // n_shards above that: the trees' level L (the first with ceil(n / 2^L) <= 4,096 nodes) is
 // folded straight from the leaves by a kernel of its own into a scratch buffer
@@ -1345,6 +1364,11 @@ struct rs2_plan {
   // decode (two slots so back-to-back async decodes never overwrite live arrays)
   DecodeSlot dec[2];
   int dec_slot = 0;
+  // decode batches (rs2_decode_batch_*): the device arrays of one chunk's jobs, two slots taken
+  // in turn like `dec`; the host-buffer form's device slivers and blobs
+  BatchDecodeSlot dbatch[2];
+  int dbatch_slot = 0;
+  DevBuf dbatch_in, dbatch_out;
   // host-buffer API: pinned staging ring, a copy stream for the sliver D2H (released by a split
   // encode as soon as the primary slivers are final), row gather offsets of the Default check
   Stager* stage = nullptr;  // the pinned ring leased for the host-buffer call in progress
@@ -1936,13 +1960,15 @@ int run_decode(Context* ctx, DecodeSlot (&slots)[2], int& cursor, DecodeSpec& sp
   return RS2_OK;
 }
 
-// Decode from chosen device slivers: sliver i at base + off[i].
-int decode_device(rs2_plan* p, int axis, const std::vector<std::pair<uint16_t, uint32_t>>& chosen,
-                  const uint8_t* base, const uint64_t* off, uint8_t* d_out, hipStream_t st) {
+// The decode of a blob of `blob_len` bytes from chosen device slivers (sliver i at base + off[i])
+// into d_out, and the key that names the job in a decode slot.
+void blob_decode_spec(const rs2_plan* p, int axis,
+                      const std::vector<std::pair<uint16_t, uint32_t>>& chosen, const uint8_t* base,
+                      const uint64_t* off, uint8_t* d_out, uint64_t blob_len, DecodeSpec& sp,
+                      std::vector<int64_t>& key) {
   const int64_t s = p->s, n = p->n, kp = p->kp, ks = p->ks;
   const bool prim = axis == RS2_AXIS_PRIMARY;
   const uint32_t K = prim ? uint32_t(kp) : uint32_t(ks);
-  DecodeSpec sp;
   sp.K = K;
   sp.R = uint32_t(n) - K;
   sp.symbol_size = int(s);
@@ -1950,22 +1976,40 @@ int decode_device(rs2_plan* p, int axis, const std::vector<std::pair<uint16_t, u
   sp.src_base = base;
   sp.src_ls = s;  // line = column c (primary) / row r (secondary): symbol c of the sliver
   sp.dst_base = d_out;
-  sp.dst_limit = int64_t(p->blob_len);
+  sp.dst_limit = int64_t(blob_len);
   sp.dst.resize(K);
   for (uint32_t i = 0; i < K; ++i) sp.dst[i] = prim ? int64_t(i) * ks * s : int64_t(i) * s;
   sp.dst_ls = prim ? s : ks * s;
   for (auto& c : chosen) sp.present[c.first] = int64_t(off[c.second]);
-  std::vector<int64_t> key;
+  key.clear();
   key.reserve(size_t(n) + 5);
   key.push_back(axis);
   key.push_back(int64_t(block_max()));
-  key.push_back(int64_t(p->blob_len));  // sp.dst_limit: rebind keeps the plan, not the limit
+  key.push_back(int64_t(blob_len));  // sp.dst_limit: rebind keeps the plan, not the limit
   key.push_back(int64_t(reinterpret_cast<uintptr_t>(base)));
   key.push_back(int64_t(reinterpret_cast<uintptr_t>(d_out)));
   key.insert(key.end(), sp.present.begin(), sp.present.end());
+}
+
+bool decode_may_fuse() {
   static const bool no_fuse = env_int("RS2_DEC_NOFUSE", 0) != 0;  // A/B knob: RS2_DEC_NOFUSE=1
-  const int lines = prim ? int(ks) : int(kp);
-  return run_decode(p->ctx, p->dec, p->dec_slot, sp, std::move(key), !no_fuse, lines, p, st);
+  return !no_fuse;
+}
+
+// Decode from chosen device slivers: sliver i at base + off[i].
+int decode_device(rs2_plan* p, int axis, const std::vector<std::pair<uint16_t, uint32_t>>& chosen,
+                  const uint8_t* base, const uint64_t* off, uint8_t* d_out, hipStream_t st,
+                  uint64_t blob_len) {
+  DecodeSpec sp;
+  std::vector<int64_t> key;
+  blob_decode_spec(p, axis, chosen, base, off, d_out, blob_len, sp, key);
+  const int lines = axis == RS2_AXIS_PRIMARY ? int(p->ks) : int(p->kp);
+  return run_decode(p->ctx, p->dec, p->dec_slot, sp, std::move(key), decode_may_fuse(), lines, p,
+                    st);
+}
+int decode_device(rs2_plan* p, int axis, const std::vector<std::pair<uint16_t, uint32_t>>& chosen,
+                  const uint8_t* base, const uint64_t* off, uint8_t* d_out, hipStream_t st) {
+  return decode_device(p, axis, chosen, base, off, d_out, st, p->blob_len);
 }
 
 // Stream argument of the plan / verifier ABI: NULL = the object's own stream,
@@ -2012,6 +2056,244 @@ int check_decode_ptrs(uint32_t count, const void* d_slivers_base, const uint64_t
   RS2_TRY(check_symbol_ptr(d_slivers_base, "d_slivers_base"));
   for (uint32_t i = 0; i < count; ++i) RS2_TRY(check_symbol_step(sliver_off[i], "sliver_off[i]"));
   return check_symbol_ptr(d_blob_out, "d_blob_out");
+}
+
+// ---------------------------------------------------------------------------------------------
+// decode batches: many blobs of the plan's symbol size, an erasure pattern per blob
+// ---------------------------------------------------------------------------------------------
+// One validated blob of a batch call: its slivers (select_slivers: index, position in `off`),
+// their offsets from the call's sliver base, its length and its output.
+struct BatchItem {
+  uint32_t blob = 0;
+  uint64_t len = 0;
+  std::vector<std::pair<uint16_t, uint32_t>> chosen;
+  const uint64_t* off = nullptr;
+  uint8_t* out = nullptr;
+};
+
+// A blob planned for the batch kernel (on a pool thread): its job, narrowed and with the
+// arrays it will point into still on the host.
+struct BatchBlob {
+  bool eligible = false;
+  CodecJobBatch job{};
+  int C = 1, ppw = kPpwTarget;
+  size_t n_off = 0;                  // position offsets in `offs`; the copy offsets follow
+  bool has_copy = false;
+  uint8_t* copy_base = nullptr;
+  int64_t copy_ls = 0, copy_limit = INT64_MAX;
+  std::vector<int64_t> offs;
+  std::vector<uint16_t> logs, mix;   // pre ++ post multiplier logs; mixing tables, rows of 8
+  size_t n_pre = 0;
+  std::vector<int> in_sd, out_sd;
+};
+
+void plan_batch_blob(const rs2_plan* p, int axis, const BatchItem& it, const uint8_t* base,
+                     BatchBlob& bb) {
+  DecodeSpec sp;
+  std::vector<int64_t> key;
+  blob_decode_spec(p, axis, it.chosen, base, it.off, it.out, it.len, sp, key);
+  uint32_t originals = 0;
+  for (uint32_t i = 0; i < sp.K; ++i) originals += sp.present[i] >= 0;
+  if (originals == sp.K) return;  // nothing erased: a copy (the per-blob path)
+  sp.copy_present = originals > 0 && sp.symbol_size >= 4 && decode_may_fuse();
+  PlannedJob pj;
+  if (plan_decode(sp, pj) != RS2_OK) return;  // the per-blob path reports it
+  const bool fused = sp.copy_present && copy_covered(pj);
+  if (!batch_eligible(pj, fused) || (originals > 0 && !fused)) return;
+  bb.n_off = finish_plan(pj);
+  pack_batch_job(pj, bb.job, bb.mix);
+  bb.C = pj.C;
+  bb.ppw = pj.ppw;
+  bb.has_copy = !pj.copy_offs.empty();
+  bb.copy_base = pj.copy_base;
+  bb.copy_ls = pj.copy_ls;
+  bb.copy_limit = pj.copy_limit;
+  bb.offs = std::move(pj.offs);
+  bb.n_pre = pj.pre_logs.size();
+  bb.logs = std::move(pj.pre_logs);
+  bb.logs.insert(bb.logs.end(), pj.post_logs.begin(), pj.post_logs.end());
+  bb.in_sd = std::move(pj.in_sd);
+  bb.out_sd = std::move(pj.out_sd);
+  bb.eligible = true;
+}
+
+// Upload through the slot ring in pieces of at most a slot (never the runtime's copy from
+// pageable memory, which Context::upload falls back to above a slot).
+int upload_pieces(Context* ctx, void* dst, const void* src, size_t n, hipStream_t st) {
+  for (size_t o = 0; o < n; o += UploadSlots::kSlotBytes)
+    HIP_TRY(ctx->upload(static_cast<uint8_t*>(dst) + o, static_cast<const uint8_t*>(src) + o,
+                        std::min(UploadSlots::kSlotBytes, n - o), st));
+  return RS2_OK;
+}
+
+hipError_t launch_decode_batch(int C, const CodecJobBatch* d_jobs, int n_blobs, int tiles_per_blob,
+                               int n_z, hipStream_t st) {
+  switch (C) {
+    case 1: return rs2k_launch_decode_batch_1(d_jobs, n_blobs, tiles_per_blob, n_z, st);
+    case 2: return rs2k_launch_decode_batch_2(d_jobs, n_blobs, tiles_per_blob, n_z, st);
+    case 4: return rs2k_launch_decode_batch_4(d_jobs, n_blobs, tiles_per_blob, n_z, st);
+    case 8: return rs2k_launch_decode_batch_8(d_jobs, n_blobs, tiles_per_blob, n_z, st);
+    case 16: return rs2k_launch_decode_batch_16(d_jobs, n_blobs, tiles_per_blob, n_z, st);
+    case 32: return rs2k_launch_decode_batch_32(d_jobs, n_blobs, tiles_per_blob, n_z, st);
+    case 64: return rs2k_launch_decode_batch_64(d_jobs, n_blobs, tiles_per_blob, n_z, st);
+    case 128: return rs2k_launch_decode_batch_128(d_jobs, n_blobs, tiles_per_blob, n_z, st);
+    case 256: return rs2k_launch_decode_batch_256(d_jobs, n_blobs, tiles_per_blob, n_z, st);
+    case 512: return rs2k_launch_decode_batch_512(d_jobs, n_blobs, tiles_per_blob, n_z, st);
+    default: return hipErrorInvalidValue;
+  }
+}
+
+// One chunk: the blobs' arrays concatenated into the slot's device arrays, every job pointed
+// at its own part, one table build over all the logs, one launch.
+int launch_batch_chunk(rs2_plan* p, std::vector<BatchBlob*>& ch, int lines, hipStream_t st) {
+  Context* ctx = p->ctx;
+  BatchDecodeSlot& sl = p->dbatch[p->dbatch_slot];
+  p->dbatch_slot ^= 1;
+  if (sl.done) HIP_TRY(hipEventSynchronize(sl.done));
+  mark(p, "", st);
+  size_t n_offs = 0, n_logs = 0, n_mix = 0;
+  for (const BatchBlob* bb : ch) {
+    n_offs += bb->offs.size();
+    n_logs += bb->logs.size();
+    n_mix += bb->mix.size();
+  }
+  std::vector<int64_t> h_offs;
+  std::vector<uint16_t> h_logs, h_mix;
+  std::vector<CodecJobBatch> h_jobs;
+  h_offs.reserve(n_offs);
+  h_logs.reserve(n_logs);
+  h_mix.reserve(n_mix);
+  h_jobs.reserve(ch.size());
+  HIP_TRY(sl.offs.ensure(std::max<size_t>(n_offs * 8, 16)));
+  HIP_TRY(sl.logs.ensure(std::max<size_t>(n_logs * 2, 16)));
+  HIP_TRY(sl.tabs.ensure(std::max<size_t>(n_logs * kTabU16 * 2, 16)));
+  HIP_TRY(sl.mix.ensure(std::max<size_t>(n_mix * 2, 16)));
+  HIP_TRY(sl.jobs.ensure(ch.size() * sizeof(CodecJobBatch)));
+  const int C = ch[0]->C;
+  const int64_t per_blob = (int64_t(lines) * ch[0]->job.pairs_span + 63) / 64;
+  if (per_blob < 1 || per_blob * int64_t(ch.size()) > 0x7FFFFFFF)
+    return fail(RS2_E_UNSUPPORTED, "decode batch chunk exceeds the launch grid");
+  int n_z = 1;
+  for (BatchBlob* bb : ch) {
+    CodecJobBatch j = bb->job;
+    const int64_t* d_offs = sl.offs.as<int64_t>() + h_offs.size();
+    const uint16_t* d_tabs = sl.tabs.as<uint16_t>() + h_logs.size() * kTabU16;
+    for (int b = 0; b < j.n_in; ++b) {
+      InBlock& ib = j.in[b];
+      ib.pos_off = d_offs + size_t(b) * bb->C;
+      if (bb->has_copy) {
+        ib.copy_base = bb->copy_base;
+        ib.copy_off = d_offs + bb->n_off + size_t(b) * bb->C;
+        ib.copy_line_stride = bb->copy_ls;
+        ib.copy_limit = bb->copy_limit;
+      } else {
+        ib.copy_off = nullptr;
+      }
+      ib.sd_tab = ctx->stream(bb->C, bb->in_sd[size_t(b)], bb->ppw);
+      if (!ib.sd_tab) return fail(RS2_E_DEVICE, "table upload failed");
+      ib.zero_first = group0_zero(bb->C, bb->in_sd[size_t(b)], bb->ppw);
+      ib.pre_tab = d_tabs + size_t(b) * bb->C * kTabU16;
+    }
+    j.pre_z_stride = int64_t(j.n_in) * bb->C * kTabU16;
+    for (int o = 0; o < j.n_out; ++o) {
+      OutBlock& ob = j.out[o];
+      ob.pos_off = d_offs + size_t(j.n_in + o) * bb->C;
+      ob.sd_tab = ctx->stream(bb->C, bb->out_sd[size_t(o)], bb->ppw);
+      if (!ob.sd_tab) return fail(RS2_E_DEVICE, "table upload failed");
+      ob.zero_first = group0_zero(bb->C, bb->out_sd[size_t(o)], bb->ppw);
+      ob.post_tab = d_tabs + (bb->n_pre + size_t(o) * bb->C) * kTabU16;
+    }
+    j.mix_tab = bb->mix.empty() ? nullptr : sl.mix.as<uint16_t>() + h_mix.size();
+    // the launch's fields (set_launch_shape): this blob alone, lines folded into the tiles
+    j.n_lines = lines;
+    j.line_base = 0;
+    j.tiles_per_blob = 0;
+    j.in_blob_stride = j.out_blob_stride = j.copy_blob_stride = 0;
+    j.stamps = nullptr;
+    j.tile_ctr = nullptr;
+    n_z = std::max(n_z, j.n_out);
+    h_jobs.push_back(j);
+    h_offs.insert(h_offs.end(), bb->offs.begin(), bb->offs.end());
+    h_logs.insert(h_logs.end(), bb->logs.begin(), bb->logs.end());
+    h_mix.insert(h_mix.end(), bb->mix.begin(), bb->mix.end());
+  }
+  RS2_TRY(upload_pieces(ctx, sl.offs.p, h_offs.data(), h_offs.size() * 8, st));
+  RS2_TRY(upload_pieces(ctx, sl.logs.p, h_logs.data(), h_logs.size() * 2, st));
+  RS2_TRY(upload_pieces(ctx, sl.mix.p, h_mix.data(), h_mix.size() * 2, st));
+  RS2_TRY(upload_pieces(ctx, sl.jobs.p, h_jobs.data(), h_jobs.size() * sizeof(CodecJobBatch), st));
+  HIP_TRY(rs2k_launch_build_mul_tables(ctx->exp_t.as<uint16_t>(), ctx->log_t.as<uint16_t>(),
+                                       sl.logs.as<uint16_t>(), int(h_logs.size()),
+                                       sl.tabs.as<uint16_t>(), st));
+  mark(p, "dec_batch_setup", st);
+  HIP_TRY(launch_decode_batch(C, sl.jobs.as<CodecJobBatch>(), int(ch.size()), int(per_blob), n_z,
+                              st));
+  mark(p, "dec_batch_codec", st);
+  if (!sl.done) HIP_TRY(hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
+  HIP_TRY(hipEventRecord(sl.done, st));
+  g_batch_launches.fetch_add(1, std::memory_order_relaxed);
+  g_batch_blobs.fetch_add(ch.size(), std::memory_order_relaxed);
+  return RS2_OK;
+}
+
+// Decode validated blobs: windows of at most a chunk's jobs are planned on the host pool, the
+// eligible blobs of a window leave in chunks (one launch each), the others through the
+// per-blob decode on the same stream.
+int decode_batch_items(rs2_plan* p, int axis, const std::vector<BatchItem>& items,
+                       const uint8_t* base, hipStream_t st) {
+  Context* ctx = p->ctx;
+  const int lines = axis == RS2_AXIS_PRIMARY ? int(p->ks) : int(p->kp);
+  for (size_t w0 = 0; w0 < items.size(); w0 += kBatchChunkJobs) {
+    const size_t cnt = std::min(kBatchChunkJobs, items.size() - w0);
+    std::vector<BatchBlob> blobs(cnt);
+    const auto host_t0 = std::chrono::steady_clock::now();
+    {
+      const size_t T = std::min<size_t>(size_t(ctx->pool.threads()), cnt);
+      std::vector<std::function<void()>> tasks;
+      for (size_t t = 0; t < T; ++t)
+        tasks.emplace_back([&, t] {
+          for (size_t i = t; i < cnt; i += T) plan_batch_blob(p, axis, items[w0 + i], base, blobs[i]);
+        });
+      ctx->pool.run(tasks);
+    }
+    prof_host(p, "dec_batch_plan_host", host_t0);
+    std::vector<BatchBlob*> ch;
+    size_t tab_bytes = 0;
+    for (size_t i = 0; i <= cnt; ++i) {
+      BatchBlob* bb = i < cnt && blobs[i].eligible ? &blobs[i] : nullptr;
+      // a blob whose lane space or block size differs from the first eligible blob's cannot
+      // share its launch geometry
+      if (bb && !ch.empty() &&
+          (bb->C != ch[0]->C || bb->job.pairs_span != ch[0]->job.pairs_span))
+        bb->eligible = false, bb = nullptr;
+      const size_t need = bb ? bb->logs.size() * kTabU16 * 2 : 0;
+      if (!ch.empty() && (i == cnt || (bb && tab_bytes + need > kBatchTableBytes))) {
+        RS2_TRY(launch_batch_chunk(p, ch, lines, st));
+        ch.clear();
+        tab_bytes = 0;
+      }
+      if (bb) {
+        ch.push_back(bb);
+        tab_bytes += need;
+      }
+    }
+    for (size_t i = 0; i < cnt; ++i) {
+      if (blobs[i].eligible) continue;
+      const BatchItem& it = items[w0 + i];
+      RS2_TRY(decode_device(p, axis, it.chosen, base, it.off, it.out, st, it.len));
+      g_batch_single.fetch_add(1, std::memory_order_relaxed);
+    }
+  }
+  return RS2_OK;
+}
+
+// Per-blob length rule of the batch calls: blob_lens[b] (NULL: the plan's) gives the plan's
+// symbol size.
+int batch_blob_len(const rs2_plan* p, const uint64_t* blob_lens, uint32_t b, uint64_t* len) {
+  *len = blob_lens ? blob_lens[b] : p->blob_len;
+  uint16_t sb = 0;
+  if (rs2_symbol_size_for_blob(p->n, *len, &sb) != RS2_OK || sb != p->s)
+    return fail(RS2_E_INVALID_ARGUMENT, "blob length outside the plan's symbol size");
+  return RS2_OK;
 }
 
 }  // namespace
@@ -2134,7 +2416,8 @@ void rs2_plan_destroy(rs2_plan* plan) {
   // its buffers then go straight back to the device arena for the next plan
   for (hipStream_t st : {plan->stream, plan->side, plan->side_hi, plan->aux, plan->io})
     if (st) (void)hipStreamSynchronize(st);
-  for (hipEvent_t ev : {plan->enc_done, plan->dec[0].done, plan->dec[1].done, plan->leaf_ev})
+  for (hipEvent_t ev : {plan->enc_done, plan->dec[0].done, plan->dec[1].done, plan->leaf_ev,
+                        plan->dbatch[0].done, plan->dbatch[1].done})
     if (ev) (void)hipEventSynchronize(ev);
   const Quiesced quiesced;
   delete plan;
@@ -2440,6 +2723,144 @@ int rs2_encode_batch_with_metadata(rs2_plan* plan, uint32_t n_blobs, const uint8
   if (blob_ids_out) segs.push_back({blob_ids_out, di, B * 32});
   if (!segs.empty()) RS2_TRY(stage_d2h(ctx, *plan->stage, segs, st));
   HIP_TRY(hipStreamSynchronize(st));
+  return RS2_OK;
+}
+
+int rs2_decode_batch_device_async(rs2_plan* plan, int axis, uint32_t n_blobs,
+                                  const uint64_t* blob_lens, const uint32_t* counts,
+                                  const uint16_t* sliver_idx, const void* d_slivers_base,
+                                  const uint64_t* sliver_off, void* d_blobs_out,
+                                  uint64_t out_stride, int* status_out, void* stream) {
+  if (!plan) return fail(RS2_E_INVALID_ARGUMENT, "null plan");
+  if (axis != RS2_AXIS_PRIMARY && axis != RS2_AXIS_SECONDARY)
+    return fail(RS2_E_INVALID_ARGUMENT, "bad axis");
+  if (n_blobs == 0) return RS2_OK;
+  if (n_blobs > 65535) return fail(RS2_E_INVALID_ARGUMENT, "more than 65535 blobs in a batch");
+  if (!counts || !sliver_idx || !sliver_off || !d_slivers_base || !d_blobs_out)
+    return fail(RS2_E_INVALID_ARGUMENT, "null argument");
+  RS2_TRY(check_symbol_ptr(d_slivers_base, "d_slivers_base"));
+  RS2_TRY(check_symbol_ptr(d_blobs_out, "d_blobs_out"));
+  RS2_TRY(check_symbol_step(out_stride, "out_stride"));
+  HIP_TRY(hipSetDevice(plan->ctx->device));
+  // every blob is validated before anything is enqueued
+  std::vector<BatchItem> items;
+  items.reserve(n_blobs);
+  size_t first = 0;
+  for (uint32_t b = 0; b < n_blobs; first += counts[b], ++b) {
+    BatchItem it;
+    it.blob = b;
+    it.off = sliver_off + first;
+    it.out = reinterpret_cast<uint8_t*>(d_blobs_out) + uint64_t(b) * out_stride;
+    auto validate = [&]() -> int {
+      RS2_TRY(batch_blob_len(plan, blob_lens, b, &it.len));
+      if (n_blobs > 1 && it.len > out_stride)
+        return fail(RS2_E_INVALID_ARGUMENT, "out_stride smaller than a blob");
+      for (uint32_t i = 0; i < counts[b]; ++i)
+        RS2_TRY(check_symbol_step(it.off[i], "sliver_off[i]"));
+      return select_slivers(plan, axis, counts[b], sliver_idx + first, nullptr, nullptr, it.chosen);
+    };
+    const int rc = validate();
+    if (status_out)
+      status_out[b] = rc;
+    else if (rc != RS2_OK)
+      return rc;
+    if (rc == RS2_OK) items.push_back(std::move(it));
+  }
+  return decode_batch_items(plan, axis, items, reinterpret_cast<const uint8_t*>(d_slivers_base),
+                            pick_stream(plan, stream));
+}
+
+int rs2_decode_batch(rs2_plan* plan, int axis, uint32_t n_blobs, const uint64_t* blob_lens,
+                     const uint32_t* counts, const uint16_t* sliver_idx,
+                     const uint8_t* const* slivers, const uint64_t* sliver_len,
+                     const uint16_t* sliver_symbol_size, uint8_t* const* blobs_out,
+                     int* status_out) {
+  if (!plan) return fail(RS2_E_INVALID_ARGUMENT, "null plan");
+  if (axis != RS2_AXIS_PRIMARY && axis != RS2_AXIS_SECONDARY)
+    return fail(RS2_E_INVALID_ARGUMENT, "bad axis");
+  if (n_blobs == 0) return RS2_OK;
+  if (n_blobs > 65535) return fail(RS2_E_INVALID_ARGUMENT, "more than 65535 blobs in a batch");
+  if (!counts || !blobs_out) return fail(RS2_E_INVALID_ARGUMENT, "null argument");
+  size_t total = 0;
+  for (uint32_t b = 0; b < n_blobs; ++b) total += counts[b];
+  if (total && (!sliver_idx || !slivers || !sliver_len))
+    return fail(RS2_E_INVALID_ARGUMENT, "null argument");
+  HIP_TRY(hipSetDevice(plan->ctx->device));
+  RingGuard ring(plan);
+  Context* ctx = plan->ctx;
+  hipStream_t st = plan->stream;
+  const size_t len = size_t(axis == RS2_AXIS_PRIMARY ? primary_len(plan) : secondary_len(plan));
+  const uint32_t K = axis == RS2_AXIS_PRIMARY ? plan->kp : plan->ks;
+  const size_t msg = size_t(plan->kp) * plan->ks * plan->s;
+  const size_t ostride = (std::max<size_t>(msg, 16) + 255) / 256 * 256;
+  std::vector<BatchItem> items;
+  items.reserve(n_blobs);
+  size_t first = 0;
+  for (uint32_t b = 0; b < n_blobs; first += counts[b], ++b) {
+    BatchItem it;
+    it.blob = b;
+    auto validate = [&]() -> int {
+      RS2_TRY(batch_blob_len(plan, blob_lens, b, &it.len));
+      if (it.len && !blobs_out[b]) return fail(RS2_E_INVALID_ARGUMENT, "null output blob");
+      RS2_TRY(select_slivers(plan, axis, counts[b], sliver_idx + first, sliver_len + first,
+                             sliver_symbol_size ? sliver_symbol_size + first : nullptr, it.chosen));
+      for (const auto& c : it.chosen)
+        if (!slivers[first + c.second]) return fail(RS2_E_INVALID_ARGUMENT, "null sliver");
+      return RS2_OK;
+    };
+    const int rc = validate();
+    if (status_out)
+      status_out[b] = rc;
+    else if (rc != RS2_OK)
+      return rc;
+    if (rc != RS2_OK) continue;
+    for (auto& c : it.chosen) c.second = uint32_t(first + c.second);  // position in `slivers`
+    items.push_back(std::move(it));
+  }
+  // groups of blobs whose device slivers and outputs stay below a fixed budget
+  constexpr size_t kGroupBytes = size_t(512) << 20;
+  const size_t per_blob = size_t(K) * len + ostride;
+  const size_t group = std::max<size_t>(1, kGroupBytes / per_blob);
+  for (size_t g0 = 0; g0 < items.size(); g0 += group) {
+    const size_t g1 = std::min(items.size(), g0 + group), nb = g1 - g0;
+    HIP_TRY(plan->dbatch_in.ensure(nb * size_t(K) * len));
+    HIP_TRY(plan->dbatch_out.ensure(nb * ostride));
+    uint8_t* din = plan->dbatch_in.as<uint8_t>();
+    uint8_t* dout = plan->dbatch_out.as<uint8_t>();
+    std::vector<Seg> segs;
+    std::vector<std::vector<uint64_t>> offs(nb);
+    std::vector<BatchItem> part(items.begin() + g0, items.begin() + g1);
+    // the chosen slivers go to the device back to back: sliver k of the group's blob i at
+    // (i * K + k) * len
+    for (size_t i = 0; i < nb; ++i) {
+      BatchItem& it = part[i];
+      offs[i].resize(it.chosen.size());
+      for (size_t k = 0; k < it.chosen.size(); ++k) {
+        const size_t at = (i * K + k) * len;
+        segs.push_back({const_cast<uint8_t*>(slivers[it.chosen[k].second]), din + at, len});
+        offs[i][k] = at;
+        it.chosen[k].second = uint32_t(k);
+      }
+      it.off = offs[i].data();
+      it.out = dout + i * ostride;
+    }
+    RS2_TRY(stage_h2d(ctx, *plan->stage, segs, st));
+    RS2_TRY(decode_batch_items(plan, axis, part, din, st));
+    segs.clear();
+    for (size_t i = 0; i < nb; ++i)
+      if (part[i].len)
+        segs.push_back({blobs_out[part[i].blob], dout + i * ostride, size_t(part[i].len)});
+    if (!segs.empty()) RS2_TRY(stage_d2h(ctx, *plan->stage, segs, st));
+    HIP_TRY(hipStreamSynchronize(st));
+  }
+  return RS2_OK;
+}
+
+int rs2_decode_batch_stats(uint64_t* stats_out) {
+  if (!stats_out) return fail(RS2_E_INVALID_ARGUMENT, "null argument");
+  stats_out[0] = g_batch_launches.load(std::memory_order_relaxed);
+  stats_out[1] = g_batch_blobs.load(std::memory_order_relaxed);
+  stats_out[2] = g_batch_single.load(std::memory_order_relaxed);
   return RS2_OK;
 }
 

@@ -24,6 +24,21 @@ RS2_DECL(128)
 RS2_DECL(256)
 RS2_DECL(512)
 #undef RS2_DECL
+// the decode batch (one CodecJobBatch per blob in device memory, rs2_decode_batch_kernel)
+#define RS2_DECL_BATCH(CC)                                                                   \
+  hipError_t rs2k_launch_decode_batch_##CC(const rs2::CodecJobBatch* d_jobs, int n_blobs,  \
+                                           int tiles_per_blob, int n_z, hipStream_t stream);
+RS2_DECL_BATCH(1)
+RS2_DECL_BATCH(2)
+RS2_DECL_BATCH(4)
+RS2_DECL_BATCH(8)
+RS2_DECL_BATCH(16)
+RS2_DECL_BATCH(32)
+RS2_DECL_BATCH(64)
+RS2_DECL_BATCH(128)
+RS2_DECL_BATCH(256)
+RS2_DECL_BATCH(512)
+#undef RS2_DECL_BATCH
 hipError_t rs2k_launch_leaf_hash(rs2::SymbolMap map, int mode, int64_t count, int n_blobs,
                                  uint8_t* d_out, hipStream_t stream);
 hipError_t rs2k_launch_merkle_trees(const uint8_t* d_leaves, int n, int n_row_trees,

@@ -10,6 +10,7 @@
 #include <iterator>
 #include <map>
 #include <mutex>
+#include <tuple>
 
 namespace rs2 {
 
@@ -311,8 +312,8 @@ std::vector<uint32_t> erasure_logs(const std::vector<uint8_t>& erased, uint32_t 
 }
 
 // Block-level mixing: out block o = FFT_o( sum_b M1[o][b] Dw(X_b) + M2[o][b] X_b ).
-void mixing_matrices(int m, uint32_t cs, uint32_t W, std::vector<std::vector<uint32_t>>& M1,
-                     std::vector<std::vector<uint32_t>>& M2) {
+void build_mixing_matrices(int m, uint32_t cs, uint32_t W, std::vector<std::vector<uint32_t>>& M1,
+                           std::vector<std::vector<uint32_t>>& M2) {
   const Gf& g = gf();
   std::vector<std::vector<uint32_t>> Va(m, std::vector<uint32_t>(m, 0)), Vb = Va;
   for (int i = 0; i < m; ++i) Va[i][i] = 1;
@@ -360,6 +361,22 @@ void mixing_matrices(int m, uint32_t cs, uint32_t W, std::vector<std::vector<uin
   M1 = Vb;
   M2 = Va;
 }
+// The matrices depend on the transform's shape only, not on the erasure pattern: built once per
+// (m, cs, W) like log_walsh (a batch plans one decode per blob, on several threads).
+struct MixingMatrices {
+  std::vector<std::vector<uint32_t>> M1, M2;
+};
+const MixingMatrices& mixing_matrices(int m, uint32_t cs, uint32_t W) {
+  static std::mutex mu;
+  static std::map<std::tuple<int, uint32_t, uint32_t>, MixingMatrices> cache;
+  std::lock_guard<std::mutex> lk(mu);
+  const auto key = std::make_tuple(m, cs, W);
+  auto it = cache.find(key);
+  if (it != cache.end()) return it->second;
+  MixingMatrices mm;
+  build_mixing_matrices(m, cs, W, mm.M1, mm.M2);
+  return cache.emplace(key, std::move(mm)).first->second;
+}
 }  // namespace
 
 int plan_decode(const DecodeSpec& sp, PlannedJob& pj) {
@@ -397,8 +414,8 @@ int plan_decode(const DecodeSpec& sp, PlannedJob& pj) {
   else
     for (uint32_t p = end; p < W; ++p) erased[p] = 1;
   const std::vector<uint32_t> L = erasure_logs(erased, W);
-  std::vector<std::vector<uint32_t>> M1, M2;
-  mixing_matrices(m, cs, W, M1, M2);
+  const MixingMatrices& mm = mixing_matrices(m, cs, W);
+  const std::vector<std::vector<uint32_t>>&M1 = mm.M1, &M2 = mm.M2;
 
   CodecJobBig& j = pj.job;
   j = CodecJobBig{};
@@ -541,6 +558,41 @@ int plan_decode(const DecodeSpec& sp, PlannedJob& pj) {
     set_mixing(pj, oi, &c1, c2);
   }
   return RS2_OK;
+}
+
+bool batch_eligible(const PlannedJob& pj, bool fused) {
+  const CodecJobBig& j = pj.job;
+  if (pj.mode != kModeDecode) return false;
+  if (j.n_in < 1 || j.n_out < 1 || j.n_in > kBatchBlocks || j.n_out > kBatchBlocks) return false;
+  if (j.symbol_size < 4) return false;
+  // (plan_decode sets copy_base only under copy_present; copy_covered empties copy_offs when the
+  // fused copy-out is not covered)
+  const bool nothing_to_copy = pj.copy_base == nullptr && pj.copy_offs.empty();
+  return nothing_to_copy || (fused && !pj.copy_offs.empty());
+}
+
+void pack_batch_job(const PlannedJob& pj, CodecJobBatch& out, std::vector<uint16_t>& mix) {
+  const CodecJobBig& b = pj.job;
+  constexpr int MB = kBatchBlocks;
+  static_cast<CodecScalars&>(out) = static_cast<const CodecScalars&>(b);
+  std::copy(b.in, b.in + MB, out.in);
+  std::copy(b.out, b.out + MB, out.out);
+  for (int o = 0; o < MB; ++o) {
+    std::copy(b.m1_kind[o], b.m1_kind[o] + MB, out.m1_kind[o]);
+    std::copy(b.m2_kind[o], b.m2_kind[o] + MB, out.m2_kind[o]);
+  }
+  std::copy(b.pair_p, b.pair_p + MB, out.pair_p);
+  std::copy(b.pair_q, b.pair_q + MB, out.pair_q);
+  std::copy(b.pair_nw, b.pair_nw + MB, out.pair_nw);
+  mix.clear();
+  if (!pj.has_mix) return;
+  const size_t ms = size_t(pj.mix_stride), row = size_t(2) * kTabU16;
+  mix.assign(size_t(b.n_out) * MB * row, 0);
+  for (int o = 0; o < b.n_out; ++o)
+    for (int i = 0; i < b.n_in; ++i)
+      std::copy(pj.mix.begin() + (size_t(o) * ms + i) * row,
+                pj.mix.begin() + (size_t(o) * ms + i + 1) * row,
+                mix.begin() + (size_t(o) * MB + i) * row);
 }
 
 }  // namespace rs2

@@ -267,4 +267,21 @@ struct DecodeSpec {
 
 int plan_decode(const DecodeSpec& sp, PlannedJob& pj);
 
+// ---------------------------------------------------------------------------------------------
+// decode batches (rs2_decode_batch_*): one CodecJobBatch per blob in a device job table
+// ---------------------------------------------------------------------------------------------
+// True when a decode planned into a fresh PlannedJob can run as one job of a batch launch: a
+// decode of at most kBatchBlocks input and output blocks (and at least one of each), whole-dword
+// symbol I/O (s >= 4), and either nothing to copy -- the plan was made without copy_present,
+// because no original is among its inputs -- or a fused copy-out that is covered (`fused`:
+// sp.copy_present && copy_covered(pj)).  The batch launch has no separate copy pass.
+bool batch_eligible(const PlannedJob& pj, bool fused);
+
+// Narrow a planned decode to the batch job, like the launch's narrowing to CodecJob: every
+// CodecScalars field, the block arrays, mixing kinds and pair arrays below kBatchBlocks.  `mix`
+// receives the mixing tables of output blocks o < n_out re-strided to rows of kBatchBlocks
+// (table (o, b, k) at ((o * kBatchBlocks + b) * 2 + k) * kTabU16), or nothing when the plan has
+// none.  The caller checked batch_eligible.
+void pack_batch_job(const PlannedJob& pj, CodecJobBatch& out, std::vector<uint16_t>& mix);
+
 }  // namespace rs2

@@ -632,6 +632,42 @@ class ReedSolomonEncodingConfig:
                                            lens, syms, out.ctypes.data), decode=True)
         return out[:blob_size].tobytes()
 
+    def decode_batch(self, blobs: Sequence[Tuple[int, Iterable[SliverData]]]) -> List[bytes]:
+        """decode of many blobs, [(blob_size, slivers), ...], one batched device call per group
+        of blobs that share a symbol size and an axis (rs2_decode_batch).  Same results as
+        decode per blob, in input order; the first failing blob raises its DecodeError."""
+        args = [(int(size),) + self._decode_args(slivers) for size, slivers in blobs]
+        groups: Dict[Tuple[int, str], List[int]] = {}
+        for i, a in enumerate(args):
+            if a[0] > self.max_blob_size():
+                self._decode_plan(a[0])  # raises DecodeDataTooLarge
+            groups.setdefault((self.symbol_size_for_blob(a[0]), a[1]), []).append(i)
+        out: List = [None] * len(args)
+        for (_, axis), members in groups.items():
+            for c0 in range(0, len(members), 65535):
+                chunk = members[c0:c0 + 65535]
+                B = len(chunk)
+                top = max(args[i][0] for i in chunk)
+                plan = self._decode_plan(top)
+                lens = (ctypes.c_uint64 * B)(*[args[i][0] for i in chunk])
+                counts = (ctypes.c_uint32 * B)(*[len(args[i][2]) for i in chunk])
+                keep = [a for i in chunk for a in args[i][3]]
+                m = max(len(keep), 1)
+                idx = (ctypes.c_uint16 * m)(*[s.index for i in chunk for s in args[i][2]])
+                ptrs = (ctypes.c_void_p * m)(*[a.ctypes.data for a in keep])
+                slens = (ctypes.c_uint64 * m)(*[len(a) for a in keep])
+                syms = (ctypes.c_uint16 * m)(*[min(s.symbol_size, 0xFFFF)
+                                               for i in chunk for s in args[i][2]])
+                outs = [np.empty(max(args[i][0], 1), dtype=np.uint8) for i in chunk]
+                op = (ctypes.c_void_p * B)(*[o.ctypes.data for o in outs])
+                with plan.lock:
+                    plan.bind(top)
+                    _ok(_lib.lib().rs2_decode_batch(plan.handle, _AXIS[axis], B, lens, counts, idx,
+                                                    ptrs, slens, syms, op, None), decode=True)
+                for k, i in enumerate(chunk):
+                    out[i] = outs[k][:args[i][0]].tobytes()
+        return out
+
     def decode_and_verify(self, metadata: VerifiedBlobMetadataWithId,
                           slivers: Iterable[SliverData], consistency_check: str = "default") -> bytes:
         """config.rs:613-658 (Default: only the systematic primary slivers that were not among
@@ -782,6 +818,14 @@ def upload_stats() -> Dict[str, int]:
     return dict(zip(("uploads", "jobs", "waits"), (int(v) for v in out)))
 
 
+def decode_batch_stats() -> Dict[str, int]:
+    """rs2_decode_batch_stats: batched decode launches, blobs decoded inside them, and blobs of
+    batch calls that took the per-blob path (process-wide)."""
+    out = (ctypes.c_uint64 * 3)()
+    _ok(_lib.lib().rs2_decode_batch_stats(out))
+    return dict(zip(("launches", "batched", "single"), (int(v) for v in out)))
+
+
 def device_memory_trim(device: int = 0) -> int:
     """rs2_device_memory_trim: hand the arena's wholly free segments back; returns the bytes."""
     out = ctypes.c_uint64()
@@ -843,6 +887,31 @@ class DevicePlan:
         off = (ctypes.c_uint64 * n)(*offsets)
         _ok(_lib.lib().rs2_decode_device_async(self.handle, _AXIS[axis], n, idx, d_base, off,
                                                d_out, _stream(stream)), decode=True)
+
+    def decode_batch_async(self, axis: str, blobs: Sequence[Tuple[Sequence[int], Sequence[int]]],
+                           d_base: int, d_out: int, out_stride: int,
+                           blob_lens: Optional[Sequence[int]] = None,
+                           stream: Optional[int] = None,
+                           statuses: bool = False) -> Optional[List[int]]:
+        """rs2_decode_batch_device_async: blob b is decoded from the slivers
+        blobs[b] = (indices, offsets from d_base) into d_out + b*out_stride (blob_lens[b] bytes,
+        None = the plan's blob_len).  statuses=False: the first invalid blob raises and nothing
+        is enqueued; True: invalid blobs are skipped and the per-blob codes are returned."""
+        B = len(blobs)
+        counts = (ctypes.c_uint32 * max(B, 1))(*[len(ix) for ix, _ in blobs])
+        # (numpy: index / offset arrays pass through without a per-element conversion)
+        idx = np.concatenate([np.asarray(ix, dtype=np.uint16) for ix, _ in blobs] +
+                             [np.zeros(1, dtype=np.uint16)])
+        off = np.concatenate([np.asarray(of, dtype=np.uint64) for _, of in blobs] +
+                             [np.zeros(1, dtype=np.uint64)])
+        lens = (ctypes.c_uint64 * max(B, 1))(*blob_lens) if blob_lens is not None else None
+        status = (ctypes.c_int * max(B, 1))() if statuses else None
+        _ok(_lib.lib().rs2_decode_batch_device_async(
+            self.handle, _AXIS[axis], B, lens, counts,
+            idx.ctypes.data_as(ctypes.POINTER(ctypes.c_uint16)), d_base,
+            off.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), d_out, out_stride,
+            status, _stream(stream)), decode=True)
+        return [int(v) for v in status[:B]] if statuses else None
 
     def decode_and_verify(self, axis: str, indices: Sequence[int], d_base: int,
                           offsets: Sequence[int], hashes: bytes, blob_id: bytes, check: str,
