@@ -412,6 +412,82 @@ int rs2_verifier_recovery_symbols_device_async(rs2_verifier* v, uint32_t count,
                                                void* d_symbols, void* d_proofs, void* d_nodes,
                                                void* stream);
 
+/* ---- sliver recovery in bulk ------------------------------------------------------------------
+ * SliverData::recover_sliver_or_generate_inconsistency_proof (slivers.rs:341-379, called per
+ * missing sliver from walrus-service's request_futures.rs:436-497) for many slivers of the
+ * verifier's axis in one call, each from its own set of received recovery symbols: the 1D
+ * decodes (slivers.rs:246-289) run as jobs of one launch per chunk of a few hundred slivers,
+ * then each recovered sliver's Merkle root is formed and compared with the expected one.  A
+ * sliver whose decode does not fit a batch job (every original received, a 2-byte symbol, more
+ * than 8 transform blocks) is decoded on its own on the same stream.
+ *
+ * Sliver i: counts[i] received symbols, their DecodingSymbol indices (symbols.rs; the source
+ * sliver's index) consecutive in symbol_idx (HOST), their data consecutive in d_symbols (sum of
+ * counts symbols of symbol_size bytes back to back, 2-byte aligned).  It is written whole to
+ * d_slivers_out + i*k*symbol_size (k = the verifier's symbols per sliver; 2-byte aligned):
+ * received originals copied, erased ones decoded.  d_roots (may be NULL; n_slivers*32 bytes,
+ * 16-byte aligned) receives the recovered slivers' roots as rs2_verifier_roots_device_async
+ * computes them.  expected_roots (HOST, n_slivers*32 bytes, may be NULL): the target slivers'
+ * hashes from their blobs' metadata; d_verdict (n_slivers int32, 16-byte aligned) then gets one
+ * of the constants below in every slot.  expected_roots NULL: no verdicts, d_verdict must be
+ * NULL too.
+ * Per sliver, checked on the host before anything is enqueued: counts[i] < k ->
+ * RS2_E_DECODING_UNSUCCESSFUL; else as rs2_decode_1d: entries in order, duplicates and indices
+ * >= n_shards ignored, the first k distinct ones used, fewer -> RS2_E_NOT_ENOUGH_SHARDS.
+ * status_out NULL: the first failing sliver's code is returned and nothing is enqueued;
+ * non-NULL: failing slivers get their code and are skipped (output and root slot not written,
+ * verdict RS2_SLIVER_SKIPPED), the rest run, RS2_OK.  n_slivers 0: RS2_OK, nothing enqueued.
+ * At most 65535 slivers.  Stream conventions as the other verifier calls. */
+#define RS2_SLIVER_MISMATCH 0   /* recovered, Merkle root differs from expected_roots[i]  */
+#define RS2_SLIVER_MATCH    1   /* recovered and verified                                  */
+#define RS2_SLIVER_SKIPPED  2   /* refused on the host (status_out[i] != RS2_OK), not decoded */
+int rs2_verifier_recover_slivers_device_async(
+    rs2_verifier* v, uint32_t n_slivers, const uint32_t* counts, const uint16_t* symbol_idx,
+    const void* d_symbols, const uint8_t* expected_roots, void* d_slivers_out,
+    void* d_roots, void* d_verdict, int* status_out, void* stream);
+/* Host form (blocking): symbols[] holds one pointer per received symbol (symbol_size bytes
+ * each), concatenated like symbol_idx; slivers_out[i] receives sliver i (k*symbol_size bytes),
+ * roots_out (may be NULL) n_slivers*32 bytes, verdict_out n_slivers values (NULL exactly when
+ * expected_roots is).  Slots of skipped slivers are not written, except verdict_out. */
+int rs2_recover_slivers(uint16_t n_shards, uint16_t symbol_size, int axis, uint32_t n_slivers,
+                        const uint32_t* counts, const uint16_t* symbol_idx,
+                        const uint8_t* const* symbols, const uint8_t* expected_roots,
+                        uint8_t* const* slivers_out, uint8_t* roots_out, int32_t* verdict_out,
+                        int* status_out);
+/* Process-wide counters, stats_out[3]: batched recovery launches, slivers decoded inside them,
+ * slivers that took the per-sliver path.  No reference counterpart. */
+int rs2_recover_stats(uint64_t* stats_out);
+/* Stage profiler of a verifier's recovery calls, as rs2_profile_enable / rs2_profile_read for a
+ * plan: host planning of the windows (rec_plan_host), the chunk uploads and table build
+ * (dec_batch_setup), the decode launches (dec_batch_codec; dec_setup / dec_codec /
+ * dec_copy_present for per-sliver decodes), the roots (rec_roots) and the verdicts
+ * (rec_verdict).  No reference counterpart. */
+int rs2_verifier_profile_enable(rs2_verifier* v, int enable);
+int rs2_verifier_profile_read(rs2_verifier* v, uint32_t max_stages, char* names,
+                              double* total_ms, uint32_t* launches, uint32_t* n_stages);
+
+/* RecoverySymbol::verify's proof step (symbols.rs:617-642; merkle.rs:78-99,150-169) for every
+ * received symbol of a recovery call, grouped and laid out as above: sliver i's counts[i]
+ * symbols all authenticate leaf target_index[i] (HOST; the target sliver's index on the
+ * orthogonal axis; >= n_shards -> RS2_E_INVALID_ARGUMENT before anything is enqueued) of their
+ * own source sliver's tree.  Symbol j (position in d_symbols, 2-byte aligned): its proof is
+ * path_len = rs2_merkle_tree_shape(n_shards) nodes at d_proofs + j*path_len*32, its expected
+ * root (the source sliver's hash, gathered by the caller) 32 bytes at d_expected_roots + j*32;
+ * d_ok + j (sum of counts bytes) receives 1 if the proof's root equals it, else 0.  d_proofs,
+ * d_expected_roots and d_ok are 16-byte aligned.  The length and index-bound checks of
+ * verify_proof stay with the caller, as for rs2_merkle_proof_roots.  At most 65535 slivers. */
+int rs2_verifier_check_recovery_symbols_device_async(
+    rs2_verifier* v, uint32_t n_slivers, const uint32_t* counts, const uint16_t* target_index,
+    const void* d_symbols, const void* d_proofs, const void* d_expected_roots,
+    void* d_ok, void* stream);
+/* Host form (blocking): symbols, proofs and expected_roots are contiguous host arrays laid out
+ * as the device form's, ok_out one byte per symbol. */
+int rs2_check_recovery_symbols(uint16_t n_shards, uint16_t symbol_size, int axis,
+                               uint32_t n_slivers, const uint32_t* counts,
+                               const uint16_t* target_index, const uint8_t* symbols,
+                               const uint8_t* proofs, const uint8_t* expected_roots,
+                               uint8_t* ok_out);
+
 /* Path length (merkle.rs path_length) and node count (n_nodes) of a tree over n_leaves. */
 int rs2_merkle_tree_shape(uint32_t n_leaves, uint32_t* path_len, uint64_t* n_nodes);
 

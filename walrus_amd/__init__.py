@@ -44,9 +44,11 @@ from .recovery import (  # noqa: F401
     MerkleProof,
     RecoverySymbol,
     recover_sliver_or_generate_inconsistency_proof,
+    recover_slivers_or_generate_inconsistency_proofs,
     recovery_symbol_for_sliver,
     recovery_symbols_for_requests,
     try_recover_sliver_from_decoding_symbols,
+    verify_recovery_symbols,
 )
 
 build_library = _lib.build_library

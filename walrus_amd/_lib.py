@@ -32,6 +32,7 @@ RS2_E_INTERNAL = -11
 AXIS_PRIMARY = 0
 AXIS_SECONDARY = 1
 CHECK_SKIP, CHECK_DEFAULT, CHECK_STRICT = 0, 1, 2
+RS2_SLIVER_MISMATCH, RS2_SLIVER_MATCH, RS2_SLIVER_SKIPPED = 0, 1, 2
 
 # (name, restype, argtypes) for every function declared in include/walrus_rs2.h
 _u8p = ctypes.POINTER(ctypes.c_uint8)
@@ -134,6 +135,28 @@ SIGNATURES = {
          _u64p, _u16p, _vp, _vp]),
     "rs2_verifier_recovery_symbols_device_async": (
         ctypes.c_int, [_vp, ctypes.c_uint32, _vp, _u16p, _vp, _vp, _vp, _vp]),
+    "rs2_verifier_recover_slivers_device_async": (
+        ctypes.c_int,
+        [_vp, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32), _u16p, _vp, _vp, _vp, _vp, _vp,
+         ctypes.POINTER(ctypes.c_int), _vp]),
+    "rs2_recover_slivers": (
+        ctypes.c_int,
+        [ctypes.c_uint16, ctypes.c_uint16, ctypes.c_int, ctypes.c_uint32,
+         ctypes.POINTER(ctypes.c_uint32), _u16p, ctypes.POINTER(_vp), _vp, ctypes.POINTER(_vp),
+         _vp, _vp, ctypes.POINTER(ctypes.c_int)]),
+    "rs2_recover_stats": (ctypes.c_int, [ctypes.POINTER(ctypes.c_uint64)]),
+    "rs2_verifier_profile_enable": (ctypes.c_int, [_vp, ctypes.c_int]),
+    "rs2_verifier_profile_read": (
+        ctypes.c_int,
+        [_vp, ctypes.c_uint32, ctypes.c_char_p, ctypes.POINTER(ctypes.c_double),
+         ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]),
+    "rs2_verifier_check_recovery_symbols_device_async": (
+        ctypes.c_int,
+        [_vp, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32), _u16p, _vp, _vp, _vp, _vp, _vp]),
+    "rs2_check_recovery_symbols": (
+        ctypes.c_int,
+        [ctypes.c_uint16, ctypes.c_uint16, ctypes.c_int, ctypes.c_uint32,
+         ctypes.POINTER(ctypes.c_uint32), _u16p, _vp, _vp, _vp, _vp]),
     "rs2_merkle_tree_shape": (
         ctypes.c_int, [ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32), _u64p]),
     "rs2_merkle_proof_roots": (

@@ -1383,10 +1383,15 @@ struct rs2_plan {
     std::vector<std::pair<std::string, hipEvent_t>> pending;  // "" = start mark
     std::map<std::string, std::pair<double, uint32_t>> acc;   // name -> (total ms, launches)
     std::vector<std::string> order;
+    Prof() = default;
+    Prof(const Prof&) = delete;
+    Prof& operator=(const Prof&) = delete;
+    ~Prof() {
+      for (auto& e : free_events) (void)hipEventDestroy(e);
+      for (auto& pe : pending) (void)hipEventDestroy(pe.second);
+    }
   } prof;
   ~rs2_plan() {
-    for (auto& e : prof.free_events) (void)hipEventDestroy(e);
-    for (auto& pe : prof.pending) (void)hipEventDestroy(pe.second);
     if (fork_ev) (void)hipEventDestroy(fork_ev);
     if (join_ev) (void)hipEventDestroy(join_ev);
     if (copy_ev) (void)hipEventDestroy(copy_ev);
@@ -1418,6 +1423,16 @@ struct rs2_verifier {
   PinnedBuf h_in, h_out;  // host-buffer forms: slivers in, roots / symbols / proofs out
   int axis = 0;
   std::vector<uint16_t> targets_h;  // alive until the upload of the last call has landed
+  // sliver recovery (rs2_verifier_recover_slivers_device_async): the chunk slots of the batched
+  // decodes and the slots of the per-sliver ones, each pair taken in turn behind `done` events
+  // like a plan's; a window's expected roots and skip mask; a window's roots when the caller
+  // wants none; the proof check's per-sliver table and leaf digests
+  BatchDecodeSlot rbatch[2];
+  int rbatch_slot = 0;
+  DecodeSlot rdec[2];
+  int rdec_slot = 0;
+  DevBuf verdict_in, window_roots, per_sliver, sym_digests;
+  rs2_plan::Prof prof;  // opt-in stage profiler of the recovery call (rs2_verifier_profile_*)
   // recorded on the caller's stream after each *_device_async call: destroy waits on it before
   // its buffers go back to the arena as quiesced (they may be handed out again at once)
   hipEvent_t done = nullptr;
@@ -1450,8 +1465,8 @@ namespace {
 
 // Record a stage boundary on `st` (no-op unless profiling).  The stage's time is the span
 // from the previous mark on this plan; a mark named "" only starts a span.
-void mark(rs2_plan* p, const char* name, hipStream_t st) {
-  auto& pr = p->prof;
+void mark(rs2_plan::Prof* prof, const char* name, hipStream_t st) {
+  auto& pr = *prof;
   if (!pr.on) return;
   hipEvent_t e;
   if (!pr.free_events.empty()) {
@@ -1463,6 +1478,8 @@ void mark(rs2_plan* p, const char* name, hipStream_t st) {
   (void)hipEventRecord(e, st);
   pr.pending.emplace_back(name, e);
 }
+
+void mark(rs2_plan* p, const char* name, hipStream_t st) { mark(&p->prof, name, st); }
 
 // one more span of `ms` under `name` in the profiler's histogram
 void prof_add(rs2_plan::Prof& pr, const std::string& name, double ms) {
@@ -1476,8 +1493,9 @@ void prof_add(rs2_plan::Prof& pr, const std::string& name, double ms) {
 }
 
 // host time since t0 under `name` (profiling on): the erasure-pattern planning of a decode
-void prof_host(rs2_plan* p, const char* name, std::chrono::steady_clock::time_point t0) {
-  auto& pr = p->prof;
+void prof_host(rs2_plan::Prof* prof, const char* name,
+               std::chrono::steady_clock::time_point t0) {
+  auto& pr = *prof;
   if (!pr.on) return;
   const double ms =
       std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -1485,8 +1503,11 @@ void prof_host(rs2_plan* p, const char* name, std::chrono::steady_clock::time_po
   prof_add(pr, name, ms);
 }
 
-void prof_collect(rs2_plan* p) {
-  auto& pr = p->prof;
+void prof_host(rs2_plan* p, const char* name, std::chrono::steady_clock::time_point t0) {
+  prof_host(&p->prof, name, t0);
+}
+
+void prof_collect(rs2_plan::Prof& pr) {
   hipEvent_t prev = nullptr;
   for (auto& pe : pr.pending) {
     (void)hipEventSynchronize(pe.second);
@@ -1499,6 +1520,9 @@ void prof_collect(rs2_plan* p) {
   for (auto& pe : pr.pending) pr.free_events.push_back(pe.second);
   pr.pending.clear();
 }
+
+int prof_read(rs2_plan::Prof& pr, uint32_t max_stages, char* names, double* total_ms,
+              uint32_t* launches, uint32_t* n_stages);
 
 int64_t primary_len(const rs2_plan* p) { return int64_t(p->ks) * p->s; }
 int64_t secondary_len(const rs2_plan* p) { return int64_t(p->kp) * p->s; }
@@ -1897,7 +1921,8 @@ int select_slivers(const rs2_plan* p, int axis, uint32_t count, const uint16_t* 
 // bytes written are the same).  A source offset of 2^63 or more is negative in sp.present and
 // so counts as absent here, as it always did for the decode plan itself.
 int run_decode(Context* ctx, DecodeSlot (&slots)[2], int& cursor, DecodeSpec& sp,
-               std::vector<int64_t> key, bool may_fuse, int lines, rs2_plan* prof, hipStream_t st) {
+               std::vector<int64_t> key, bool may_fuse, int lines, rs2_plan::Prof* prof,
+               hipStream_t st) {
   DecodeSlot& sl = slots[cursor];
   cursor ^= 1;
   const auto wait_t0 = std::chrono::steady_clock::now();
@@ -2004,7 +2029,8 @@ int decode_device(rs2_plan* p, int axis, const std::vector<std::pair<uint16_t, u
   std::vector<int64_t> key;
   blob_decode_spec(p, axis, chosen, base, off, d_out, blob_len, sp, key);
   const int lines = axis == RS2_AXIS_PRIMARY ? int(p->ks) : int(p->kp);
-  return run_decode(p->ctx, p->dec, p->dec_slot, sp, std::move(key), decode_may_fuse(), lines, p,
+  return run_decode(p->ctx, p->dec, p->dec_slot, sp, std::move(key), decode_may_fuse(), lines,
+                    &p->prof,
                     st);
 }
 int decode_device(rs2_plan* p, int axis, const std::vector<std::pair<uint16_t, uint32_t>>& chosen,
@@ -2087,6 +2113,8 @@ struct BatchBlob {
   std::vector<int> in_sd, out_sd;
 };
 
+void plan_batch_spec(const DecodeSpec& sp, uint32_t originals, BatchBlob& bb);
+
 void plan_batch_blob(const rs2_plan* p, int axis, const BatchItem& it, const uint8_t* base,
                      BatchBlob& bb) {
   DecodeSpec sp;
@@ -2096,6 +2124,12 @@ void plan_batch_blob(const rs2_plan* p, int axis, const BatchItem& it, const uin
   for (uint32_t i = 0; i < sp.K; ++i) originals += sp.present[i] >= 0;
   if (originals == sp.K) return;  // nothing erased: a copy (the per-blob path)
   sp.copy_present = originals > 0 && sp.symbol_size >= 4 && decode_may_fuse();
+  plan_batch_spec(sp, originals, bb);
+}
+
+// Plan `sp` (with `originals` of its K originals present, not all of them, and copy_present set
+// by the caller's rule) as a job of a batch launch; bb.eligible stays false when it cannot be one.
+void plan_batch_spec(const DecodeSpec& sp, uint32_t originals, BatchBlob& bb) {
   PlannedJob pj;
   if (plan_decode(sp, pj) != RS2_OK) return;  // the per-blob path reports it
   const bool fused = sp.copy_present && copy_covered(pj);
@@ -2144,13 +2178,16 @@ hipError_t launch_decode_batch(int C, const CodecJobBatch* d_jobs, int n_blobs, 
 }
 
 // One chunk: the blobs' arrays concatenated into the slot's device arrays, every job pointed
-// at its own part, one table build over all the logs, one launch.
-int launch_batch_chunk(rs2_plan* p, std::vector<BatchBlob*>& ch, int lines, hipStream_t st) {
-  Context* ctx = p->ctx;
-  BatchDecodeSlot& sl = p->dbatch[p->dbatch_slot];
-  p->dbatch_slot ^= 1;
+// at its own part, one table build over all the logs, one launch.  The slot pair and its cursor
+// belong to the caller (a blob plan, or a verifier recovering slivers); `prof` (may be null) is
+// the caller's stage profiler.
+int launch_batch_chunk(Context* ctx, BatchDecodeSlot (&slots)[2], int& cursor,
+                       std::vector<BatchBlob*>& ch, int lines, rs2_plan::Prof* prof,
+                       hipStream_t st) {
+  BatchDecodeSlot& sl = slots[cursor];
+  cursor ^= 1;
   if (sl.done) HIP_TRY(hipEventSynchronize(sl.done));
-  mark(p, "", st);
+  if (prof) mark(prof, "", st);
   size_t n_offs = 0, n_logs = 0, n_mix = 0;
   for (const BatchBlob* bb : ch) {
     n_offs += bb->offs.size();
@@ -2224,14 +2261,12 @@ int launch_batch_chunk(rs2_plan* p, std::vector<BatchBlob*>& ch, int lines, hipS
   HIP_TRY(rs2k_launch_build_mul_tables(ctx->exp_t.as<uint16_t>(), ctx->log_t.as<uint16_t>(),
                                        sl.logs.as<uint16_t>(), int(h_logs.size()),
                                        sl.tabs.as<uint16_t>(), st));
-  mark(p, "dec_batch_setup", st);
+  if (prof) mark(prof, "dec_batch_setup", st);
   HIP_TRY(launch_decode_batch(C, sl.jobs.as<CodecJobBatch>(), int(ch.size()), int(per_blob), n_z,
                               st));
-  mark(p, "dec_batch_codec", st);
+  if (prof) mark(prof, "dec_batch_codec", st);
   if (!sl.done) HIP_TRY(hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
   HIP_TRY(hipEventRecord(sl.done, st));
-  g_batch_launches.fetch_add(1, std::memory_order_relaxed);
-  g_batch_blobs.fetch_add(ch.size(), std::memory_order_relaxed);
   return RS2_OK;
 }
 
@@ -2267,7 +2302,9 @@ int decode_batch_items(rs2_plan* p, int axis, const std::vector<BatchItem>& item
         bb->eligible = false, bb = nullptr;
       const size_t need = bb ? bb->logs.size() * kTabU16 * 2 : 0;
       if (!ch.empty() && (i == cnt || (bb && tab_bytes + need > kBatchTableBytes))) {
-        RS2_TRY(launch_batch_chunk(p, ch, lines, st));
+        RS2_TRY(launch_batch_chunk(ctx, p->dbatch, p->dbatch_slot, ch, lines, &p->prof, st));
+        g_batch_launches.fetch_add(1, std::memory_order_relaxed);
+        g_batch_blobs.fetch_add(ch.size(), std::memory_order_relaxed);
         ch.clear();
         tab_bytes = 0;
       }
@@ -2561,8 +2598,30 @@ int rs2_profile_read(rs2_plan* plan, uint32_t max_stages, char* names, double* t
                      uint32_t* launches, uint32_t* n_stages) {
   if (!plan || !n_stages) return fail(RS2_E_INVALID_ARGUMENT, "null argument");
   (void)hipSetDevice(plan->ctx->device);
-  prof_collect(plan);
-  auto& pr = plan->prof;
+  return prof_read(plan->prof, max_stages, names, total_ms, launches, n_stages);
+}
+
+int rs2_verifier_profile_enable(rs2_verifier* v, int enable) {
+  if (!v) return fail(RS2_E_INVALID_ARGUMENT, "null verifier");
+  v->prof.on = enable != 0;
+  return RS2_OK;
+}
+
+int rs2_verifier_profile_read(rs2_verifier* v, uint32_t max_stages, char* names, double* total_ms,
+                              uint32_t* launches, uint32_t* n_stages) {
+  if (!v || !n_stages) return fail(RS2_E_INVALID_ARGUMENT, "null argument");
+  (void)hipSetDevice(v->ctx->device);
+  return prof_read(v->prof, max_stages, names, total_ms, launches, n_stages);
+}
+
+}  // extern "C"
+
+namespace {
+// Synchronise on the pending marks, hand out the per-stage totals (names: 32-byte NUL-padded
+// slots) and reset them.
+int prof_read(rs2_plan::Prof& pr, uint32_t max_stages, char* names, double* total_ms,
+              uint32_t* launches, uint32_t* n_stages) {
+  prof_collect(pr);
   uint32_t k = 0;
   for (const auto& name : pr.order) {
     if (k >= max_stages) break;
@@ -2580,6 +2639,9 @@ int rs2_profile_read(rs2_plan* plan, uint32_t max_stages, char* names, double* t
   pr.order.clear();
   return RS2_OK;
 }
+}  // namespace
+
+extern "C" {
 
 int rs2_sync(rs2_plan* plan, void* stream) {
   if (!plan) return fail(RS2_E_INVALID_ARGUMENT, "null plan");
@@ -3295,6 +3357,161 @@ int verifier_mark_done(rs2_verifier* v, hipStream_t st) {
   HIP_TRY(hipEventRecord(v->done, st));
   return RS2_OK;
 }
+
+// Merkle roots of `count` back-to-back slivers into d_roots (32 B each), on st.
+int verifier_roots(rs2_verifier* v, uint32_t count, const uint8_t* d_slivers, uint8_t* d_roots,
+                   hipStream_t st) {
+  RS2_TRY(verifier_leaves(v, count, d_slivers, st));
+  uint8_t* scratch = nullptr;
+  if (const size_t sb = tree_scratch_bytes(count, v->n)) {
+    HIP_TRY(v->tree_scratch.ensure(sb));
+    scratch = v->tree_scratch.as<uint8_t>();
+  }
+  HIP_TRY(rs2k_launch_merkle_trees(v->leaves.as<uint8_t>(), int(v->n), int(count), 0,
+                                   int64_t(v->n) * 32, 32, 0, 0, d_roots, 32, st, nullptr, 0, 1, 0,
+                                   0, scratch));
+  return RS2_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// sliver recovery: many slivers of the verifier's axis, a received symbol set per sliver
+// ---------------------------------------------------------------------------------------------
+std::atomic<uint64_t> g_recover_launches{0}, g_recover_batched{0}, g_recover_single{0};
+
+// One validated sliver of a recovery call: its slot in the call, its first symbol in the call's
+// symbol buffer and the symbols it is recovered from (select_recovery_symbols).
+struct RecoverItem {
+  uint32_t slot = 0;
+  size_t first = 0;
+  std::vector<std::pair<uint16_t, uint32_t>> chosen;
+};
+
+// The per-sliver rules of a recovery call for every sliver (status_out as for
+// rs2_decode_batch_device_async): the accepted slivers in `items`, in slot order.
+int validate_recovery(const rs2_verifier* v, uint32_t n_slivers, const uint32_t* counts,
+                      const uint16_t* symbol_idx, int* status_out, std::vector<RecoverItem>& items) {
+  items.clear();
+  items.reserve(n_slivers);
+  size_t first = 0;
+  for (uint32_t i = 0; i < n_slivers; first += counts[i], ++i) {
+    RecoverItem it;
+    it.slot = i;
+    it.first = first;
+    const int rc = select_recovery_symbols(v->k, v->n, counts[i], symbol_idx + first, it.chosen);
+    if (status_out)
+      status_out[i] = rc;
+    else if (rc != RS2_OK)
+      return rc;
+    if (rc == RS2_OK) items.push_back(std::move(it));
+  }
+  return RS2_OK;
+}
+
+// Recover validated slivers (slot order) on st: windows of at most a chunk's jobs are planned on
+// the host pool; a window's eligible slivers leave in chunks (one launch each, one line per
+// job), the others through the per-pattern decode; then the window's roots and verdicts.
+// Slots of the call that are not in `items` were refused: their verdict is RS2_SLIVER_SKIPPED.
+int recover_items(rs2_verifier* v, uint32_t n_slivers, const std::vector<RecoverItem>& items,
+                  const uint8_t* d_symbols, const uint8_t* expected_roots, uint8_t* d_out,
+                  uint8_t* d_roots, int32_t* d_verdict, hipStream_t st) {
+  Context* ctx = v->ctx;
+  const int64_t s = v->s, K = v->k;
+  const size_t sliver_len = size_t(K) * size_t(s);
+  // a previous call on another stream still owns the scratch buffers (verifier_mark_done)
+  if (v->done) HIP_TRY(hipStreamWaitEvent(st, v->done, 0));
+  const bool want_roots = d_roots || expected_roots;
+  size_t next_item = 0;
+  for (uint32_t w0 = 0; w0 < n_slivers; w0 += uint32_t(kBatchChunkJobs)) {
+    const uint32_t w1 = uint32_t(std::min<size_t>(n_slivers, size_t(w0) + kBatchChunkJobs));
+    const size_t i0 = next_item;
+    while (next_item < items.size() && items[next_item].slot < w1) ++next_item;
+    const size_t cnt = next_item - i0;
+    std::vector<BatchBlob> jobs(cnt);
+    std::vector<DecodeSpec> specs(cnt);
+    const auto host_t0 = std::chrono::steady_clock::now();
+    if (cnt) {
+      const size_t T = std::min<size_t>(size_t(ctx->pool.threads()), cnt);
+      std::vector<std::function<void()>> tasks;
+      for (size_t t = 0; t < T; ++t)
+        tasks.emplace_back([&, t] {
+          for (size_t i = t; i < cnt; i += T) {
+            const RecoverItem& it = items[i0 + i];
+            DecodeSpec& sp = specs[i];
+            sliver_recover_spec(uint32_t(K), v->n, int(s), it.chosen, d_symbols + it.first * s,
+                                d_out + size_t(it.slot) * sliver_len, decode_may_fuse(), sp);
+            uint32_t originals = 0;
+            for (uint32_t q = 0; q < sp.K; ++q) originals += sp.present[q] >= 0;
+            if (originals < sp.K) plan_batch_spec(sp, originals, jobs[i]);
+          }
+        });
+      ctx->pool.run(tasks);
+    }
+    prof_host(&v->prof, "rec_plan_host", host_t0);
+    std::vector<BatchBlob*> ch;
+    size_t tab_bytes = 0;
+    for (size_t i = 0; i <= cnt; ++i) {
+      BatchBlob* bb = i < cnt && jobs[i].eligible ? &jobs[i] : nullptr;
+      if (bb && !ch.empty() && (bb->C != ch[0]->C || bb->job.pairs_span != ch[0]->job.pairs_span))
+        bb->eligible = false, bb = nullptr;
+      const size_t need = bb ? bb->logs.size() * kTabU16 * 2 : 0;
+      if (!ch.empty() && (i == cnt || (bb && tab_bytes + need > kBatchTableBytes))) {
+        RS2_TRY(launch_batch_chunk(ctx, v->rbatch, v->rbatch_slot, ch, 1, &v->prof, st));
+        g_recover_launches.fetch_add(1, std::memory_order_relaxed);
+        g_recover_batched.fetch_add(ch.size(), std::memory_order_relaxed);
+        ch.clear();
+        tab_bytes = 0;
+      }
+      if (bb) {
+        ch.push_back(bb);
+        tab_bytes += need;
+      }
+    }
+    for (size_t i = 0; i < cnt; ++i) {
+      if (jobs[i].eligible) continue;
+      RS2_TRY(run_decode(ctx, v->rdec, v->rdec_slot, specs[i], {}, decode_may_fuse(), 1,
+                         &v->prof, st));
+      g_recover_single.fetch_add(1, std::memory_order_relaxed);
+    }
+    if (!want_roots) continue;
+    mark(&v->prof, "", st);
+    // roots of the window's recovered slivers, in runs of neighbouring slots (a refused sliver
+    // leaves a gap: its output was not written and its root slot is not either)
+    uint8_t* roots = d_roots ? d_roots + size_t(w0) * 32 : nullptr;  // of slot w0
+    if (!roots) {
+      HIP_TRY(v->window_roots.ensure(kBatchChunkJobs * 32));
+      roots = v->window_roots.as<uint8_t>();
+    }
+    if (cnt) {  // the hashing scratch once, for the longest run: no run regrows it in flight
+      HIP_TRY(v->leaves.ensure(cnt * size_t(v->n) * 32));
+      HIP_TRY(v->repair.ensure(cnt * size_t(v->n - v->k) * size_t(s)));
+      if (const size_t sb = tree_scratch_bytes(int64_t(cnt), v->n))
+        HIP_TRY(v->tree_scratch.ensure(sb));
+    }
+    for (size_t a = 0; a < cnt;) {
+      size_t b = a + 1;
+      while (b < cnt && items[i0 + b].slot == items[i0 + b - 1].slot + 1) ++b;
+      const uint32_t slot = items[i0 + a].slot;
+      RS2_TRY(verifier_roots(v, uint32_t(b - a), d_out + size_t(slot) * sliver_len,
+                             roots + size_t(slot - w0) * 32, st));
+      a = b;
+    }
+    mark(&v->prof, "rec_roots", st);
+    if (!expected_roots) continue;
+    // expected roots and skip mask of the window through one upload slot
+    const uint32_t wn = w1 - w0;
+    const size_t mask_at = size_t(wn) * 32;
+    std::vector<uint8_t> up(mask_at + wn, 1);
+    std::memcpy(up.data(), expected_roots + size_t(w0) * 32, mask_at);
+    for (size_t i = 0; i < cnt; ++i) up[mask_at + (items[i0 + i].slot - w0)] = 0;
+    HIP_TRY(v->verdict_in.ensure(kBatchChunkJobs * 33));
+    RS2_TRY(upload_pieces(ctx, v->verdict_in.p, up.data(), up.size(), st));
+    HIP_TRY(rs2k_launch_sliver_verdict(roots, v->verdict_in.as<uint8_t>(),
+                                       v->verdict_in.as<uint8_t>() + mask_at, int(wn),
+                                       d_verdict + w0, st));
+    mark(&v->prof, "rec_verdict", st);
+  }
+  return RS2_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -3307,17 +3524,203 @@ int rs2_verifier_roots_device_async(rs2_verifier* v, uint32_t count, const void*
   if (count == 0) return RS2_OK;
   HIP_TRY(hipSetDevice(v->ctx->device));
   hipStream_t st = abi_stream(stream, v->stream);
-  RS2_TRY(verifier_leaves(v, count, reinterpret_cast<const uint8_t*>(d_slivers), st));
-  uint8_t* scratch = nullptr;
-  if (const size_t sb = tree_scratch_bytes(count, v->n)) {
-    HIP_TRY(v->tree_scratch.ensure(sb));
-    scratch = v->tree_scratch.as<uint8_t>();
-  }
-  HIP_TRY(rs2k_launch_merkle_trees(v->leaves.as<uint8_t>(), int(v->n), int(count), 0,
-                                   int64_t(v->n) * 32, 32, 0, 0,
-                                   reinterpret_cast<uint8_t*>(d_roots), 32, st, nullptr, 0, 1, 0,
-                                   0, scratch));
+  RS2_TRY(verifier_roots(v, count, reinterpret_cast<const uint8_t*>(d_slivers),
+                         reinterpret_cast<uint8_t*>(d_roots), st));
   return verifier_mark_done(v, st);
+}
+
+int rs2_verifier_recover_slivers_device_async(rs2_verifier* v, uint32_t n_slivers,
+                                              const uint32_t* counts, const uint16_t* symbol_idx,
+                                              const void* d_symbols, const uint8_t* expected_roots,
+                                              void* d_slivers_out, void* d_roots, void* d_verdict,
+                                              int* status_out, void* stream) {
+  if (!v) return fail(RS2_E_INVALID_ARGUMENT, "null verifier");
+  if (n_slivers == 0) return RS2_OK;
+  if (n_slivers > 65535) return fail(RS2_E_INVALID_ARGUMENT, "more than 65535 slivers in a call");
+  if (!counts || !d_slivers_out) return fail(RS2_E_INVALID_ARGUMENT, "null argument");
+  size_t total = 0;
+  for (uint32_t i = 0; i < n_slivers; ++i) total += counts[i];
+  if (total && (!symbol_idx || !d_symbols)) return fail(RS2_E_INVALID_ARGUMENT, "null argument");
+  if (expected_roots ? !d_verdict : d_verdict != nullptr)
+    return fail(RS2_E_INVALID_ARGUMENT, "expected_roots and d_verdict go together");
+  RS2_TRY(check_symbol_ptr(d_symbols, "d_symbols"));
+  RS2_TRY(check_symbol_ptr(d_slivers_out, "d_slivers_out"));
+  RS2_TRY(check_digest_ptr(d_roots, "d_roots"));
+  RS2_TRY(check_digest_ptr(d_verdict, "d_verdict"));
+  if (v->n <= v->k) return fail(RS2_E_INCOMPATIBLE_PARAMETERS, "no repair symbols");
+  HIP_TRY(hipSetDevice(v->ctx->device));
+  // every sliver is validated before anything is enqueued
+  std::vector<RecoverItem> items;
+  RS2_TRY(validate_recovery(v, n_slivers, counts, symbol_idx, status_out, items));
+  hipStream_t st = abi_stream(stream, v->stream);
+  RS2_TRY(recover_items(v, n_slivers, items, reinterpret_cast<const uint8_t*>(d_symbols),
+                        expected_roots, reinterpret_cast<uint8_t*>(d_slivers_out),
+                        reinterpret_cast<uint8_t*>(d_roots), reinterpret_cast<int32_t*>(d_verdict),
+                        st));
+  return verifier_mark_done(v, st);
+}
+
+int rs2_recover_slivers(uint16_t n_shards, uint16_t symbol_size, int axis, uint32_t n_slivers,
+                        const uint32_t* counts, const uint16_t* symbol_idx,
+                        const uint8_t* const* symbols, const uint8_t* expected_roots,
+                        uint8_t* const* slivers_out, uint8_t* roots_out, int32_t* verdict_out,
+                        int* status_out) {
+  if (n_slivers == 0) return RS2_OK;
+  if (n_slivers > 65535) return fail(RS2_E_INVALID_ARGUMENT, "more than 65535 slivers in a call");
+  if (!counts || !slivers_out) return fail(RS2_E_INVALID_ARGUMENT, "null argument");
+  if (expected_roots ? !verdict_out : verdict_out != nullptr)
+    return fail(RS2_E_INVALID_ARGUMENT, "expected_roots and verdict_out go together");
+  size_t total = 0;
+  for (uint32_t i = 0; i < n_slivers; ++i) total += counts[i];
+  if (total && (!symbol_idx || !symbols)) return fail(RS2_E_INVALID_ARGUMENT, "null argument");
+  VerifierLease lease;
+  RS2_TRY(lease.get(n_shards, symbol_size, axis));
+  rs2_verifier* v = lease.v;
+  if (v->n <= v->k) return fail(RS2_E_INCOMPATIBLE_PARAMETERS, "no repair symbols");
+  std::vector<RecoverItem> items;
+  RS2_TRY(validate_recovery(v, n_slivers, counts, symbol_idx, status_out, items));
+  for (const RecoverItem& it : items) {
+    if (!slivers_out[it.slot]) return fail(RS2_E_INVALID_ARGUMENT, "null output sliver");
+    for (const auto& c : it.chosen)
+      if (!symbols[it.first + c.second]) return fail(RS2_E_INVALID_ARGUMENT, "null symbol");
+  }
+  HIP_TRY(hipSetDevice(v->ctx->device));
+  hipStream_t st = v->stream;
+  const size_t s = symbol_size, K = v->k, len = K * s;
+  // only the chosen symbols go up, K per accepted sliver, back to back; one H2D
+  const size_t in_b = items.size() * len;
+  const size_t out_b = size_t(n_slivers) * len, roots_at = (out_b + 15) / 16 * 16;
+  const size_t verdict_at = roots_at + size_t(n_slivers) * 32;
+  const size_t back_b = verdict_at + size_t(n_slivers) * 4;
+  HIP_TRY(v->input.ensure(std::max<size_t>(in_b, 16)));
+  HIP_TRY(v->sym_out.ensure(back_b));
+  HIP_TRY(v->h_in.ensure(std::max<size_t>(in_b, 16)));
+  HIP_TRY(v->h_out.ensure(back_b));
+  std::vector<RecoverItem> part = items;
+  for (size_t i = 0; i < part.size(); ++i) {
+    RecoverItem& it = part[i];
+    for (size_t q = 0; q < K; ++q) {
+      std::memcpy(static_cast<uint8_t*>(v->h_in.p) + (i * K + q) * s,
+                  symbols[it.first + it.chosen[q].second], s);
+      it.chosen[q].second = uint32_t(q);
+    }
+    it.first = i * K;
+  }
+  if (in_b) HIP_TRY(hipMemcpyAsync(v->input.p, v->h_in.p, in_b, hipMemcpyHostToDevice, st));
+  uint8_t* dout = v->sym_out.as<uint8_t>();
+  const bool roots = roots_out || expected_roots;
+  RS2_TRY(recover_items(v, n_slivers, part, v->input.as<uint8_t>(), expected_roots, dout,
+                        roots ? dout + roots_at : nullptr,
+                        expected_roots ? reinterpret_cast<int32_t*>(dout + verdict_at) : nullptr,
+                        st));
+  RS2_TRY(verifier_mark_done(v, st));
+  // one D2H of slivers, roots and verdicts; slots of refused slivers are not copied out
+  HIP_TRY(hipMemcpyAsync(v->h_out.p, dout, back_b, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  const uint8_t* ho = static_cast<const uint8_t*>(v->h_out.p);
+  for (const RecoverItem& it : items) {
+    std::memcpy(slivers_out[it.slot], ho + size_t(it.slot) * len, len);
+    if (roots_out)
+      std::memcpy(roots_out + size_t(it.slot) * 32, ho + roots_at + size_t(it.slot) * 32, 32);
+  }
+  if (verdict_out) std::memcpy(verdict_out, ho + verdict_at, size_t(n_slivers) * 4);
+  return RS2_OK;
+}
+
+int rs2_recover_stats(uint64_t* stats_out) {
+  if (!stats_out) return fail(RS2_E_INVALID_ARGUMENT, "null argument");
+  stats_out[0] = g_recover_launches.load(std::memory_order_relaxed);
+  stats_out[1] = g_recover_batched.load(std::memory_order_relaxed);
+  stats_out[2] = g_recover_single.load(std::memory_order_relaxed);
+  return RS2_OK;
+}
+
+int rs2_verifier_check_recovery_symbols_device_async(rs2_verifier* v, uint32_t n_slivers,
+                                                     const uint32_t* counts,
+                                                     const uint16_t* target_index,
+                                                     const void* d_symbols, const void* d_proofs,
+                                                     const void* d_expected_roots, void* d_ok,
+                                                     void* stream) {
+  if (!v) return fail(RS2_E_INVALID_ARGUMENT, "null verifier");
+  if (n_slivers == 0) return RS2_OK;
+  if (n_slivers > 65535) return fail(RS2_E_INVALID_ARGUMENT, "more than 65535 slivers in a call");
+  if (!counts || !target_index) return fail(RS2_E_INVALID_ARGUMENT, "null argument");
+  const int L = merkle_path_len(v->n);
+  uint64_t total = 0;
+  uint32_t max_count = 0;
+  std::vector<uint32_t> per(size_t(n_slivers) * 2);
+  for (uint32_t i = 0; i < n_slivers; ++i) {
+    if (target_index[i] >= v->n)  // merkle.rs verify_proof: the leaf index is below n_leaves
+      return fail(RS2_E_INVALID_ARGUMENT, "target index too large");
+    per[2 * i] = uint32_t(total);
+    per[2 * i + 1] = target_index[i];
+    total += counts[i];
+    max_count = std::max(max_count, counts[i]);
+    if (total > 0x7FFFFFFFu) return fail(RS2_E_INVALID_ARGUMENT, "too many symbols in a call");
+  }
+  if (total == 0) return RS2_OK;
+  if (!d_symbols || !d_expected_roots || !d_ok || (L && !d_proofs))
+    return fail(RS2_E_INVALID_ARGUMENT, "null argument");
+  RS2_TRY(check_symbol_ptr(d_symbols, "d_symbols"));
+  RS2_TRY(check_digest_ptr(d_proofs, "d_proofs"));
+  RS2_TRY(check_digest_ptr(d_expected_roots, "d_expected_roots"));
+  RS2_TRY(check_digest_ptr(d_ok, "d_ok"));
+  HIP_TRY(hipSetDevice(v->ctx->device));
+  hipStream_t st = abi_stream(stream, v->stream);
+  if (v->done) HIP_TRY(hipStreamWaitEvent(st, v->done, 0));
+  HIP_TRY(v->sym_digests.ensure(size_t(total) * 32));
+  HIP_TRY(v->per_sliver.ensure(per.size() * 4));
+  RS2_TRY(upload_pieces(v->ctx, v->per_sliver.p, per.data(), per.size() * 4, st));
+  SymbolMap map{reinterpret_cast<const uint8_t*>(d_symbols), nullptr, nullptr, 0, 0, 0, int(v->s)};
+  HIP_TRY(rs2k_launch_leaf_hash(map, 1, int64_t(total), 1, v->sym_digests.as<uint8_t>(), st));
+  HIP_TRY(rs2k_launch_recovery_proof_check(
+      v->sym_digests.as<uint8_t>(), v->per_sliver.as<uint32_t>(), int(n_slivers), max_count,
+      uint32_t(total), reinterpret_cast<const uint8_t*>(d_proofs), L,
+      reinterpret_cast<const uint8_t*>(d_expected_roots), reinterpret_cast<uint8_t*>(d_ok), st));
+  return verifier_mark_done(v, st);
+}
+
+int rs2_check_recovery_symbols(uint16_t n_shards, uint16_t symbol_size, int axis,
+                               uint32_t n_slivers, const uint32_t* counts,
+                               const uint16_t* target_index, const uint8_t* symbols,
+                               const uint8_t* proofs, const uint8_t* expected_roots,
+                               uint8_t* ok_out) {
+  if (n_slivers == 0) return RS2_OK;
+  if (!counts || !target_index) return fail(RS2_E_INVALID_ARGUMENT, "null argument");
+  size_t total = 0;
+  for (uint32_t i = 0; i < n_slivers; ++i) total += counts[i];
+  VerifierLease lease;
+  RS2_TRY(lease.get(n_shards, symbol_size, axis));
+  rs2_verifier* v = lease.v;
+  const size_t L = size_t(merkle_path_len(n_shards));
+  if (total && (!symbols || !expected_roots || !ok_out || (L && !proofs)))
+    return fail(RS2_E_INVALID_ARGUMENT, "null argument");
+  HIP_TRY(hipSetDevice(v->ctx->device));
+  hipStream_t st = v->stream;
+  // symbols, proofs and expected roots through one pinned buffer: one H2D
+  const size_t sym_b = total * symbol_size, prf_at = (sym_b + 15) / 16 * 16;
+  const size_t exp_at = prf_at + total * L * 32, ok_at = exp_at + total * 32;
+  const size_t all_b = ok_at + (total + 15) / 16 * 16;
+  HIP_TRY(v->input.ensure(std::max<size_t>(all_b, 16)));
+  HIP_TRY(v->h_in.ensure(std::max<size_t>(ok_at, 16)));
+  HIP_TRY(v->h_out.ensure(std::max<size_t>(total, 16)));
+  uint8_t* hi = static_cast<uint8_t*>(v->h_in.p);
+  if (total) {
+    std::memcpy(hi, symbols, sym_b);
+    if (L) std::memcpy(hi + prf_at, proofs, total * L * 32);
+    std::memcpy(hi + exp_at, expected_roots, total * 32);
+    HIP_TRY(hipMemcpyAsync(v->input.p, hi, ok_at, hipMemcpyHostToDevice, st));
+  }
+  uint8_t* d = v->input.as<uint8_t>();
+  RS2_TRY(rs2_verifier_check_recovery_symbols_device_async(v, n_slivers, counts, target_index, d,
+                                                           d + prf_at, d + exp_at, d + ok_at,
+                                                           nullptr));
+  if (total) {
+    HIP_TRY(hipMemcpyAsync(v->h_out.p, d + ok_at, total, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    std::memcpy(ok_out, v->h_out.p, total);
+  }
+  return RS2_OK;
 }
 
 int rs2_verifier_recovery_symbols_device_async(rs2_verifier* v, uint32_t count,

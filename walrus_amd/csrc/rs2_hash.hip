@@ -994,6 +994,66 @@ __global__ void __launch_bounds__(64)
   sfor<8>([&](auto jj) { o[decltype(jj)::value] = cur[decltype(jj)::value]; });
 }
 
+// RecoverySymbol::verify's proof step (symbols.rs:617-642, merkle.rs:78-99,150-169) for the
+// received symbols of many slivers: sliver y's symbols are consecutive from symbol first[y]
+// (per_sliver[y] = {first, target}; its count is the next sliver's first, or `total`), and all
+// of them authenticate leaf `target` of their own source sliver's tree.  One lane per symbol:
+// start from the symbol's leaf digest, climb its path like proof_root_kernel, compare with its
+// expected root, store one byte.  The root stays in registers.
+__global__ void __launch_bounds__(64)
+    recovery_proof_check_kernel(const uint8_t* __restrict__ leaf_digests,
+                                const uint2* __restrict__ per_sliver, int n_slivers,
+                                uint32_t total, const uint8_t* __restrict__ paths, int path_len,
+                                const uint8_t* __restrict__ expected, uint8_t* __restrict__ ok) {
+  const int y = blockIdx.y;
+  const uint2 ps = per_sliver[y];
+  const uint32_t end = y + 1 < n_slivers ? per_sliver[y + 1].x : total;
+  const uint32_t w = blockIdx.x * 64 + threadIdx.x;
+  if (ps.x > end || w >= end - ps.x) return;
+  const int64_t r = int64_t(ps.x) + w;
+  uint32_t cur[8];
+  const uint32_t* lf = reinterpret_cast<const uint32_t*>(leaf_digests + r * 32);
+  sfor<8>([&](auto jj) { cur[decltype(jj)::value] = lf[decltype(jj)::value]; });
+  uint32_t idx = ps.y;
+  for (int l = 0; l < path_len; ++l) {
+    const uint32_t* sb = reinterpret_cast<const uint32_t*>(paths + (r * path_len + l) * 32);
+    uint32_t d[16], o[8];
+    const bool right = idx & 1u;
+    sfor<8>([&](auto jj) {
+      constexpr int j = decltype(jj)::value;
+      d[j] = right ? sb[j] : cur[j];
+      d[j + 8] = right ? cur[j] : sb[j];
+    });
+    b2_hash65(1u, d, o);
+    sfor<8>([&](auto jj) { cur[decltype(jj)::value] = o[decltype(jj)::value]; });
+    idx >>= 1;
+  }
+  const uint32_t* ex = reinterpret_cast<const uint32_t*>(expected + r * 32);
+  uint32_t diff = 0;
+  sfor<8>([&](auto jj) { diff |= cur[decltype(jj)::value] ^ ex[decltype(jj)::value]; });
+  ok[r] = diff == 0 ? 1 : 0;
+}
+
+// Verdicts of a recovery call's slivers (rs2_verifier_recover_slivers_device_async): slot i was
+// refused on the host (skipped[i] != 0: RS2_SLIVER_SKIPPED, its root slot is never read), or its
+// recovered sliver's root (roots + 32 i) equals the expected one (expected + 32 i) or not.
+__global__ void __launch_bounds__(64)
+    sliver_verdict_kernel(const uint8_t* __restrict__ roots, const uint8_t* __restrict__ expected,
+                          const uint8_t* __restrict__ skipped, int count,
+                          int32_t* __restrict__ verdict) {
+  const int i = blockIdx.x * 64 + threadIdx.x;
+  if (i >= count) return;
+  if (skipped[i]) {
+    verdict[i] = 2;
+    return;
+  }
+  const uint32_t* a = reinterpret_cast<const uint32_t*>(roots + int64_t(i) * 32);
+  const uint32_t* b = reinterpret_cast<const uint32_t*>(expected + int64_t(i) * 32);
+  uint32_t diff = 0;
+  sfor<8>([&](auto jj) { diff |= a[decltype(jj)::value] ^ b[decltype(jj)::value]; });
+  verdict[i] = diff == 0 ? 1 : 0;
+}
+
 // Node j of level L of the tree over n pair leaves (pair q = 64 bytes at pair_hashes + 64 q,
 // leaf-hashed with prefix 0x00), computed in registers (see fold_node).
 template <int L>
@@ -1260,6 +1320,30 @@ hipError_t rs2k_launch_proof_roots(const uint8_t* d_leaf_digests, const uint32_t
   if (count <= 0) return hipSuccess;
   hipLaunchKernelGGL(rs2::proof_root_kernel, dim3(unsigned((count + 63) / 64)), dim3(64), 0, stream,
                      d_leaf_digests, d_leaf_index, d_paths, path_len, count, d_roots);
+  return hipGetLastError();
+}
+
+hipError_t rs2k_launch_recovery_proof_check(const uint8_t* d_leaf_digests,
+                                            const uint32_t* d_per_sliver, int n_slivers,
+                                            uint32_t max_count, uint32_t total,
+                                            const uint8_t* d_paths, int path_len,
+                                            const uint8_t* d_expected, uint8_t* d_ok,
+                                            hipStream_t stream) {
+  if (n_slivers <= 0 || max_count == 0) return hipSuccess;
+  if (n_slivers > 65535) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(rs2::recovery_proof_check_kernel,
+                     dim3((max_count + 63) / 64, unsigned(n_slivers)), dim3(64), 0, stream,
+                     d_leaf_digests, reinterpret_cast<const uint2*>(d_per_sliver), n_slivers, total,
+                     d_paths, path_len, d_expected, d_ok);
+  return hipGetLastError();
+}
+
+hipError_t rs2k_launch_sliver_verdict(const uint8_t* d_roots, const uint8_t* d_expected,
+                                      const uint8_t* d_skipped, int count, int32_t* d_verdict,
+                                      hipStream_t stream) {
+  if (count <= 0) return hipSuccess;
+  hipLaunchKernelGGL(rs2::sliver_verdict_kernel, dim3(unsigned((count + 63) / 64)), dim3(64), 0,
+                     stream, d_roots, d_expected, d_skipped, count, d_verdict);
   return hipGetLastError();
 }
 

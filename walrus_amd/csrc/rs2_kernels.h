@@ -58,6 +58,17 @@ hipError_t rs2k_launch_proof_gather(const uint8_t* d_sys, const uint8_t* d_rep, 
 hipError_t rs2k_launch_proof_roots(const uint8_t* d_leaf_digests, const uint32_t* d_leaf_index,
                                    const uint8_t* d_paths, int path_len, int count,
                                    uint8_t* d_roots, hipStream_t stream);
+// d_per_sliver: n_slivers x {first symbol, target index} (uint32 pairs); max_count: the largest
+// symbol count of a sliver (grid.x); total: symbols of the call
+hipError_t rs2k_launch_recovery_proof_check(const uint8_t* d_leaf_digests,
+                                            const uint32_t* d_per_sliver, int n_slivers,
+                                            uint32_t max_count, uint32_t total,
+                                            const uint8_t* d_paths, int path_len,
+                                            const uint8_t* d_expected, uint8_t* d_ok,
+                                            hipStream_t stream);
+hipError_t rs2k_launch_sliver_verdict(const uint8_t* d_roots, const uint8_t* d_expected,
+                                      const uint8_t* d_skipped, int count, int32_t* d_verdict,
+                                      hipStream_t stream);
 hipError_t rs2k_launch_merkle_root(const uint8_t* d_pair_hashes, int n, uint64_t blob_len,
                                    uint8_t* d_blob_id, hipStream_t stream, int n_blobs = 1,
                                    const uint64_t* d_blob_lens = nullptr);

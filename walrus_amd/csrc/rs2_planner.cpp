@@ -595,4 +595,45 @@ void pack_batch_job(const PlannedJob& pj, CodecJobBatch& out, std::vector<uint16
                 mix.begin() + (size_t(o) * MB + i) * row);
 }
 
+int select_recovery_symbols(uint32_t k, uint32_t n, uint32_t count, const uint16_t* idx,
+                            std::vector<std::pair<uint16_t, uint32_t>>& chosen) {
+  chosen.clear();
+  if (count < k) return fail(RS2_E_DECODING_UNSUCCESSFUL, "fewer recovery symbols than the sliver has");
+  std::vector<uint8_t> seen(n, 0);
+  for (uint32_t i = 0; i < count && chosen.size() < k; ++i) {
+    const uint16_t q = idx[i];
+    if (q >= n || seen[q]) continue;  // invalid indices are ignored by the crate
+    seen[q] = 1;
+    chosen.emplace_back(q, i);
+  }
+  if (chosen.size() < k) {
+    chosen.clear();
+    return fail(RS2_E_NOT_ENOUGH_SHARDS, "not enough shards");
+  }
+  return RS2_OK;
+}
+
+void sliver_recover_spec(uint32_t k, uint32_t n, int symbol_size,
+                         const std::vector<std::pair<uint16_t, uint32_t>>& chosen,
+                         const uint8_t* src, uint8_t* dst, bool may_fuse, DecodeSpec& sp) {
+  const int64_t s = symbol_size;
+  sp.K = k;
+  sp.R = n - k;
+  sp.symbol_size = symbol_size;
+  sp.present.assign(n, -1);
+  uint32_t originals = 0;
+  for (const auto& c : chosen) {
+    sp.present[c.first] = int64_t(c.second) * s;
+    originals += c.first < k;
+  }
+  sp.src_base = src;
+  sp.src_ls = 0;
+  sp.dst_base = dst;
+  sp.dst_ls = 0;
+  sp.dst.resize(k);
+  for (uint32_t i = 0; i < k; ++i) sp.dst[i] = int64_t(i) * s;
+  sp.dst_limit = int64_t(k) * s;
+  sp.copy_present = originals > 0 && symbol_size >= 4 && may_fuse;
+}
+
 }  // namespace rs2

@@ -7,6 +7,7 @@
 #include <algorithm>
 #include <cstdint>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/walrus_rs2.h"
@@ -283,5 +284,24 @@ bool batch_eligible(const PlannedJob& pj, bool fused);
 // (table (o, b, k) at ((o * kBatchBlocks + b) * 2 + k) * kTabU16), or nothing when the plan has
 // none.  The caller checked batch_eligible.
 void pack_batch_job(const PlannedJob& pj, CodecJobBatch& out, std::vector<uint16_t>& mix);
+
+// ---------------------------------------------------------------------------------------------
+// sliver recovery (rs2_recover_slivers, rs2_verifier_recover_slivers_device_async): a sliver is
+// one line of a 1D code, K = its symbols, recovered from `count` received symbols
+// ---------------------------------------------------------------------------------------------
+// The symbols a recovery uses, as (index, position in idx) in the caller's order.  Fewer than k
+// entries: RS2_E_DECODING_UNSUCCESSFUL (slivers.rs:246-289).  Otherwise rs2_decode_1d's rules:
+// entries are taken in order, duplicates and indices >= n are ignored, the first k distinct ones
+// are used; fewer than k distinct: RS2_E_NOT_ENOUGH_SHARDS.
+int select_recovery_symbols(uint32_t k, uint32_t n, uint32_t count, const uint16_t* idx,
+                            std::vector<std::pair<uint16_t, uint32_t>>& chosen);
+
+// The decode of one sliver from its chosen symbols: the received symbols are back to back from
+// `src` (symbol at position p at p * s), the sliver's k symbols back to back from `dst`, bytes
+// from k * s on never written.  copy_present: an original is among the chosen symbols, s >= 4
+// and the fused copy-out is allowed (`may_fuse`), as for a blob of a decode batch.
+void sliver_recover_spec(uint32_t k, uint32_t n, int symbol_size,
+                         const std::vector<std::pair<uint16_t, uint32_t>>& chosen,
+                         const uint8_t* src, uint8_t* dst, bool may_fuse, DecodeSpec& sp);
 
 }  // namespace rs2

@@ -795,6 +795,58 @@ class SliverVerifier:
             self.handle, count, d_slivers, tg, d_symbols, d_proofs, d_nodes or None,
             _stream(stream)))
 
+    def recover_slivers_async(self, index_lists: Sequence[Sequence[int]], d_symbols: int,
+                              d_slivers_out: int, expected_roots: Optional[bytes] = None,
+                              d_roots: int = 0, d_verdict: int = 0,
+                              stream: Optional[int] = None, statuses: bool = False):
+        """rs2_verifier_recover_slivers_device_async: sliver i is recovered from the received
+        symbols whose source indices are index_lists[i], their data back to back in d_symbols in
+        the same order.  With `statuses` the per-sliver codes are returned and failing slivers
+        skipped; without, the first failure raises and nothing is enqueued."""
+        m = len(index_lists)
+        counts = (ctypes.c_uint32 * max(m, 1))(*[len(x) for x in index_lists])
+        flat = [i for x in index_lists for i in x]
+        idx = (ctypes.c_uint16 * max(len(flat), 1))(*flat)
+        exp = None
+        if expected_roots is not None:
+            exp = (ctypes.c_uint8 * max(len(expected_roots), 1)).from_buffer_copy(
+                bytes(expected_roots) or b"\0")
+        st = (ctypes.c_int * max(m, 1))() if statuses else None
+        rc = _lib.lib().rs2_verifier_recover_slivers_device_async(
+            self.handle, m, counts, idx, d_symbols or None, exp, d_slivers_out or None,
+            d_roots or None, d_verdict or None, st, _stream(stream))
+        if statuses:
+            _ok(rc)
+            return list(st)[:m]
+        return rc
+
+    def check_recovery_symbols_async(self, counts: Sequence[int], targets: Sequence[int],
+                                     d_symbols: int, d_proofs: int, d_expected_roots: int,
+                                     d_ok: int, stream: Optional[int] = None) -> int:
+        """rs2_verifier_check_recovery_symbols_device_async (returns the status code)."""
+        m = len(counts)
+        return _lib.lib().rs2_verifier_check_recovery_symbols_device_async(
+            self.handle, m, (ctypes.c_uint32 * max(m, 1))(*counts),
+            (ctypes.c_uint16 * max(m, 1))(*targets), d_symbols or None, d_proofs or None,
+            d_expected_roots or None, d_ok or None, _stream(stream))
+
+    def profile(self, enable: bool = True) -> None:
+        _ok(_lib.lib().rs2_verifier_profile_enable(self.handle, int(enable)))
+
+    def profile_read(self) -> dict:
+        """{stage: (total_ms, launches)} of the recovery calls since the last read
+        (synchronises)."""
+        m = 64
+        names = ctypes.create_string_buffer(32 * m)
+        ms = (ctypes.c_double * m)()
+        cnt = (ctypes.c_uint32 * m)()
+        k = ctypes.c_uint32()
+        _ok(_lib.lib().rs2_verifier_profile_read(self.handle, m, names, ms, cnt,
+                                                 ctypes.byref(k)))
+        raw = names.raw
+        return {raw[32 * i:32 * i + 32].split(b"\0")[0].decode(): (ms[i], cnt[i])
+                for i in range(k.value)}
+
     def __del__(self):
         h = getattr(self, "handle", None)
         if h and h.value and _lib._LIB is not None:
@@ -823,6 +875,14 @@ def decode_batch_stats() -> Dict[str, int]:
     batch calls that took the per-blob path (process-wide)."""
     out = (ctypes.c_uint64 * 3)()
     _ok(_lib.lib().rs2_decode_batch_stats(out))
+    return dict(zip(("launches", "batched", "single"), (int(v) for v in out)))
+
+
+def recover_stats() -> Dict[str, int]:
+    """rs2_recover_stats: batched sliver-recovery launches, slivers decoded inside them, and
+    slivers of recovery calls that took the per-sliver path (process-wide)."""
+    out = (ctypes.c_uint64 * 3)()
+    _ok(_lib.lib().rs2_recover_stats(out))
     return dict(zip(("launches", "batched", "single"), (int(v) for v in out)))
 
 

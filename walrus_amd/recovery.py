@@ -319,6 +319,99 @@ def recover_sliver_or_generate_inconsistency_proof(
     return sliver
 
 
+def verify_recovery_symbols(config, metadatas: Sequence[BlobMetadata], targets: Sequence[int],
+                            symbol_lists: Sequence[Sequence[RecoverySymbol]],
+                            axis: str = PRIMARY) -> List[List[bool]]:
+    """RecoverySymbol::verify (symbols.rs:617-642) for the received symbols of many slivers of
+    `axis`: request i's symbols (symbol_lists[i]) all claim to be symbol targets[i] of their
+    source sliver's expansion, under metadatas[i].  The index bound, symbol size and path length
+    are checked here; every remaining symbol's proof root is formed and compared on the device,
+    one rs2_check_recovery_symbols call per symbol size.  Returns one flag per symbol."""
+    n = config.n_shards
+    L = path_length(n)
+    orth = _ORTHOGONAL[axis]
+    out: List[List[bool]] = [[False] * len(sl) for sl in symbol_lists]
+    groups = {}
+    for i, (meta, tgt, syms) in enumerate(zip(metadatas, targets, symbol_lists)):
+        if tgt >= n:
+            continue  # LeafIndexOutOfBounds for every symbol of the request
+        s = config.symbol_size_for_blob(meta.unencoded_length)
+        ok = [j for j, r in enumerate(syms)
+              if r.index < n and len(r.data) == s and len(r.proof.path) == L]
+        if ok:
+            groups.setdefault(s, []).append((i, ok))
+    for s, members in groups.items():
+        m = len(members)
+        counts = (ctypes.c_uint32 * m)(*[len(ok) for _, ok in members])
+        tgts = (ctypes.c_uint16 * m)(*[targets[i] for i, _ in members])
+        picked = [(i, j, symbol_lists[i][j]) for i, ok in members for j in ok]
+        data = np.frombuffer(b"".join(bytes(r.data) for _, _, r in picked), dtype=np.uint8)
+        paths = np.frombuffer(b"".join(b"".join(r.proof.path) for _, _, r in picked) or b"\0" * 32,
+                              dtype=np.uint8)
+        roots = np.frombuffer(b"".join(bytes(_sliver_hash(metadatas[i], n, r.index, orth))
+                                       for i, _, r in picked), dtype=np.uint8)
+        flags = np.zeros(len(picked), dtype=np.uint8)
+        _ok(_lib.lib().rs2_check_recovery_symbols(n, s, _AXIS[axis], m, counts, tgts,
+                                                  data.ctypes.data, paths.ctypes.data,
+                                                  roots.ctypes.data, flags.ctypes.data))
+        for (i, j, _), f in zip(picked, flags):
+            out[i][j] = bool(f)
+    return out
+
+
+def recover_slivers_or_generate_inconsistency_proofs(config, requests, axis: str = PRIMARY):
+    """recover_sliver_or_generate_inconsistency_proof (slivers.rs:341-379) for many requests
+    (verified recovery symbols, target index, metadata) of one axis: the first
+    n_symbols_for_recovery symbols of each are decoded and the recovered slivers verified
+    against their metadata in one rs2_recover_slivers call per symbol size.  Per request: the
+    SliverData when it verifies, an InconsistencyProof on a Merkle-root mismatch, a
+    SliverRecoveryError instance when the decode was refused."""
+    n = config.n_shards
+    need = config.n_symbols_for_recovery(axis)
+    out: list = [None] * len(requests)
+    groups = {}
+    for i, (symbols, target, meta) in enumerate(requests):
+        if target >= len(meta.hashes):
+            raise ValueError("IndexTooLarge")
+        s = config.symbol_size_for_blob(meta.unencoded_length)
+        taken = []
+        for r in symbols:
+            if len(taken) == need:
+                break
+            taken.append(r)
+        if len(taken) < need:  # slivers.rs:246-289 refuses before decoding
+            out[i] = SliverRecoveryError("DecodingFailure")
+            continue
+        groups.setdefault(s, []).append((i, taken))
+    for s, members in groups.items():
+        m = len(members)
+        # wrong-size symbols are dropped by the decoder (basic_encoding.rs:400-410)
+        usable = [[r for r in taken if len(r.data) == s] for _, taken in members]
+        counts = (ctypes.c_uint32 * m)(*[len(u) for u in usable])
+        flat = [r for u in usable for r in u]
+        idx = (ctypes.c_uint16 * max(len(flat), 1))(*[r.index for r in flat])
+        keep = [np.frombuffer(bytes(r.data), dtype=np.uint8) for r in flat]
+        ptrs = (ctypes.c_void_p * max(len(flat), 1))(*[a.ctypes.data for a in keep])
+        expected = np.frombuffer(
+            b"".join(bytes(_sliver_hash(requests[i][2], n, requests[i][1], axis))
+                     for i, _ in members), dtype=np.uint8)
+        bufs = [np.zeros(need * s, dtype=np.uint8) for _ in members]
+        outs = (ctypes.c_void_p * m)(*[b.ctypes.data for b in bufs])
+        verdict = np.zeros(m, dtype=np.int32)
+        status = (ctypes.c_int * m)()
+        _ok(_lib.lib().rs2_recover_slivers(n, s, _AXIS[axis], m, counts, idx, ptrs,
+                                           expected.ctypes.data, outs, None, verdict.ctypes.data,
+                                           status))
+        for k, (i, taken) in enumerate(members):
+            if status[k] != _lib.RS2_OK or verdict[k] == _lib.RS2_SLIVER_SKIPPED:
+                out[i] = SliverRecoveryError("DecodingFailure")
+            elif verdict[k] == _lib.RS2_SLIVER_MATCH:
+                out[i] = SliverData(Symbols(bufs[k].tobytes(), s), requests[i][1], axis)
+            else:
+                out[i] = InconsistencyProof(axis, requests[i][1], taken)
+    return out
+
+
 def try_recover_sliver_from_decoding_symbols(decoding_symbols: Sequence[DecodingSymbol],
                                              target_index: int, metadata: BlobMetadata, config,
                                              axis: str = PRIMARY) -> SliverData:
