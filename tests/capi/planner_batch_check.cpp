@@ -3,6 +3,9 @@
 // by tests/test_planner_batch.py.  For every case it plans a decode into a fresh PlannedJob,
 // states the eligibility rule independently, and compares the packed CodecJobBatch and its
 // re-strided mixing tables with the planned job.  One line per case; a breach exits non-zero.
+// With a file argument (lines `k n limit s q0 q1 ...`, the k present shards of an n-shard code)
+// the cases are the file's patterns instead of the built-in ones, through the same checks, and
+// each line also reports how many output blocks the planner paired.
 #include "../../walrus_amd/csrc/rs2_planner.h"
 
 #include <cstdio>
@@ -91,13 +94,11 @@ void same_out(const OutBlock& a, const OutBlock& b, const char* label) {
 
 int g_cases = 0;
 
-void run_case(uint32_t n, int axis, uint32_t bm, int pat, uint64_t seed, int s) {
-  const uint32_t f = (n - 1) / 3, kp = n - 2 * f, ks = n - f, K = axis == 0 ? kp : ks;
-  char label[160];
-  std::snprintf(label, sizeof label, "n=%u axis=%d bm=%u s=%d pat=%s seed=%llu", n, axis, bm, s,
-                kPatternName[pat], static_cast<unsigned long long>(seed));
+// One decode of K of n shards from the shards `have` at block limit bm and symbol size s: plan,
+// rule, packed job.  `paired` adds the number of output blocks with a P/Q pair to the line.
+void check_pattern(const char* label, uint32_t n, uint32_t K, uint32_t bm, int s,
+                   const std::vector<uint32_t>& have, bool paired) {
   set_block_max(bm);
-  const std::vector<uint32_t> have = pattern(pat, n, K, seed);
   CHECK(have.size() == K);
   DecodeSpec sp;
   sp.K = K;
@@ -181,14 +182,76 @@ void run_case(uint32_t n, int axis, uint32_t bm, int pat, uint64_t seed, int s) 
           }
     }
   }
-  std::printf("%s n_in=%d n_out=%d originals=%u fused=%d eligible=%d\n", label, j.n_in, j.n_out,
+  std::printf("%s n_in=%d n_out=%d originals=%u fused=%d eligible=%d", label, j.n_in, j.n_out,
               originals, int(fused), int(got));
+  if (paired) {
+    int pairs = 0;
+    for (int o = 0; o < j.n_out; ++o) pairs += j.pair_nw[o] != 0;
+    std::printf(" paired=%d", pairs);
+  }
+  std::printf("\n");
   ++g_cases;
+}
+
+void run_case(uint32_t n, int axis, uint32_t bm, int pat, uint64_t seed, int s) {
+  const uint32_t f = (n - 1) / 3, kp = n - 2 * f, ks = n - f, K = axis == 0 ? kp : ks;
+  char label[160];
+  std::snprintf(label, sizeof label, "n=%u axis=%d bm=%u s=%d pat=%s seed=%llu", n, axis, bm, s,
+                kPatternName[pat], static_cast<unsigned long long>(seed));
+  check_pattern(label, n, K, bm, s, pattern(pat, n, K, seed), false);
+}
+
+// A file of explicit patterns, one per line: k n limit s q0 q1 ... (the k present shards).
+int run_file(const char* path) {
+  std::FILE* f = std::fopen(path, "r");
+  if (!f) {
+    std::fprintf(stderr, "planner_batch_check: cannot open %s\n", path);
+    return 2;
+  }
+  std::vector<char> buf(1 << 20);
+  for (int line = 1; std::fgets(buf.data(), int(buf.size()), f); ++line) {
+    char label[160];
+    std::snprintf(label, sizeof label, "line=%d", line);
+    CHECK(std::strchr(buf.data(), '\n') != nullptr);  // a whole line was read
+    std::vector<unsigned long> v;
+    char* at = buf.data();
+    for (;;) {
+      char* end = nullptr;
+      const unsigned long x = std::strtoul(at, &end, 10);
+      if (end == at) break;
+      v.push_back(x);
+      at = end;
+    }
+    while (*at == ' ' || *at == '\n' || *at == '\r') ++at;
+    CHECK(*at == 0);  // numbers only
+    if (v.empty()) continue;
+    CHECK(v.size() >= 4);
+    const uint32_t k = uint32_t(v[0]), n = uint32_t(v[1]), bm = uint32_t(v[2]);
+    const int s = int(v[3]);
+    CHECK(k >= 1 && k < n && n <= 65535 && v.size() == size_t(4) + k);
+    CHECK(bm >= 1 && bm <= uint32_t(kMaxC) && (bm & (bm - 1)) == 0 && s >= 2 && s % 2 == 0);
+    std::vector<uint32_t> have;
+    std::vector<uint8_t> seen(n, 0);
+    for (size_t i = 4; i < v.size(); ++i) {
+      CHECK(v[i] < n && !seen[v[i]]);
+      seen[v[i]] = 1;
+      have.push_back(uint32_t(v[i]));
+    }
+    std::snprintf(label, sizeof label, "line=%d k=%u n=%u bm=%u s=%d", line, k, n, bm, s);
+    check_pattern(label, n, k, bm, s, have, true);
+  }
+  std::fclose(f);
+  return 0;
 }
 
 }  // namespace
 
-int main() {
+int main(int argc, char** argv) {
+  if (argc > 1) {
+    const int rc = run_file(argv[1]);
+    std::fprintf(stderr, "planner_batch_check: %d cases\n", g_cases);
+    return rc;
+  }
   const uint32_t ns[] = {10, 13, 100, 1000, 3100, 4500};
   for (uint32_t n : ns)
     for (int axis = 0; axis < 2; ++axis)

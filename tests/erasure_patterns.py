@@ -37,6 +37,11 @@ Whether a given pattern takes the pair branches of load_ifft (rs2_codec.hip) is 
 observable here; the coverage claim is the counting precondition over every output block and
 many input arrangements, and a byte-exact result for each of them.
 
+  batch_path(lay, s), predicted_stats(lays, s), batch_jobs(fams)
+      for the batched decode and recovery calls (BATCH_GEOMETRIES): the path each pattern takes
+      (batched launch or per-job decode), the counters a call must add, and one call's job list
+      with every family in it.
+
   block_limit(b)   context manager: rs2_set_block_limit(b), restored to 512 on exit.  The 1D
                    decode plans with the limit current at the call; make a fresh DeviceOps /
                    DevicePlan inside the context, never one created under another limit.
@@ -57,6 +62,25 @@ GEOMETRIES = [(34, 100, 16, 67), (67, 100, 16, 90), (100, 300, 64, 56), (200, 30
 # (None = the default), 396 k-subsets in all
 SMALL = [(2, 4, (None, 1)), (3, 4, (None,)), (3, 7, (None, 2, 1)), (5, 7, (None, 1)),
          (4, 10, (None, 2, 1)), (7, 10, (None, 2, 1))]
+# (k, n, block limit, patterns, batch-eligible patterns at s >= 4) of the batched decode and
+# recovery tests: one call carries every family of an entry, so one launch mixes n_in 1..8 with
+# n_out 1..5, paired and unpaired jobs, fused and unfused ones, and -- where eligible < patterns
+# -- jobs of 9 and more blocks that leave the launch for the per-job path.  (67, 100, 8) is left
+# out: all its patterns have 9 or more input blocks.  tests/test_erasure_patterns.py re-derives
+# the last two figures from decode_layout / batch_path.
+BATCH_GEOMETRIES = [(34, 100, 16, 67, 67), (67, 100, 16, 90, 90), (34, 100, 8, 91, 90),
+                    (100, 300, 64, 56, 56), (200, 300, 64, 81, 81), (200, 300, 32, 117, 102),
+                    (334, 1000, 512, 45, 45), (667, 1000, 512, 55, 55), (334, 1000, 128, 69, 69),
+                    (667, 1000, 128, 105, 103)]
+# The same for the codes of a 300-shard BLOB: n = 300 gives K_p = 102 and K_s = 201, so the
+# (100, 300) and (200, 300) codes above -- 1D codes of the decode_lines tests -- are no axis of a
+# blob plan or a sliver verifier.  The planner proofs run both; the batched GPU calls, which go
+# through blob plans and verifiers, run BATCH_CALLS: these at n = 300 and the entries above at
+# n = 100 (K_p 34, K_s 67) and n = 1000 (K_p 334, K_s 667).
+BLOB_300 = [(102, 300, 64, 57, 57), (201, 300, 64, 81, 81), (201, 300, 32, 117, 101)]
+BATCH_CALLS = [g for g in BATCH_GEOMETRIES if g[1] != 300] + BLOB_300
+BATCH_BLOCKS = 8      # kBatchBlocks: input / output blocks a job of a batched launch may have
+CHUNK_JOBS = 341      # jobs of one planning window (an upload slot of 512 KiB / 1536-byte jobs)
 DEFAULT_LIMIT = 512   # kMaxC, the engine's block limit unless lowered
 PPW = 32              # kPpwTarget: positions per wave
 
@@ -112,6 +136,60 @@ def pair_precondition(lay):
         return False
     return any(lay.waves[p] + lay.waves[q] <= lay.nw
                for p, q in combinations([b for b, _ in lay.in_blocks], 2))
+
+
+def batch_path(lay, s, may_fuse=True):
+    """The path a pattern takes through a batched decode / recovery call, from its layout alone:
+    "copy" when nothing is erased, "single" (the per-job decode) with 2-byte symbols, with more
+    than BATCH_BLOCKS input or output blocks, or -- where the fused copy of the present originals
+    is switched off (may_fuse=False, RS2_DEC_NOFUSE=1) -- with any original present; "batched"
+    otherwise.  (With may_fuse the fused copy is covered for every family pattern of
+    BATCH_GEOMETRIES, which tests/test_planner_batch.py proves on the planner itself.)"""
+    if not lay.erased:
+        return "copy"
+    if s < 4 or len(lay.in_blocks) > BATCH_BLOCKS or len(lay.out_blocks) > BATCH_BLOCKS:
+        return "single"
+    if not may_fuse and len(lay.erased) < lay.k:
+        return "single"
+    return "batched"
+
+
+def predicted_stats(lays, s, may_fuse=True, refused=()):
+    """(launches, batched, single) a call of these layouts adds to the engine's counters: one
+    launch per planning window of CHUNK_JOBS jobs that holds a batched job (the tests' tables
+    stay far below the engine's per-launch table budget).  The jobs at the positions `refused`
+    are invalid ones, which count nowhere.  No layout may be a plain copy."""
+    paths = ["refused" if j in refused else batch_path(lay, s, may_fuse)
+             for j, lay in enumerate(lays)]
+    assert "copy" not in paths
+    windows = sum("batched" in paths[w:w + CHUNK_JOBS] for w in range(0, len(paths), CHUNK_JOBS))
+    return windows, paths.count("batched"), paths.count("single")
+
+
+def batch_jobs(fams, seed=0):
+    """One call's jobs from a family list: [(name, shards in the order they are handed over,
+    source)].  Job j takes pattern j; its shard order is sorted on even j and seeded-shuffled on
+    odd j (the recovery spec places symbols by their position in the received list, the blob plan
+    by the order of the selection); its source is blob / sliver j % 4 of four distinct ones, so a
+    job that wrote a neighbour's data is seen."""
+    rng = np.random.default_rng(seed)
+    jobs = []
+    for j, (name, present) in enumerate(fams):
+        sel = sorted(int(q) for q in present)
+        if j % 2:
+            sel = [sel[i] for i in rng.permutation(len(sel))]
+        jobs.append((name, sel, j % 4))
+    return jobs
+
+
+def window_repeats(lays):
+    """How often a family list is repeated for the two-window calls: the fewest times that give
+    CHUNK_JOBS jobs of one output block, so that -- with those jobs sorted to the front -- the
+    first window launches one block deep and the second as deep as the families go."""
+    ones = sum(len(lay.out_blocks) == 1 for lay in lays)
+    reps = -(-CHUNK_JOBS // ones)
+    assert CHUNK_JOBS < reps * len(lays) <= 2 * CHUNK_JOBS
+    return reps
 
 
 def original_blocks(k, n, block_limit):

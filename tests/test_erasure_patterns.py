@@ -2,8 +2,10 @@
 the pattern families reach in each geometry the device tests run (no GPU, no engine)."""
 import pytest
 
-from erasure_patterns import (GEOMETRIES, SMALL, all_subsets, cut_for, decode_layout, families,
-                              max_trunc, original_blocks, pair_precondition)
+from erasure_patterns import (BATCH_BLOCKS, BATCH_CALLS, BATCH_GEOMETRIES, BLOB_300, CHUNK_JOBS,
+                              GEOMETRIES, SMALL,
+                              all_subsets, batch_jobs, batch_path, cut_for, decode_layout, families,
+                              max_trunc, original_blocks, pair_precondition, predicted_stats, window_repeats)
 
 
 def test_layout_restates_the_planner():
@@ -55,6 +57,113 @@ def test_families_reach_the_planner_corners(k, n, limit, count):
         assert not any(pair_precondition(lay) for lay in lays)
     # every pattern loses an original (else nothing is decoded) and is decodable (k shards)
     assert all(lay.erased and len(lay.erased) <= n - k for lay in lays)
+
+
+# What the one call of each BATCH_GEOMETRIES entry holds: the n_in and the n_out values of its
+# jobs (input / output blocks, ineligible jobs included).
+BATCH_REACH = {
+    (34, 100, 16): ({3, 4, 5, 6}, {1, 2, 3}),
+    (67, 100, 16): ({5, 6, 7, 8}, {1, 2, 3, 5}),
+    (34, 100, 8): ({5, 6, 7, 8, 10}, {1, 2, 3, 4, 5}),
+    (100, 300, 64): ({2, 3, 4}, {1, 2}),
+    (200, 300, 64): ({4, 5, 6}, {1, 2, 3, 4}),
+    (200, 300, 32): ({7, 8, 9, 11}, {1, 2, 3, 4, 7}),
+    (334, 1000, 512): ({1, 2, 3}, {1}),
+    (667, 1000, 512): ({2, 3}, {1, 2}),
+    (334, 1000, 128): ({3, 4, 5, 6}, {1, 2, 3}),
+    (667, 1000, 128): ({6, 7, 9}, {1, 2, 3, 4, 6}),
+    # the codes of a 300-shard blob reach what (100, 300) and (200, 300) reach
+    (102, 300, 64): ({2, 3, 4}, {1, 2}),
+    (201, 300, 64): ({4, 5, 6}, {1, 2, 3, 4}),
+    (201, 300, 32): ({7, 8, 9, 11}, {1, 2, 3, 4, 7}),
+}
+# the entries whose call must mix at least three launch depths (grid.z against a job's n_out)
+THREE_N_OUT = {(34, 100, 16), (67, 100, 16), (34, 100, 8), (200, 300, 64), (200, 300, 32),
+               (334, 1000, 128), (667, 1000, 128), (201, 300, 64), (201, 300, 32)}
+# the entries with per-job decodes between batched jobs
+WITH_FALLBACKS = {(200, 300, 32), (667, 1000, 128), (201, 300, 32)}
+
+
+def test_batch_calls_are_codes_of_a_blob():
+    """Every BATCH_CALLS entry is K_p or K_s of its n (so a blob plan and a sliver verifier can
+    run it), both axes of n = 100, 300 and 1000 occur, and only the n = 300 entries of
+    BATCH_GEOMETRIES had to be replaced."""
+    import rs2_oracle as O
+    assert {(n, O.source_symbols_for_n_shards(n).index(k)) for k, n, _, _, _ in BATCH_CALLS} == \
+        {(n, axis) for n in (100, 300, 1000) for axis in (0, 1)}
+    assert O.source_symbols_for_n_shards(300) == (102, 201)
+    assert [g for g in BATCH_GEOMETRIES if g not in BATCH_CALLS] == \
+        [g for g in BATCH_GEOMETRIES if g[1] == 300]
+    assert [(round(k, -2), n, limit) for k, n, limit, _, _ in BLOB_300] == \
+        [(k, n, limit) for k, n, limit, _, _ in BATCH_GEOMETRIES if n == 300]   # limit for limit
+
+
+@pytest.mark.parametrize("k,n,limit,count,eligible", BATCH_GEOMETRIES + BLOB_300)
+def test_batch_calls_are_heterogeneous(k, n, limit, count, eligible):
+    """What keeps the batched GPU tests (test_gpu_patterns_3_batch / _4_recover) from passing
+    vacuously, from the reference arithmetic alone: one call of a geometry holds jobs of several
+    n_in and n_out, paired and unpaired ones, ones with and without a present original, and --
+    where some patterns have more than 8 blocks -- per-job decodes between batched jobs."""
+    fams = families(k, n, limit)
+    assert len(fams) == count
+    assert [name for name, _, _ in batch_jobs(fams)] == [name for name, _ in fams]
+    lays = [decode_layout(k, n, limit, present) for _, present in fams]
+    for s in (6, 66, 130):
+        paths = [batch_path(lay, s) for lay in lays]
+        assert set(paths) <= {"batched", "single"}      # no family pattern is a plain copy
+        assert paths.count("batched") == eligible
+        assert predicted_stats(lays, s) == (1, eligible, count - eligible)
+    assert {batch_path(lay, 2) for lay in lays} == {"single"}
+    shape = [(len(lay.in_blocks), len(lay.out_blocks)) for lay in lays]
+    n_in, n_out = BATCH_REACH[k, n, limit]
+    assert {a for a, _ in shape} == n_in and {b for _, b in shape} == n_out
+    assert ((k, n, limit) in THREE_N_OUT) == (len(n_out) >= 3)
+    # the eligibility rule restated: at most 8 blocks either way
+    assert [p == "batched" for p in paths] == [max(a, b) <= BATCH_BLOCKS for a, b in shape]
+    if (k, n, limit) == (67, 100, 16):
+        assert (8, 5) in shape                                        # the 8-block edge
+    switches = sum(paths[j] != paths[j + 1] for j in range(count - 1))
+    if (k, n, limit) in WITH_FALLBACKS:
+        assert eligible < count and switches >= 1   # a per-job decode between batched jobs
+    else:
+        assert count - eligible <= 1
+    paired = [pair_precondition(lay) for lay in lays]
+    if lays[0].C >= 64:
+        assert any(paired) and not all(paired)
+    else:
+        assert not any(paired)
+    # with and without a present original.  A pattern keeps k of n shards, so at least
+    # k - (n - k) originals are present: only a low-rate code (k <= n - k) can lose them all.
+    originals = [k - len(lay.erased) for lay in lays]
+    assert any(originals)
+    if k <= n - k:
+        assert 0 in originals
+    else:
+        assert min(originals) >= 2 * k - n > 0
+    # RS2_DEC_NOFUSE=1: every job with a present original leaves the batch
+    nofuse = predicted_stats(lays, 6, may_fuse=False)
+    assert nofuse[1] == sum(o == 0 and p == "batched" for o, p in zip(originals, paths))
+    assert nofuse[1] + nofuse[2] == count and nofuse[0] == (nofuse[1] > 0)
+
+
+@pytest.mark.parametrize("k,n,limit,reps", [(34, 100, 16, 9), (67, 100, 16, 6)])
+def test_batch_jobs_order_sources_and_windows(k, n, limit, reps):
+    fams = families(k, n, limit)
+    assert window_repeats([decode_layout(k, n, limit, p) for _, p in fams]) == reps
+    jobs = batch_jobs(fams * reps)
+    assert CHUNK_JOBS < len(jobs) == reps * len(fams) <= 2 * CHUNK_JOBS
+    for j, ((name, sel, src), (fname, present)) in enumerate(zip(jobs, fams * reps)):
+        assert name == fname and sorted(sel) == sorted(present) and src == j % 4
+        assert (sel == sorted(sel)) == (j % 2 == 0)
+    assert batch_jobs(fams) == jobs[:len(fams)] and batch_jobs(fams, seed=1) != jobs[:len(fams)]
+    # a pattern meets more than one source over the repeats
+    assert len({src for name, _, src in jobs if name == fams[1][0]}) > 1
+    # two planning windows; with the one-block jobs first, each has its own largest n_out
+    lays = [decode_layout(k, n, limit, sel) for _, sel, _ in jobs]
+    assert predicted_stats(lays, 6) == (2, len(jobs), 0)
+    depth = sorted((len(lay.out_blocks) for lay in lays), key=lambda d: d != 1)
+    assert max(depth[:CHUNK_JOBS]) == 1 < max(depth[CHUNK_JOBS:])
+    assert max(len(lay.out_blocks) for lay in lays[:CHUNK_JOBS]) > 1   # family order: both deep
 
 
 @pytest.mark.parametrize("k,n,limit,count", GEOMETRIES)

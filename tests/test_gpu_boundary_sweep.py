@@ -37,8 +37,9 @@ def _kp_ks(n):
 # (n, K_p, K_s) at the edges: K_p 255 / 256 / 257, K_s 511 / 512 / 513, K_p 511 / 512 / 513,
 # K_s 1023 / 1024 / 1025
 EDGE_N = [763, 764, 766, 767, 769, 1531, 1532, 1534, 1535, 1537]
-# K_p 1024 / 1025, K_s 2047 / 2048 / 2049, K_p 2048 / 2049, K_s 4095 / 4097 (small symbols)
-LARGE_EDGE_N = [3070, 3071, 3073, 6142, 6145]
+# K_p 1023 / 1024 / 1025, K_s 2047 / 2048 / 2049, K_p 2047 / 2048 / 2049, K_s 4095 / 4096 / 4097
+# (small symbols)
+LARGE_EDGE_N = [3067, 3070, 3071, 3073, 6139, 6142, 6143, 6145]
 SMALL_N = [4, 5, 6, 7, 8, 9]
 RANDOM_N = sorted(int(x) for x in np.random.default_rng(2026).integers(10, 1300, 6))
 
@@ -69,8 +70,11 @@ def _c_encode(cpu, n, blob, threads=1):
 
 def test_edge_n_are_edges():
     ks = [_kp_ks(n) for n in EDGE_N + LARGE_EDGE_N]
-    assert {kp for kp, _ in ks} >= {255, 256, 257, 511, 512, 513, 1024, 1025, 2048, 2049}
-    assert {k for _, k in ks} >= {511, 512, 513, 1023, 1024, 1025, 2047, 2048, 2049, 4095, 4097}
+    assert {kp for kp, _ in ks} >= {255, 256, 257, 511, 512, 513, 1023, 1024, 1025, 2047, 2048,
+                                    2049}
+    assert {k for _, k in ks} >= {511, 512, 513, 1023, 1024, 1025, 2047, 2048, 2049, 4095, 4096,
+                                  4097}
+    assert _kp_ks(3067)[0] == 1023 and _kp_ks(6139)[0] == 2047 and _kp_ks(6143) == (2049, 4096)
 
 
 @pytest.mark.parametrize("n", [1, 2, 3])

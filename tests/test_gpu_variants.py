@@ -9,6 +9,10 @@ stage-fusion knobs RS2_FUSE_BLOB=0 / RS2_TAIL_AUX=1 / RS2_SPLIT_LEAF=0 / RS2_DEC
 RS2_SMALL_LEAF=0 their unfused forms.  The knobs are read once per process, so the variant runs
 in a child process and reports digests of its slivers, metadata and decodes; the parent compares
 them with its own (default) run and with the CPU oracle's encode at the small shape.
+
+The two knobs that reach the batched calls (rs2_decode_batch_device_async,
+rs2_verifier_recover_slivers_device_async) run through them as well: RS2_PAIR=0 and
+RS2_DEC_NOFUSE=1, one child each, over the family calls of two geometries (batched_digests).
 """
 import hashlib
 import json
@@ -52,6 +56,77 @@ def digests(shapes):
             "slivers": h.hexdigest(), "blob_id": bytes(meta.blob_id).hex(),
             "decodes_ok": dec == blob and worst == blob and sec == blob}
     return out
+
+
+# (k, n, block limit) of the batched family calls run under the knobs that reach them: at
+# (334, 1000, 512) half the jobs pair and a third have no present original, at (201, 300, 64)
+# (K_s of n = 300) every job has one
+BATCHED = [(334, 1000, 512), (201, 300, 64)]
+BATCHED_S = 6
+
+
+def batched_digests():
+    """The family calls of test_gpu_patterns_3_batch (blob decode) and _4_recover (sliver
+    recovery): digests of everything they wrote, whether it is exact, and the counters' deltas."""
+    import torch
+    import walrus_amd as W
+    import test_gpu_patterns_3_batch as B
+    import test_gpu_patterns_4_recover as R
+    from erasure_patterns import families, load_cpu
+    cpu = load_cpu()
+    out = {}
+    for k, n, limit in BATCHED:
+        fams = families(k, n, limit)
+        bs = B.blob_set(cpu, n, BATCHED_S)
+        buf, jobs, _, delta, _, _ = B.family_call(W, bs, k, limit, fams)
+        fc = R.FamilyCall(k, n, limit, BATCHED_S, fams)
+        call, rdelta, _, rc = fc.run()
+        slivers, roots, verdict = call.results()
+        exact = rc == 0 and all(
+            np.array_equal(slivers[j], sl.data.reshape(-1)) and roots[j].tobytes() == sl.root and
+            verdict[j] == R.MATCH for j, sl in enumerate(fc.slivers))
+        out[f"{k}/{n}/{limit}"] = {
+            "blobs": hashlib.sha256(buf.cpu().numpy().tobytes()).hexdigest(),
+            "blobs_exact": torch.equal(buf, B.expected(bs, jobs)), "blobs_stats": delta,
+            "slivers": hashlib.sha256(slivers.tobytes() + roots.tobytes() +
+                                      verdict.tobytes()).hexdigest(),
+            "slivers_exact": bool(exact), "slivers_stats": rdelta}
+    return out
+
+
+def test_batched_calls_under_pair_and_nofuse(gpu):
+    """RS2_PAIR=0 changes the pair arrays of batch jobs, RS2_DEC_NOFUSE=1 sends every batch job
+    with a present original to the per-job decode: the same bytes, roots and verdicts either
+    way, and the counters say which way each job went."""
+    from erasure_patterns import decode_layout, families, predicted_stats
+    base = batched_digests()
+    lays = {f"{k}/{n}/{limit}": [decode_layout(k, n, limit, p) for _, p in families(k, n, limit)]
+            for k, n, limit in BATCHED}
+
+    def check_stats(got, may_fuse, env):
+        for key, v in got.items():
+            launches, batched, single = predicted_stats(lays[key], BATCHED_S, may_fuse)
+            assert v["blobs_stats"][1:] == [batched, single], (env, key, v)
+            assert v["blobs_stats"][0] >= launches and (batched or not v["blobs_stats"][0])
+            assert v["slivers_stats"] == [launches, batched, single], (env, key, v)
+
+    assert all(v["blobs_exact"] and v["slivers_exact"] for v in base.values()), base
+    check_stats(base, True, {})
+    code = ("import json, sys; sys.path[:0] = %r; "
+            "import test_gpu_variants as T; print(json.dumps(T.batched_digests()))"
+            % ([ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "oracle")],))
+    for env, may_fuse in (({"RS2_PAIR": "0"}, True), ({"RS2_DEC_NOFUSE": "1"}, False)):
+        r = subprocess.run([sys.executable, "-c", code], env={**os.environ, **env},
+                           capture_output=True, text=True, timeout=240, cwd=ROOT)
+        assert r.returncode == 0, (env, r.stderr[-2000:])
+        got = json.loads(r.stdout.strip().splitlines()[-1])
+        for key, v in base.items():
+            for field in ("blobs", "blobs_exact", "slivers", "slivers_exact"):
+                assert got[key][field] == v[field], (env, key, field)
+        check_stats(got, may_fuse, env)
+    # the knob moved jobs: without the fused copy only the jobs with no present original batch
+    assert predicted_stats(lays["201/300/64"], BATCHED_S, False) == (0, 0, 81)
+    assert predicted_stats(lays["334/1000/512"], BATCHED_S, False) == (1, 15, 30)
 
 
 def test_variants_match_default(gpu):

@@ -9,7 +9,13 @@ one-erasure patterns, that batch_eligible equals the rule (a decode with at most
 way, s >= 4, nothing to copy or a covered fused copy-out), that every field of the packed job
 equals the planned job's below n_in / n_out, and that each re-strided mixing table equals its
 source.  This file adds what must hold per case: never at n = 4500 or n = 1000 / limit 128 for
-random subsets, never with 2-byte symbols, never when nothing is erased, always otherwise."""
+random subsets, never with 2-byte symbols, never when nothing is erased, always otherwise.
+
+Given a file of explicit patterns the program runs those through the same checks instead.  The
+last test feeds it every family pattern of the geometries of the batched GPU tests
+(tests/erasure_patterns.py BATCH_GEOMETRIES and BLOB_300) and compares what the planner made of
+each with the Python restatement that those tests predict their paths from."""
+import hashlib
 import re
 import subprocess
 from pathlib import Path
@@ -21,6 +27,10 @@ SRC = [str(ROOT / "tests" / "capi" / "planner_batch_check.cpp"),
        str(ROOT / "walrus_amd" / "csrc" / "rs2_planner.cpp")]
 LINE = re.compile(r"n=(\d+) axis=(\d) bm=(\d+) s=(\d+) pat=(\w+) seed=(\d+) n_in=(\d+) n_out=(\d+) "
                   r"originals=(\d+) fused=(\d) eligible=(\d)$")
+FILE_LINE = re.compile(r"line=(\d+) k=(\d+) n=(\d+) bm=(\d+) s=(\d+) n_in=(\d+) n_out=(\d+) "
+                       r"originals=(\d+) fused=(\d) eligible=(\d) paired=(\d+)$")
+# SHA-256 of the program's output without an argument (338 lines), as it was before the file form
+BUILT_IN_OUTPUT = "8c20ccd49768a82583bd74b80be80b8fd76998a24b14d416d54f3631d5fbb9ef"
 
 
 @pytest.fixture(scope="module")
@@ -40,8 +50,8 @@ def programs(tmp_path_factory):
     return plain, san
 
 
-def _run(prog):
-    run = subprocess.run([str(prog)], capture_output=True, text=True)
+def _run(prog, *args):
+    run = subprocess.run([str(prog), *map(str, args)], capture_output=True, text=True)
     assert run.returncode == 0, run.stderr[-4000:]  # non-zero: a property was breached
     return run.stdout.splitlines()
 
@@ -71,3 +81,51 @@ def test_batch_rule_and_packed_jobs(programs):
 
 def test_same_under_host_sanitizers(programs):
     assert _run(programs[1]) == _run(programs[0])
+
+
+def test_built_in_cases_unchanged(programs):
+    run = subprocess.run([str(programs[0])], capture_output=True)
+    assert run.returncode == 0 and run.stderr == b"planner_batch_check: 338 cases\n"
+    assert hashlib.sha256(run.stdout).hexdigest() == BUILT_IN_OUTPUT
+
+
+def test_families_of_the_batch_geometries(programs, tmp_path):
+    """Every family pattern of every BATCH_GEOMETRIES entry (s = 6) through the program's file
+    form, plain and under the host sanitizers: the planner's n_in, n_out and eligibility equal
+    decode_layout / batch_path, "the planner paired" equals pair_precondition, and the fused copy
+    of the present originals is covered wherever an original is present (so the engine's
+    `originals > 0 && !fused` fallback does not occur in the batched GPU tests)."""
+    from erasure_patterns import (BATCH_GEOMETRIES, BLOB_300, batch_path, decode_layout, families,
+                                  pair_precondition)
+    s = 6
+    cases = []
+    geometries = BATCH_GEOMETRIES + BLOB_300   # (BLOB_300: what the GPU calls run at n = 300)
+    for k, n, limit, count, eligible in geometries:
+        fams = families(k, n, limit)
+        assert len(fams) == count
+        cases += [(k, n, limit, name, present) for name, present in fams]
+    path = tmp_path / "families.txt"
+    path.write_text("".join(f"{k} {n} {limit} {s} {' '.join(map(str, present))}\n"
+                            for k, n, limit, _, present in cases))
+    lines = _run(programs[0], path)
+    assert len(lines) == len(cases) == 776 + 255
+    eligible_seen, paired_seen = {}, 0
+    for at, (ln, (k, n, limit, name, present)) in enumerate(zip(lines, cases), 1):
+        m = FILE_LINE.match(ln)
+        assert m, ln
+        got = dict(zip(("line", "k", "n", "bm", "s", "n_in", "n_out", "originals", "fused",
+                        "eligible", "paired"), map(int, m.groups())))
+        what = f"{k}-of-{n} block limit {limit} pattern {name}: {ln}"
+        assert (got["line"], got["k"], got["n"], got["bm"], got["s"]) == (at, k, n, limit, s), what
+        lay = decode_layout(k, n, limit, present)
+        assert (got["n_in"], got["n_out"]) == (len(lay.in_blocks), len(lay.out_blocks)), \
+            f"{what}\n{lay}"
+        assert got["eligible"] == (batch_path(lay, s) == "batched"), f"{what}\n{lay}"
+        assert got["originals"] == k - len(lay.erased), what
+        assert got["paired"] == int(pair_precondition(lay)), f"{what}\n{lay}"
+        assert got["fused"] == int(got["originals"] > 0), what
+        eligible_seen[k, n, limit] = eligible_seen.get((k, n, limit), 0) + got["eligible"]
+        paired_seen += got["paired"]
+    assert eligible_seen == {(k, n, limit): e for k, n, limit, _, e in geometries}
+    assert paired_seen == 180 + 26
+    assert _run(programs[1], path) == lines
