@@ -320,6 +320,56 @@ int rs2_decode_batch(rs2_plan* plan, int axis, uint32_t n_blobs, const uint64_t*
  * took the per-blob path.  No reference counterpart. */
 int rs2_decode_batch_stats(uint64_t* stats_out);
 
+/* ---- verified decode batches ------------------------------------------------------------------
+ * The read path's call, EncodingFactory::decode_and_verify (config.rs:613-658), for many blobs of
+ * the plan's symbol size at once: each blob decoded from its own slivers as in a decode batch and
+ * checked against its own metadata, with a verdict per blob.  The blob, sliver, length and stride
+ * arguments, the per-blob rules, the alignment rules, the status_out contract and the 65535-blob
+ * limit are those of rs2_decode_batch_device_async / rs2_decode_batch; n_blobs 0: RS2_OK.
+ *
+ * Device form: the metadata is device-resident in the layout rs2_encode_batch_device_async
+ * writes -- blob b's pair hashes at d_hashes + b*64*n, its id at d_blob_ids + b*32, both 16-byte
+ * aligned.  RS2_CHECK_DEFAULT reads only the primary hash of pairs < K_p (d_blob_ids may be
+ * NULL), RS2_CHECK_STRICT only the blob ids (d_hashes may be NULL), RS2_CHECK_SKIP neither.  A
+ * NULL pointer the check needs, a misaligned one or a bad check value: RS2_E_INVALID_ARGUMENT
+ * before anything is enqueued.  d_verdict (n_blobs int32, 16-byte aligned) receives one of the
+ * constants below in every slot.  The checks are those of rs2_decode_and_verify_device: on the
+ * primary axis every systematic index among the input slivers the decoder pulled counts as
+ * verified, a blob with nothing left to check is a match; rows at or past blob_lens[b] are the
+ * message's zero padding and hashed as zeros, no byte at or past blob_lens[b] of an output slot
+ * is read or written.  A mismatching blob's decoded bytes stay in its slot.  With status_out
+ * NULL and a failing blob the first code is returned and neither outputs nor verdicts are
+ * touched.  All work is enqueued on the one stream (decodes, checks and verdicts of a window of
+ * blobs, window after window); the call never synchronizes and reads no result back, and its
+ * device scratch is bounded by the window budget below, not by n_blobs. */
+#define RS2_BLOB_MISMATCH 0  /* decoded, the check failed                         */
+#define RS2_BLOB_MATCH    1  /* decoded and the check passed (always, under SKIP) */
+#define RS2_BLOB_SKIPPED  2  /* refused on the host (status_out[b] != RS2_OK)     */
+int rs2_decode_and_verify_batch_device_async(
+    rs2_plan* plan, int axis, uint32_t n_blobs, const uint64_t* blob_lens, const uint32_t* counts,
+    const uint16_t* sliver_idx, const void* d_slivers_base, const uint64_t* sliver_off,
+    const void* d_hashes, const void* d_blob_ids, int consistency_check, void* d_blobs_out,
+    uint64_t out_stride, void* d_verdict, int* status_out, void* stream);
+/* Host form (blocking): slivers as rs2_decode_batch (per-sliver rules as rs2_decode_and_verify),
+ * hashes n_blobs*n*64 and blob_ids n_blobs*32 host bytes in the same layout (NULL as above).
+ * blobs_out[b] receives blob b whatever its verdict; verdict_out (n_blobs values, required) is
+ * written whenever the call returns RS2_OK. */
+int rs2_decode_and_verify_batch(rs2_plan* plan, int axis, uint32_t n_blobs,
+                                const uint64_t* blob_lens, const uint32_t* counts,
+                                const uint16_t* sliver_idx, const uint8_t* const* slivers,
+                                const uint64_t* sliver_len, const uint16_t* sliver_symbol_size,
+                                const uint8_t* hashes, const uint8_t* blob_ids,
+                                int consistency_check, uint8_t* const* blobs_out,
+                                int32_t* verdict_out, int* status_out);
+/* A window holds at most a decode chunk's blobs (a few hundred) and at most `bytes` of check
+ * scratch (Default: gathered rows, their leaves and repair symbols; Strict: the re-encoded
+ * slivers, repair quadrant and leaves), but always one blob.  Default 256 MiB; 0 restores it.
+ * Process-wide, applies to calls made afterwards.  No reference counterpart. */
+int rs2_set_verify_batch_budget(uint64_t bytes);
+/* Process-wide counters, stats_out[4]: check windows, blobs checked (Default or Strict), rows
+ * hashed by Default, blobs re-encoded by Strict.  No reference counterpart. */
+int rs2_verify_batch_stats(uint64_t* stats_out);
+
 /* EncodingFactory::decode_and_verify (config.rs:613-658) on device-resident slivers (as
  * rs2_decode_device_async) into the device buffer d_blob_out (blob_len bytes); `hashes` /
  * `blob_id` are host copies of the metadata.  The checks are those of rs2_decode_and_verify and

@@ -33,8 +33,10 @@ from .encoding import (  # noqa: F401
     VerificationError,
     VerifiedBlobMetadataWithId,
     compute_symbol_size,
+    set_verify_batch_budget,
     sliver_merkle_roots,
     source_symbols_for_n_shards,
+    verify_batch_stats,
     verify_slivers,
 )
 

@@ -33,6 +33,7 @@ AXIS_PRIMARY = 0
 AXIS_SECONDARY = 1
 CHECK_SKIP, CHECK_DEFAULT, CHECK_STRICT = 0, 1, 2
 RS2_SLIVER_MISMATCH, RS2_SLIVER_MATCH, RS2_SLIVER_SKIPPED = 0, 1, 2
+RS2_BLOB_MISMATCH, RS2_BLOB_MATCH, RS2_BLOB_SKIPPED = 0, 1, 2
 
 # (name, restype, argtypes) for every function declared in include/walrus_rs2.h
 _u8p = ctypes.POINTER(ctypes.c_uint8)
@@ -102,6 +103,18 @@ SIGNATURES = {
         [_vp, ctypes.c_int, ctypes.c_uint32, _u64p, ctypes.POINTER(ctypes.c_uint32), _u16p,
          ctypes.POINTER(_vp), _u64p, _u16p, ctypes.POINTER(_vp), ctypes.POINTER(ctypes.c_int)]),
     "rs2_decode_batch_stats": (ctypes.c_int, [ctypes.POINTER(ctypes.c_uint64)]),
+    "rs2_decode_and_verify_batch_device_async": (
+        ctypes.c_int,
+        [_vp, ctypes.c_int, ctypes.c_uint32, _u64p, ctypes.POINTER(ctypes.c_uint32), _u16p, _vp,
+         _u64p, _vp, _vp, ctypes.c_int, _vp, ctypes.c_uint64, _vp, ctypes.POINTER(ctypes.c_int),
+         _vp]),
+    "rs2_decode_and_verify_batch": (
+        ctypes.c_int,
+        [_vp, ctypes.c_int, ctypes.c_uint32, _u64p, ctypes.POINTER(ctypes.c_uint32), _u16p,
+         ctypes.POINTER(_vp), _u64p, _u16p, _vp, _vp, ctypes.c_int, ctypes.POINTER(_vp),
+         ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int)]),
+    "rs2_set_verify_batch_budget": (ctypes.c_int, [ctypes.c_uint64]),
+    "rs2_verify_batch_stats": (ctypes.c_int, [ctypes.POINTER(ctypes.c_uint64)]),
     "rs2_decode_and_verify_device": (
         ctypes.c_int,
         [_vp, ctypes.c_int, ctypes.c_uint32, _u16p, _vp, _u64p, _vp, _vp, ctypes.c_int, _vp, _vp]),

@@ -6,6 +6,7 @@
 // batch_blob_copy_kernel the blobs of a batch into their systematic primary slivers.
 // build_mul_tables       per-position GF multiplier nibble tables for the decoder.
 // row_gather_kernel      the Default check's unverified rows, gathered back to back.
+// check_rows_gather_kernel  the same for a verified decode batch: a source and valid length per row.
 // host_upload_kernel     small host -> device uploads from pinned slots, upload_signal_kernel.
 // tail_rows_kernel       the encode's zero-padded tail rows.
 #include <hip/hip_runtime.h>
@@ -238,6 +239,56 @@ __global__ void __launch_bounds__(256) row_gather_kernel(const uint8_t* __restri
       *reinterpret_cast<uint8_t*>(x) = *reinterpret_cast<const uint8_t*>(s0 + (x - d0));
 }
 
+// Row gather of a verified decode batch (rs2_decode_and_verify_batch_*): row_gather_kernel with a
+// source address and a valid length per row.  Row a of the launch (row0 + a of the table) is
+// row_bytes bytes at dst + (row0 + a) * row_bytes: bytes [0, valid) from the row's source, zeros
+// from there on.  Nothing at or past src + valid is read -- it may be another blob's slot or the
+// end of the caller's buffer.  Sources and destinations are 2-byte aligned and row_bytes is even,
+// so a lane moves 16 bytes of one row as one, four or eight aligned words, by the alignment the
+// two ends share; the piece that holds the valid end goes element by element, its odd last byte
+// alone.  The row index is folded into grid.x (`chunks` workgroups of 4 KiB per row): a window
+// holds more rows than grid.y may count.
+__global__ void __launch_bounds__(256)
+    check_rows_gather_kernel(const CheckRow* __restrict__ rows, int64_t row0, uint32_t chunks,
+                             int64_t row_bytes, uint8_t* __restrict__ dst) {
+  const int64_t a = row0 + blockIdx.x / chunks;
+  const int64_t g = (int64_t(blockIdx.x % chunks) * 256 + threadIdx.x) * 16;
+  if (g >= row_bytes) return;
+  const CheckRow row = rows[a];
+  const int64_t valid = row.valid;
+  const int n = int(row_bytes - g < 16 ? row_bytes - g : 16);  // even
+  const uint8_t* sp = row.src + g;
+  uint8_t* dp = dst + a * row_bytes + g;
+  const uintptr_t dal = reinterpret_cast<uintptr_t>(dp);
+  if (n == 16 && g + 16 <= valid) {
+    const uintptr_t al = reinterpret_cast<uintptr_t>(sp) | dal;
+    if ((al & 15) == 0) {
+      *reinterpret_cast<uint4*>(dp) = *reinterpret_cast<const uint4*>(sp);
+    } else if ((al & 3) == 0) {
+      uint32_t v[4];
+      sfor<4>([&](auto j) { v[decltype(j)::value] = reinterpret_cast<const uint32_t*>(sp)[decltype(j)::value]; });
+      sfor<4>([&](auto j) { reinterpret_cast<uint32_t*>(dp)[decltype(j)::value] = v[decltype(j)::value]; });
+    } else {
+      uint16_t v[8];
+      sfor<8>([&](auto j) { v[decltype(j)::value] = reinterpret_cast<const uint16_t*>(sp)[decltype(j)::value]; });
+      sfor<8>([&](auto j) { reinterpret_cast<uint16_t*>(dp)[decltype(j)::value] = v[decltype(j)::value]; });
+    }
+    return;
+  }
+  if (n == 16 && g >= valid && (dal & 15) == 0) {
+    *reinterpret_cast<uint4*>(dp) = make_uint4(0u, 0u, 0u, 0u);
+    return;
+  }
+  for (int e = 0; e < n; e += 2) {
+    uint16_t v = 0;
+    if (g + e + 2 <= valid)
+      v = *reinterpret_cast<const uint16_t*>(sp + e);
+    else if (g + e < valid)
+      v = sp[e];  // the blob's odd last byte; the element's high byte is padding
+    *reinterpret_cast<uint16_t*>(dp + e) = v;
+  }
+}
+
 // Small host -> device uploads (rs2_engine.cpp UploadSlots): the kernel reads the pinned,
 // device-mapped host slot over PCIe and writes the device buffer, in stream order like any
 // launch -- no DMA-engine copy, whose cross-engine dependency on the stream's earlier kernels
@@ -420,6 +471,23 @@ hipError_t rs2k_launch_row_gather(const uint8_t* src, const int64_t* d_src_off, 
   hipLaunchKernelGGL(rs2::row_gather_kernel, dim3(unsigned(bx), unsigned(rows)), dim3(256), 0,
                      stream, src, d_src_off, dst, row_bytes);
   return hipGetLastError();
+}
+
+hipError_t rs2k_launch_check_rows_gather(const rs2::CheckRow* d_rows, int64_t n_rows,
+                                         int64_t row_bytes, uint8_t* dst, hipStream_t stream) {
+  if (n_rows <= 0 || row_bytes <= 0) return hipSuccess;
+  const int64_t chunks = (row_bytes + 4095) / 4096;
+  if (chunks >= (int64_t(1) << 31)) return hipErrorInvalidValue;
+  // as many rows per launch as grid.x can count
+  const int64_t per_launch = ((int64_t(1) << 31) - 1) / chunks;
+  for (int64_t row0 = 0; row0 < n_rows; row0 += per_launch) {
+    const int64_t cnt = std::min(per_launch, n_rows - row0);
+    hipLaunchKernelGGL(rs2::check_rows_gather_kernel, dim3(unsigned(cnt * chunks)), dim3(256), 0,
+                       stream, d_rows, row0, uint32_t(chunks), row_bytes, dst);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
 }
 
 hipError_t rs2k_launch_host_upload(const void* src, void* dst, int64_t n, uint64_t* done,

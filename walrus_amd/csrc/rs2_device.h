@@ -164,4 +164,21 @@ struct SymbolMap {
   int64_t primary_stride, secondary_stride, both_stride, leaf_stride;
 };
 
+// A verified decode batch's check tables (rs2_decode_and_verify_batch_*), one window at a time.
+// A row the Default check hashes: where it starts in its decoded blob, how many of its bytes lie
+// inside the blob (the rest is hashed as zeros, never read) and its sliver-pair index.
+struct CheckRow {
+  const uint8_t* src;
+  uint32_t valid;
+  uint32_t pair;
+};
+// A slot of the window: its rows in the window's row table (Default; none: nothing to check),
+// or kCheckSkipped in `rows` for a blob that was refused on the host.
+struct CheckSlot {
+  uint32_t first;
+  uint32_t rows;
+};
+constexpr uint32_t kCheckSkipped = 0xFFFFFFFFu;
+static_assert(sizeof(CheckRow) == 16 && sizeof(CheckSlot) == 8, "check tables are packed");
+
 }  // namespace rs2

@@ -1376,6 +1376,13 @@ struct rs2_plan {
   rs2_verifier* check_v = nullptr;
   DevBuf check_src, check_rows, check_roots;
   std::vector<int64_t> check_src_h;
+  // verified decode batches (rs2_decode_and_verify_batch_*): one window's row and slot tables,
+  // gathered rows and roots (Default), re-encoded slivers, hashes and ids (Strict), the call's
+  // blob lengths; the host-buffer form's metadata and verdicts.  vb_done: the last call's work,
+  // which the next call's stream waits for before it reuses them.
+  DevBuf vb_row_tab, vb_slot_tab, vb_rows, vb_roots, vb_primary, vb_secondary, vb_hashes, vb_ids,
+      vb_lens, vb_h_hashes, vb_h_ids, vb_h_verdict;
+  hipEvent_t vb_done = nullptr;
   // opt-in stage profiler: events recorded between consecutive launches on the stream
   struct Prof {
     bool on = false;
@@ -1399,6 +1406,7 @@ struct rs2_plan {
     if (leaf_ev) (void)hipEventDestroy(leaf_ev);
     if (aux) (void)hipStreamDestroy(aux);
     if (enc_done) (void)hipEventDestroy(enc_done);
+    if (vb_done) (void)hipEventDestroy(vb_done);
     if (side) (void)hipStreamDestroy(side);
     if (side_hi) (void)hipStreamDestroy(side_hi);
     if (io) (void)hipStreamDestroy(io);
@@ -1803,7 +1811,8 @@ int encode_device(rs2_plan* p, const uint8_t* d_blob, uint8_t* d_primary, uint8_
 int encode_batch_device(rs2_plan* p, uint32_t n_blobs, const uint8_t* d_blobs, int64_t blob_stride,
                         const uint64_t* lens, uint8_t* d_primary, int64_t p_stride,
                         uint8_t* d_secondary, int64_t s_stride, uint8_t* d_hashes,
-                        uint8_t* d_blob_ids, hipStream_t st) {
+                        uint8_t* d_blob_ids, hipStream_t st,
+                        const uint64_t* d_lens_ready = nullptr) {
   const int64_t s = p->s, n = p->n, kp = p->kp, ks = p->ks;
   const int64_t msg = kp * ks * s, pl = ks * s, sl = kp * s;
   if (n_blobs == 0) return RS2_OK;
@@ -1828,13 +1837,15 @@ int encode_batch_device(rs2_plan* p, uint32_t n_blobs, const uint8_t* d_blobs, i
   HIP_TRY(p->batch_both.ensure(size_t(n_blobs) * both_b));
   HIP_TRY(p->batch_leaves.ensure(size_t(n_blobs) * leaves_b));
   RS2_TRY(bind_encode_buffers(p, d_primary, d_secondary, st, p->batch_both.as<uint8_t>()));
-  if (lv != p->batch_lens_h) {  // upload the lengths (the host copy stays alive until it lands)
+  // d_lens_ready: the caller has the same lengths on the device already (a verified decode
+  // batch uploads its call's lengths once, so no run of a window waits for the one before)
+  if (!d_lens_ready && lv != p->batch_lens_h) {  // upload the lengths (the host copy stays alive until it lands)
     if (p->enc_done) HIP_TRY(hipEventSynchronize(p->enc_done));
     p->batch_lens_h = lv;
     HIP_TRY(p->batch_lens.ensure(lv.size() * 8));
     HIP_TRY(p->ctx->upload(p->batch_lens.p, p->batch_lens_h.data(), lv.size() * 8, st));
   }
-  const uint64_t* d_lens = p->batch_lens.as<uint64_t>();
+  const uint64_t* d_lens = d_lens_ready ? d_lens_ready : p->batch_lens.as<uint64_t>();
   const int B = int(n_blobs);
   mark(p, "", st);
   HIP_TRY(rs2k_launch_batch_blob_copy(d_blobs, blob_stride, d_lens, msg, d_primary, p_stride, B, st));
@@ -2095,6 +2106,10 @@ struct BatchItem {
   std::vector<std::pair<uint16_t, uint32_t>> chosen;
   const uint64_t* off = nullptr;
   uint8_t* out = nullptr;
+  // the input indices the decoder consumed (select_slivers' *pulled): what the Default check of
+  // a verified batch counts as already verified
+  const uint16_t* idx = nullptr;
+  uint32_t pulled = 0;
 };
 
 // A blob planned for the batch kernel (on a pool thread): its job, narrowed and with the
@@ -2333,6 +2348,52 @@ int batch_blob_len(const rs2_plan* p, const uint64_t* blob_lens, uint32_t b, uin
   return RS2_OK;
 }
 
+// The per-blob rules of the device batch calls (rs2_decode_batch_device_async and its verified
+// form) for every blob: the accepted blobs in `items`, in slot order.  status_out NULL: the first
+// failing blob's code is returned; non-NULL: every blob's code is stored, RS2_OK.
+int validate_batch_device(const rs2_plan* plan, int axis, uint32_t n_blobs,
+                          const uint64_t* blob_lens, const uint32_t* counts,
+                          const uint16_t* sliver_idx, const uint64_t* sliver_off,
+                          void* d_blobs_out, uint64_t out_stride, int* status_out,
+                          std::vector<BatchItem>& items) {
+  items.clear();
+  items.reserve(n_blobs);
+  size_t first = 0;
+  for (uint32_t b = 0; b < n_blobs; first += counts[b], ++b) {
+    BatchItem it;
+    it.blob = b;
+    it.off = sliver_off + first;
+    it.idx = sliver_idx + first;
+    it.out = reinterpret_cast<uint8_t*>(d_blobs_out) + uint64_t(b) * out_stride;
+    auto validate = [&]() -> int {
+      RS2_TRY(batch_blob_len(plan, blob_lens, b, &it.len));
+      if (n_blobs > 1 && it.len > out_stride)
+        return fail(RS2_E_INVALID_ARGUMENT, "out_stride smaller than a blob");
+      for (uint32_t i = 0; i < counts[b]; ++i)
+        RS2_TRY(check_symbol_step(it.off[i], "sliver_off[i]"));
+      return select_slivers(plan, axis, counts[b], it.idx, nullptr, nullptr, it.chosen,
+                            &it.pulled);
+    };
+    const int rc = validate();
+    if (status_out)
+      status_out[b] = rc;
+    else if (rc != RS2_OK)
+      return rc;
+    if (rc == RS2_OK) items.push_back(std::move(it));
+  }
+  return RS2_OK;
+}
+
+// The host-buffer batch decode, plain (check == kNoCheck: rs2_decode_batch) or verified
+// (rs2_decode_and_verify_batch); defined with the verified batch below.
+constexpr int kNoCheck = -1;
+int decode_batch_host(rs2_plan* plan, int axis, uint32_t n_blobs, const uint64_t* blob_lens,
+                      const uint32_t* counts, const uint16_t* sliver_idx,
+                      const uint8_t* const* slivers, const uint64_t* sliver_len,
+                      const uint16_t* sliver_symbol_size, const uint8_t* hashes,
+                      const uint8_t* blob_ids, int check, uint8_t* const* blobs_out,
+                      int32_t* verdict_out, int* status_out);
+
 }  // namespace
 
 // =============================================================================================
@@ -2454,7 +2515,7 @@ void rs2_plan_destroy(rs2_plan* plan) {
   for (hipStream_t st : {plan->stream, plan->side, plan->side_hi, plan->aux, plan->io})
     if (st) (void)hipStreamSynchronize(st);
   for (hipEvent_t ev : {plan->enc_done, plan->dec[0].done, plan->dec[1].done, plan->leaf_ev,
-                        plan->dbatch[0].done, plan->dbatch[1].done})
+                        plan->dbatch[0].done, plan->dbatch[1].done, plan->vb_done})
     if (ev) (void)hipEventSynchronize(ev);
   const Quiesced quiesced;
   delete plan;
@@ -2806,28 +2867,8 @@ int rs2_decode_batch_device_async(rs2_plan* plan, int axis, uint32_t n_blobs,
   HIP_TRY(hipSetDevice(plan->ctx->device));
   // every blob is validated before anything is enqueued
   std::vector<BatchItem> items;
-  items.reserve(n_blobs);
-  size_t first = 0;
-  for (uint32_t b = 0; b < n_blobs; first += counts[b], ++b) {
-    BatchItem it;
-    it.blob = b;
-    it.off = sliver_off + first;
-    it.out = reinterpret_cast<uint8_t*>(d_blobs_out) + uint64_t(b) * out_stride;
-    auto validate = [&]() -> int {
-      RS2_TRY(batch_blob_len(plan, blob_lens, b, &it.len));
-      if (n_blobs > 1 && it.len > out_stride)
-        return fail(RS2_E_INVALID_ARGUMENT, "out_stride smaller than a blob");
-      for (uint32_t i = 0; i < counts[b]; ++i)
-        RS2_TRY(check_symbol_step(it.off[i], "sliver_off[i]"));
-      return select_slivers(plan, axis, counts[b], sliver_idx + first, nullptr, nullptr, it.chosen);
-    };
-    const int rc = validate();
-    if (status_out)
-      status_out[b] = rc;
-    else if (rc != RS2_OK)
-      return rc;
-    if (rc == RS2_OK) items.push_back(std::move(it));
-  }
+  RS2_TRY(validate_batch_device(plan, axis, n_blobs, blob_lens, counts, sliver_idx, sliver_off,
+                                d_blobs_out, out_stride, status_out, items));
   return decode_batch_items(plan, axis, items, reinterpret_cast<const uint8_t*>(d_slivers_base),
                             pick_stream(plan, stream));
 }
@@ -2837,85 +2878,9 @@ int rs2_decode_batch(rs2_plan* plan, int axis, uint32_t n_blobs, const uint64_t*
                      const uint8_t* const* slivers, const uint64_t* sliver_len,
                      const uint16_t* sliver_symbol_size, uint8_t* const* blobs_out,
                      int* status_out) {
-  if (!plan) return fail(RS2_E_INVALID_ARGUMENT, "null plan");
-  if (axis != RS2_AXIS_PRIMARY && axis != RS2_AXIS_SECONDARY)
-    return fail(RS2_E_INVALID_ARGUMENT, "bad axis");
-  if (n_blobs == 0) return RS2_OK;
-  if (n_blobs > 65535) return fail(RS2_E_INVALID_ARGUMENT, "more than 65535 blobs in a batch");
-  if (!counts || !blobs_out) return fail(RS2_E_INVALID_ARGUMENT, "null argument");
-  size_t total = 0;
-  for (uint32_t b = 0; b < n_blobs; ++b) total += counts[b];
-  if (total && (!sliver_idx || !slivers || !sliver_len))
-    return fail(RS2_E_INVALID_ARGUMENT, "null argument");
-  HIP_TRY(hipSetDevice(plan->ctx->device));
-  RingGuard ring(plan);
-  Context* ctx = plan->ctx;
-  hipStream_t st = plan->stream;
-  const size_t len = size_t(axis == RS2_AXIS_PRIMARY ? primary_len(plan) : secondary_len(plan));
-  const uint32_t K = axis == RS2_AXIS_PRIMARY ? plan->kp : plan->ks;
-  const size_t msg = size_t(plan->kp) * plan->ks * plan->s;
-  const size_t ostride = (std::max<size_t>(msg, 16) + 255) / 256 * 256;
-  std::vector<BatchItem> items;
-  items.reserve(n_blobs);
-  size_t first = 0;
-  for (uint32_t b = 0; b < n_blobs; first += counts[b], ++b) {
-    BatchItem it;
-    it.blob = b;
-    auto validate = [&]() -> int {
-      RS2_TRY(batch_blob_len(plan, blob_lens, b, &it.len));
-      if (it.len && !blobs_out[b]) return fail(RS2_E_INVALID_ARGUMENT, "null output blob");
-      RS2_TRY(select_slivers(plan, axis, counts[b], sliver_idx + first, sliver_len + first,
-                             sliver_symbol_size ? sliver_symbol_size + first : nullptr, it.chosen));
-      for (const auto& c : it.chosen)
-        if (!slivers[first + c.second]) return fail(RS2_E_INVALID_ARGUMENT, "null sliver");
-      return RS2_OK;
-    };
-    const int rc = validate();
-    if (status_out)
-      status_out[b] = rc;
-    else if (rc != RS2_OK)
-      return rc;
-    if (rc != RS2_OK) continue;
-    for (auto& c : it.chosen) c.second = uint32_t(first + c.second);  // position in `slivers`
-    items.push_back(std::move(it));
-  }
-  // groups of blobs whose device slivers and outputs stay below a fixed budget
-  constexpr size_t kGroupBytes = size_t(512) << 20;
-  const size_t per_blob = size_t(K) * len + ostride;
-  const size_t group = std::max<size_t>(1, kGroupBytes / per_blob);
-  for (size_t g0 = 0; g0 < items.size(); g0 += group) {
-    const size_t g1 = std::min(items.size(), g0 + group), nb = g1 - g0;
-    HIP_TRY(plan->dbatch_in.ensure(nb * size_t(K) * len));
-    HIP_TRY(plan->dbatch_out.ensure(nb * ostride));
-    uint8_t* din = plan->dbatch_in.as<uint8_t>();
-    uint8_t* dout = plan->dbatch_out.as<uint8_t>();
-    std::vector<Seg> segs;
-    std::vector<std::vector<uint64_t>> offs(nb);
-    std::vector<BatchItem> part(items.begin() + g0, items.begin() + g1);
-    // the chosen slivers go to the device back to back: sliver k of the group's blob i at
-    // (i * K + k) * len
-    for (size_t i = 0; i < nb; ++i) {
-      BatchItem& it = part[i];
-      offs[i].resize(it.chosen.size());
-      for (size_t k = 0; k < it.chosen.size(); ++k) {
-        const size_t at = (i * K + k) * len;
-        segs.push_back({const_cast<uint8_t*>(slivers[it.chosen[k].second]), din + at, len});
-        offs[i][k] = at;
-        it.chosen[k].second = uint32_t(k);
-      }
-      it.off = offs[i].data();
-      it.out = dout + i * ostride;
-    }
-    RS2_TRY(stage_h2d(ctx, *plan->stage, segs, st));
-    RS2_TRY(decode_batch_items(plan, axis, part, din, st));
-    segs.clear();
-    for (size_t i = 0; i < nb; ++i)
-      if (part[i].len)
-        segs.push_back({blobs_out[part[i].blob], dout + i * ostride, size_t(part[i].len)});
-    if (!segs.empty()) RS2_TRY(stage_d2h(ctx, *plan->stage, segs, st));
-    HIP_TRY(hipStreamSynchronize(st));
-  }
-  return RS2_OK;
+  return decode_batch_host(plan, axis, n_blobs, blob_lens, counts, sliver_idx, slivers, sliver_len,
+                           sliver_symbol_size, nullptr, nullptr, kNoCheck, blobs_out, nullptr,
+                           status_out);
 }
 
 int rs2_decode_batch_stats(uint64_t* stats_out) {
@@ -3512,9 +3477,370 @@ int recover_items(rs2_verifier* v, uint32_t n_slivers, const std::vector<Recover
   }
   return RS2_OK;
 }
+// ---------------------------------------------------------------------------------------------
+// verified decode batches: many blobs, each decoded from its own slivers and checked against its
+// own metadata, a verdict per blob in device memory
+// ---------------------------------------------------------------------------------------------
+constexpr uint64_t kVerifyBatchBudget = uint64_t(256) << 20;
+std::atomic<uint64_t> g_vb_budget{kVerifyBatchBudget};
+std::atomic<uint64_t> g_vb_windows{0}, g_vb_blobs{0}, g_vb_rows{0}, g_vb_encoded{0};
+
+int check_value(int check) {
+  if (check == RS2_CHECK_SKIP || check == RS2_CHECK_DEFAULT || check == RS2_CHECK_STRICT)
+    return RS2_OK;
+  return fail(RS2_E_INVALID_ARGUMENT, "bad consistency check");
+}
+
+// Decode and check validated blobs (slot order; it.blob = the slot) of a call of n_slots slots on
+// st.  Slot b's metadata is at d_hashes + b*64n / d_ids + b*32, its verdict at d_verdict + b;
+// accepted blobs lie out_stride apart.  Slots that are not in `items` were refused:
+// RS2_BLOB_SKIPPED.  The slots are cut into windows (verify_windows: at most a decode chunk's
+// blobs, check scratch within the budget); per window the decodes, then the checks -- Default:
+// the unverified rows of every blob gathered back to back and hashed by one verifier_roots;
+// Strict: the blobs re-encoded in runs of neighbouring accepted slots -- then one verdict launch.
+// Every scratch buffer is sized for the largest window before the first one runs, so nothing is
+// re-allocated with work in flight and the call never waits for the device.
+int verify_batch_items(rs2_plan* p, int axis, uint32_t n_slots, const std::vector<BatchItem>& items,
+                       const uint8_t* base, const uint8_t* d_hashes, const uint8_t* d_ids,
+                       int check, int32_t* d_verdict, uint64_t out_stride, hipStream_t st) {
+  Context* ctx = p->ctx;
+  const int64_t n = p->n, kp = p->kp, ks = p->ks, s = p->s;
+  const int64_t row = ks * s, pl = primary_len(p), sl = secondary_len(p);
+  const int64_t both_b = (n - kp) * (n - ks) * s, leaves_b = n * n * 32;
+  const bool dflt = check == RS2_CHECK_DEFAULT, strict = check == RS2_CHECK_STRICT;
+  // per slot: the rows to hash (Default) and the check scratch
+  std::vector<std::vector<VerifyRow>> rows(dflt ? items.size() : 0);
+  std::vector<uint64_t> need(n_slots, 0);
+  const uint64_t row_need = uint64_t(row) + uint64_t(n) * 32 + uint64_t(n - ks) * s;
+  const uint64_t strict_need = uint64_t(n) * (pl + sl) + uint64_t(both_b) + uint64_t(leaves_b);
+  for (size_t i = 0; i < items.size(); ++i) {
+    const BatchItem& it = items[i];
+    if (dflt) {
+      verify_rows(uint32_t(kp), uint32_t(ks), uint32_t(s), axis, it.idx, it.pulled, it.len, rows[i]);
+      need[it.blob] = rows[i].size() * row_need;
+    } else if (strict) {
+      need[it.blob] = strict_need;
+    }
+  }
+  std::vector<uint32_t> ends;
+  verify_windows(need, g_vb_budget.load(std::memory_order_relaxed), kBatchChunkJobs, ends);
+  // the largest window: accepted blobs and rows
+  size_t max_cnt = 0, max_rows = 0;
+  {
+    size_t i = 0;
+    for (uint32_t w1 : ends) {
+      size_t cnt = 0, nr = 0;
+      for (; i < items.size() && items[i].blob < w1; ++i, ++cnt)
+        if (dflt) nr += rows[i].size();
+      max_cnt = std::max(max_cnt, cnt);
+      max_rows = std::max(max_rows, nr);
+    }
+  }
+  // the previous call's work (possibly on another stream) still owns the scratch
+  if (p->vb_done) HIP_TRY(hipStreamWaitEvent(st, p->vb_done, 0));
+  HIP_TRY(p->vb_slot_tab.ensure(kBatchChunkJobs * sizeof(CheckSlot)));
+  rs2_verifier* v = nullptr;
+  if (dflt && max_rows) {
+    if (!p->check_v) RS2_TRY(rs2_verifier_create(p->n, p->s, RS2_AXIS_PRIMARY, &p->check_v));
+    v = p->check_v;
+    HIP_TRY(p->vb_row_tab.ensure(max_rows * sizeof(CheckRow)));
+    HIP_TRY(p->vb_rows.ensure(max_rows * size_t(row)));
+    HIP_TRY(p->vb_roots.ensure(max_rows * 32));
+    HIP_TRY(v->leaves.ensure(max_rows * size_t(n) * 32));
+    HIP_TRY(v->repair.ensure(max_rows * size_t(n - ks) * size_t(s)));
+    if (const size_t sb = tree_scratch_bytes(int64_t(max_rows), v->n))
+      HIP_TRY(v->tree_scratch.ensure(sb));
+  }
+  if (strict && max_cnt) {
+    HIP_TRY(p->vb_primary.ensure(max_cnt * size_t(n * pl)));
+    HIP_TRY(p->vb_secondary.ensure(max_cnt * size_t(n * sl)));
+    HIP_TRY(p->vb_hashes.ensure(max_cnt * size_t(n) * 64));
+    HIP_TRY(p->vb_ids.ensure(kBatchChunkJobs * 32));
+    HIP_TRY(p->batch_both.ensure(max_cnt * size_t(both_b)));
+    HIP_TRY(p->batch_leaves.ensure(max_cnt * size_t(leaves_b)));
+    if (const size_t sb = tree_scratch_bytes(2 * n, n)) HIP_TRY(p->tree_scratch.ensure(sb));
+    // the call's blob lengths by slot, once (refused slots: 0, never read)
+    std::vector<uint64_t> lens(n_slots, 0);
+    for (const BatchItem& it : items) lens[it.blob] = it.len;
+    HIP_TRY(p->vb_lens.ensure(lens.size() * 8));
+    RS2_TRY(upload_pieces(ctx, p->vb_lens.p, lens.data(), lens.size() * 8, st));
+  }
+  size_t next_item = 0;
+  uint32_t w0 = 0;
+  for (uint32_t w1 : ends) {
+    const uint32_t wn = w1 - w0;
+    const size_t i0 = next_item;
+    while (next_item < items.size() && items[next_item].blob < w1) ++next_item;
+    const size_t cnt = next_item - i0;
+    // 1. the window's decodes
+    if (cnt) {
+      const std::vector<BatchItem> part(items.begin() + i0, items.begin() + next_item);
+      RS2_TRY(decode_batch_items(p, axis, part, base, st));
+    }
+    // 2. its checks
+    std::vector<CheckSlot> slots(wn, CheckSlot{0, kCheckSkipped});
+    size_t n_rows = 0;
+    if (dflt) {
+      std::vector<CheckRow> tab;
+      for (size_t i = i0; i < next_item; ++i) {
+        const BatchItem& it = items[i];
+        slots[it.blob - w0] = CheckSlot{uint32_t(tab.size()), uint32_t(rows[i].size())};
+        for (const VerifyRow& r : rows[i])
+          tab.push_back(CheckRow{it.out + int64_t(r.row) * row, r.valid, r.row});
+      }
+      n_rows = tab.size();
+      if (n_rows) {
+        mark(p, "", st);
+        RS2_TRY(upload_pieces(ctx, p->vb_row_tab.p, tab.data(), n_rows * sizeof(CheckRow), st));
+        HIP_TRY(rs2k_launch_check_rows_gather(p->vb_row_tab.as<CheckRow>(), int64_t(n_rows), row,
+                                              p->vb_rows.as<uint8_t>(), st));
+        mark(p, "ver_batch_rows", st);
+        RS2_TRY(verifier_roots(v, uint32_t(n_rows), p->vb_rows.as<uint8_t>(),
+                               p->vb_roots.as<uint8_t>(), st));
+        mark(p, "ver_batch_roots", st);
+      }
+    } else {
+      for (size_t i = i0; i < next_item; ++i) slots[items[i].blob - w0] = CheckSlot{0, 0};
+    }
+    if (strict && cnt) {
+      mark(p, "", st);
+      const bool prof_on = p->prof.on;
+      p->prof.on = false;  // one stage for the window's encodes, not encode_batch_device's own
+      int rc = RS2_OK;
+      // runs of neighbouring accepted slots: a refused blob's slot is never read
+      for (size_t a = i0; a < next_item && rc == RS2_OK;) {
+        size_t b = a + 1;
+        while (b < next_item && items[b].blob == items[b - 1].blob + 1) ++b;
+        const uint32_t slot = items[a].blob;
+        std::vector<uint64_t> lens(b - a);
+        for (size_t i = a; i < b; ++i) lens[i - a] = items[i].len;
+        rc = encode_batch_device(p, uint32_t(b - a), items[a].out, int64_t(out_stride), lens.data(),
+                                 p->vb_primary.as<uint8_t>(), n * pl,
+                                 p->vb_secondary.as<uint8_t>(), n * sl, p->vb_hashes.as<uint8_t>(),
+                                 p->vb_ids.as<uint8_t>() + size_t(slot - w0) * 32, st,
+                                 p->vb_lens.as<uint64_t>() + slot);
+        a = b;
+      }
+      p->prof.on = prof_on;
+      RS2_TRY(rc);
+      mark(p, "ver_batch_encode", st);
+      g_vb_encoded.fetch_add(cnt, std::memory_order_relaxed);
+    }
+    // 3. its verdicts
+    mark(p, "", st);
+    RS2_TRY(upload_pieces(ctx, p->vb_slot_tab.p, slots.data(), wn * sizeof(CheckSlot), st));
+    if (strict)
+      HIP_TRY(rs2k_launch_blob_verdict(p->vb_slot_tab.as<CheckSlot>(), int(wn), nullptr,
+                                       p->vb_ids.as<uint8_t>(), d_ids + size_t(w0) * 32, 32, 1,
+                                       d_verdict + w0, st));
+    else
+      HIP_TRY(rs2k_launch_blob_verdict(p->vb_slot_tab.as<CheckSlot>(), int(wn),
+                                       p->vb_row_tab.as<CheckRow>(), p->vb_roots.as<uint8_t>(),
+                                       dflt ? d_hashes + size_t(w0) * 64 * size_t(n) : nullptr,
+                                       64 * n, 0, d_verdict + w0, st));
+    mark(p, "ver_batch_verdict", st);
+    g_vb_windows.fetch_add(1, std::memory_order_relaxed);
+    if (dflt || strict) g_vb_blobs.fetch_add(cnt, std::memory_order_relaxed);
+    g_vb_rows.fetch_add(n_rows, std::memory_order_relaxed);
+    w0 = w1;
+  }
+  if (v) RS2_TRY(verifier_mark_done(v, st));
+  if (!p->vb_done) HIP_TRY(hipEventCreateWithFlags(&p->vb_done, hipEventDisableTiming));
+  HIP_TRY(hipEventRecord(p->vb_done, st));
+  return RS2_OK;
+}
+
+// The argument rules the two forms of the verified batch share.
+int check_verify_batch_args(int check, const void* hashes, const void* blob_ids,
+                            const void* verdict) {
+  RS2_TRY(check_value(check));
+  if (!verdict) return fail(RS2_E_INVALID_ARGUMENT, "null verdicts");
+  if (check == RS2_CHECK_DEFAULT && !hashes) return fail(RS2_E_INVALID_ARGUMENT, "null hashes");
+  if (check == RS2_CHECK_STRICT && !blob_ids) return fail(RS2_E_INVALID_ARGUMENT, "null blob ids");
+  return RS2_OK;
+}
+
+int decode_batch_host(rs2_plan* plan, int axis, uint32_t n_blobs, const uint64_t* blob_lens,
+                      const uint32_t* counts, const uint16_t* sliver_idx,
+                      const uint8_t* const* slivers, const uint64_t* sliver_len,
+                      const uint16_t* sliver_symbol_size, const uint8_t* hashes,
+                      const uint8_t* blob_ids, int check, uint8_t* const* blobs_out,
+                      int32_t* verdict_out, int* status_out) {
+  if (!plan) return fail(RS2_E_INVALID_ARGUMENT, "null plan");
+  if (axis != RS2_AXIS_PRIMARY && axis != RS2_AXIS_SECONDARY)
+    return fail(RS2_E_INVALID_ARGUMENT, "bad axis");
+  const bool verify = check != kNoCheck;
+  if (verify) RS2_TRY(check_verify_batch_args(check, hashes, blob_ids, verdict_out));
+  if (n_blobs == 0) return RS2_OK;
+  if (n_blobs > 65535) return fail(RS2_E_INVALID_ARGUMENT, "more than 65535 blobs in a batch");
+  if (!counts || !blobs_out) return fail(RS2_E_INVALID_ARGUMENT, "null argument");
+  size_t total = 0;
+  for (uint32_t b = 0; b < n_blobs; ++b) total += counts[b];
+  if (total && (!sliver_idx || !slivers || !sliver_len))
+    return fail(RS2_E_INVALID_ARGUMENT, "null argument");
+  HIP_TRY(hipSetDevice(plan->ctx->device));
+  RingGuard ring(plan);
+  Context* ctx = plan->ctx;
+  hipStream_t st = plan->stream;
+  const size_t len = size_t(axis == RS2_AXIS_PRIMARY ? primary_len(plan) : secondary_len(plan));
+  const uint32_t K = axis == RS2_AXIS_PRIMARY ? plan->kp : plan->ks;
+  const size_t msg = size_t(plan->kp) * plan->ks * plan->s;
+  const size_t ostride = (std::max<size_t>(msg, 16) + 255) / 256 * 256;
+  const size_t hashes_b = size_t(plan->n) * 64;
+  std::vector<BatchItem> items;
+  items.reserve(n_blobs);
+  size_t first = 0;
+  for (uint32_t b = 0; b < n_blobs; first += counts[b], ++b) {
+    BatchItem it;
+    it.blob = b;
+    it.idx = sliver_idx + first;
+    auto validate = [&]() -> int {
+      RS2_TRY(batch_blob_len(plan, blob_lens, b, &it.len));
+      if (it.len && !blobs_out[b]) return fail(RS2_E_INVALID_ARGUMENT, "null output blob");
+      RS2_TRY(select_slivers(plan, axis, counts[b], sliver_idx + first, sliver_len + first,
+                             sliver_symbol_size ? sliver_symbol_size + first : nullptr, it.chosen,
+                             &it.pulled));
+      for (const auto& c : it.chosen)
+        if (!slivers[first + c.second]) return fail(RS2_E_INVALID_ARGUMENT, "null sliver");
+      return RS2_OK;
+    };
+    const int rc = validate();
+    if (status_out)
+      status_out[b] = rc;
+    else if (rc != RS2_OK)
+      return rc;
+    if (rc != RS2_OK) continue;
+    for (auto& c : it.chosen) c.second = uint32_t(first + c.second);  // position in `slivers`
+    items.push_back(std::move(it));
+  }
+  if (verify) std::fill(verdict_out, verdict_out + n_blobs, int32_t(RS2_BLOB_SKIPPED));
+  // groups of blobs whose device slivers and outputs stay below a fixed budget
+  constexpr size_t kGroupBytes = size_t(512) << 20;
+  const size_t per_blob = size_t(K) * len + ostride;
+  const size_t group = std::max<size_t>(1, kGroupBytes / per_blob);
+  for (size_t g0 = 0; g0 < items.size(); g0 += group) {
+    const size_t g1 = std::min(items.size(), g0 + group), nb = g1 - g0;
+    HIP_TRY(plan->dbatch_in.ensure(nb * size_t(K) * len));
+    HIP_TRY(plan->dbatch_out.ensure(nb * ostride));
+    uint8_t* din = plan->dbatch_in.as<uint8_t>();
+    uint8_t* dout = plan->dbatch_out.as<uint8_t>();
+    std::vector<Seg> segs;
+    std::vector<std::vector<uint64_t>> offs(nb);
+    std::vector<BatchItem> part(items.begin() + g0, items.begin() + g1);
+    // the chosen slivers go to the device back to back: sliver k of the group's blob i at
+    // (i * K + k) * len
+    for (size_t i = 0; i < nb; ++i) {
+      BatchItem& it = part[i];
+      offs[i].resize(it.chosen.size());
+      for (size_t k = 0; k < it.chosen.size(); ++k) {
+        const size_t at = (i * K + k) * len;
+        segs.push_back({const_cast<uint8_t*>(slivers[it.chosen[k].second]), din + at, len});
+        offs[i][k] = at;
+        it.chosen[k].second = uint32_t(k);
+      }
+      it.off = offs[i].data();
+      it.out = dout + i * ostride;
+    }
+    if (!verify) {
+      RS2_TRY(stage_h2d(ctx, *plan->stage, segs, st));
+      RS2_TRY(decode_batch_items(plan, axis, part, din, st));
+    } else {
+      // the group's metadata beside its slivers, by the group's own slots 0 .. nb
+      uint8_t *dh = nullptr, *di = nullptr;
+      if (check == RS2_CHECK_DEFAULT) {
+        HIP_TRY(plan->vb_h_hashes.ensure(nb * hashes_b));
+        dh = plan->vb_h_hashes.as<uint8_t>();
+      } else if (check == RS2_CHECK_STRICT) {
+        HIP_TRY(plan->vb_h_ids.ensure(nb * 32));
+        di = plan->vb_h_ids.as<uint8_t>();
+      }
+      HIP_TRY(plan->vb_h_verdict.ensure(nb * 4));
+      for (size_t i = 0; i < nb; ++i) {
+        const size_t b = part[i].blob;
+        if (dh) segs.push_back({const_cast<uint8_t*>(hashes) + b * hashes_b, dh + i * hashes_b, hashes_b});
+        if (di) segs.push_back({const_cast<uint8_t*>(blob_ids) + b * 32, di + i * 32, 32});
+        part[i].blob = uint32_t(i);
+      }
+      RS2_TRY(stage_h2d(ctx, *plan->stage, segs, st));
+      RS2_TRY(verify_batch_items(plan, axis, uint32_t(nb), part, din, dh, di, check,
+                                 plan->vb_h_verdict.as<int32_t>(), ostride, st));
+    }
+    segs.clear();
+    for (size_t i = 0; i < nb; ++i)
+      if (items[g0 + i].len)
+        segs.push_back({blobs_out[items[g0 + i].blob], dout + i * ostride, size_t(items[g0 + i].len)});
+    std::vector<int32_t> verdicts(verify ? nb : 0);
+    if (verify)
+      segs.push_back({reinterpret_cast<uint8_t*>(verdicts.data()), plan->vb_h_verdict.as<uint8_t>(), nb * 4});
+    if (!segs.empty()) RS2_TRY(stage_d2h(ctx, *plan->stage, segs, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    for (size_t i = 0; i < verdicts.size(); ++i) verdict_out[items[g0 + i].blob] = verdicts[i];
+  }
+  return RS2_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int rs2_decode_and_verify_batch_device_async(
+    rs2_plan* plan, int axis, uint32_t n_blobs, const uint64_t* blob_lens, const uint32_t* counts,
+    const uint16_t* sliver_idx, const void* d_slivers_base, const uint64_t* sliver_off,
+    const void* d_hashes, const void* d_blob_ids, int consistency_check, void* d_blobs_out,
+    uint64_t out_stride, void* d_verdict, int* status_out, void* stream) {
+  if (!plan) return fail(RS2_E_INVALID_ARGUMENT, "null plan");
+  if (axis != RS2_AXIS_PRIMARY && axis != RS2_AXIS_SECONDARY)
+    return fail(RS2_E_INVALID_ARGUMENT, "bad axis");
+  RS2_TRY(check_verify_batch_args(consistency_check, d_hashes, d_blob_ids, d_verdict));
+  RS2_TRY(check_digest_ptr(d_hashes, "d_hashes"));
+  RS2_TRY(check_digest_ptr(d_blob_ids, "d_blob_ids"));
+  RS2_TRY(check_digest_ptr(d_verdict, "d_verdict"));
+  if (n_blobs == 0) return RS2_OK;
+  if (n_blobs > 65535) return fail(RS2_E_INVALID_ARGUMENT, "more than 65535 blobs in a batch");
+  if (!counts || !sliver_idx || !sliver_off || !d_slivers_base || !d_blobs_out)
+    return fail(RS2_E_INVALID_ARGUMENT, "null argument");
+  RS2_TRY(check_symbol_ptr(d_slivers_base, "d_slivers_base"));
+  RS2_TRY(check_symbol_ptr(d_blobs_out, "d_blobs_out"));
+  RS2_TRY(check_symbol_step(out_stride, "out_stride"));
+  HIP_TRY(hipSetDevice(plan->ctx->device));
+  // every blob is validated before anything is enqueued
+  std::vector<BatchItem> items;
+  RS2_TRY(validate_batch_device(plan, axis, n_blobs, blob_lens, counts, sliver_idx, sliver_off,
+                                d_blobs_out, out_stride, status_out, items));
+  return verify_batch_items(plan, axis, n_blobs, items,
+                            reinterpret_cast<const uint8_t*>(d_slivers_base),
+                            reinterpret_cast<const uint8_t*>(d_hashes),
+                            reinterpret_cast<const uint8_t*>(d_blob_ids), consistency_check,
+                            reinterpret_cast<int32_t*>(d_verdict), out_stride,
+                            pick_stream(plan, stream));
+}
+
+int rs2_decode_and_verify_batch(rs2_plan* plan, int axis, uint32_t n_blobs,
+                                const uint64_t* blob_lens, const uint32_t* counts,
+                                const uint16_t* sliver_idx, const uint8_t* const* slivers,
+                                const uint64_t* sliver_len, const uint16_t* sliver_symbol_size,
+                                const uint8_t* hashes, const uint8_t* blob_ids,
+                                int consistency_check, uint8_t* const* blobs_out,
+                                int32_t* verdict_out, int* status_out) {
+  RS2_TRY(check_value(consistency_check));  // (kNoCheck is not a value of the ABI)
+  return decode_batch_host(plan, axis, n_blobs, blob_lens, counts, sliver_idx, slivers, sliver_len,
+                           sliver_symbol_size, hashes, blob_ids, consistency_check, blobs_out,
+                           verdict_out, status_out);
+}
+
+int rs2_set_verify_batch_budget(uint64_t bytes) {
+  g_vb_budget.store(bytes ? bytes : kVerifyBatchBudget, std::memory_order_relaxed);
+  return RS2_OK;
+}
+
+int rs2_verify_batch_stats(uint64_t* stats_out) {
+  if (!stats_out) return fail(RS2_E_INVALID_ARGUMENT, "null argument");
+  stats_out[0] = g_vb_windows.load(std::memory_order_relaxed);
+  stats_out[1] = g_vb_blobs.load(std::memory_order_relaxed);
+  stats_out[2] = g_vb_rows.load(std::memory_order_relaxed);
+  stats_out[3] = g_vb_encoded.load(std::memory_order_relaxed);
+  return RS2_OK;
+}
 
 int rs2_verifier_roots_device_async(rs2_verifier* v, uint32_t count, const void* d_slivers,
                                     void* d_roots, void* stream) {

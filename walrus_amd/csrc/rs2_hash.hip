@@ -1054,6 +1054,46 @@ __global__ void __launch_bounds__(64)
   verdict[i] = diff == 0 ? 1 : 0;
 }
 
+// Verdicts of one window of a verified decode batch (rs2_decode_and_verify_batch_*), a wave per
+// slot of the window.  A slot refused on the host (slots[b].rows == kCheckSkipped) is
+// RS2_BLOB_SKIPPED and nothing of it is read.  Default (strict == 0): the slot's rows
+// [first, first + rows) of the window's row table each have a 32-byte root at roots + 32 r, which
+// must equal the primary hash of the row's pair in the slot's metadata (expected +
+// b * expected_stride + 64 pair); no rows (nothing left to check, or RS2_CHECK_SKIP) is a match.
+// Strict: the 32 bytes at roots + 32 b (the re-derived blob id) against expected +
+// b * expected_stride, a dword per lane.  The wave ORs its lanes' differences and lane 0 stores
+// the slot's one verdict, so the result depends on no order between waves or launches.
+__global__ void __launch_bounds__(64)
+    blob_verdict_kernel(const CheckSlot* __restrict__ slots, const CheckRow* __restrict__ rows,
+                        const uint8_t* __restrict__ roots, const uint8_t* __restrict__ expected,
+                        int64_t expected_stride, int strict, int32_t* __restrict__ verdict) {
+  const int b = blockIdx.x;
+  const int lane = threadIdx.x;
+  const CheckSlot sl = slots[b];
+  if (sl.rows == kCheckSkipped) {
+    if (lane == 0) verdict[b] = 2;
+    return;
+  }
+  const uint8_t* want = expected + int64_t(b) * expected_stride;
+  uint32_t diff = 0;
+  if (strict) {
+    if (lane < 8)
+      diff = reinterpret_cast<const uint32_t*>(roots + int64_t(b) * 32)[lane] ^
+             reinterpret_cast<const uint32_t*>(want)[lane];
+  } else {
+    for (uint32_t r = uint32_t(lane); r < sl.rows; r += 64) {
+      const int64_t at = int64_t(sl.first) + r;
+      const uint4* got = reinterpret_cast<const uint4*>(roots + at * 32);
+      const uint4* ex = reinterpret_cast<const uint4*>(want + int64_t(rows[at].pair) * 64);
+      const uint4 g0 = got[0], g1 = got[1], e0 = ex[0], e1 = ex[1];
+      diff |= (g0.x ^ e0.x) | (g0.y ^ e0.y) | (g0.z ^ e0.z) | (g0.w ^ e0.w) | (g1.x ^ e1.x) |
+              (g1.y ^ e1.y) | (g1.z ^ e1.z) | (g1.w ^ e1.w);
+    }
+  }
+  const bool mismatch = __ballot(diff != 0) != 0;
+  if (lane == 0) verdict[b] = mismatch ? 0 : 1;
+}
+
 // Node j of level L of the tree over n pair leaves (pair q = 64 bytes at pair_hashes + 64 q,
 // leaf-hashed with prefix 0x00), computed in registers (see fold_node).
 template <int L>
@@ -1344,6 +1384,16 @@ hipError_t rs2k_launch_sliver_verdict(const uint8_t* d_roots, const uint8_t* d_e
   if (count <= 0) return hipSuccess;
   hipLaunchKernelGGL(rs2::sliver_verdict_kernel, dim3(unsigned((count + 63) / 64)), dim3(64), 0,
                      stream, d_roots, d_expected, d_skipped, count, d_verdict);
+  return hipGetLastError();
+}
+
+hipError_t rs2k_launch_blob_verdict(const rs2::CheckSlot* d_slots, int n_slots,
+                                    const rs2::CheckRow* d_rows, const uint8_t* d_roots,
+                                    const uint8_t* d_expected, int64_t expected_stride, int strict,
+                                    int32_t* d_verdict, hipStream_t stream) {
+  if (n_slots <= 0) return hipSuccess;
+  hipLaunchKernelGGL(rs2::blob_verdict_kernel, dim3(unsigned(n_slots)), dim3(64), 0, stream,
+                     d_slots, d_rows, d_roots, d_expected, expected_stride, strict, d_verdict);
   return hipGetLastError();
 }
 

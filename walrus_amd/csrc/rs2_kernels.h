@@ -93,6 +93,14 @@ hipError_t rs2k_launch_tail_rows(const uint8_t* src, int64_t have, uint8_t* dst,
                                  hipStream_t stream);
 hipError_t rs2k_launch_row_gather(const uint8_t* src, const int64_t* d_src_off, uint8_t* dst,
                                   int64_t row_bytes, int rows, hipStream_t stream);
+// verified decode batches: the window's rows gathered back to back (d_rows: n_rows CheckRow),
+// and the verdicts of its n_slots slots (d_roots: a root per row, or with `strict` an id per slot)
+hipError_t rs2k_launch_check_rows_gather(const rs2::CheckRow* d_rows, int64_t n_rows,
+                                         int64_t row_bytes, uint8_t* dst, hipStream_t stream);
+hipError_t rs2k_launch_blob_verdict(const rs2::CheckSlot* d_slots, int n_slots,
+                                    const rs2::CheckRow* d_rows, const uint8_t* d_roots,
+                                    const uint8_t* d_expected, int64_t expected_stride, int strict,
+                                    int32_t* d_verdict, hipStream_t stream);
 hipError_t rs2k_launch_build_mul_tables(const uint16_t* d_exp, const uint16_t* d_log,
                                         const uint16_t* d_logs, int count, uint16_t* d_out,
                                         hipStream_t stream);

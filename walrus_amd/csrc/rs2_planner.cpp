@@ -636,4 +636,37 @@ void sliver_recover_spec(uint32_t k, uint32_t n, int symbol_size,
   sp.copy_present = originals > 0 && symbol_size >= 4 && may_fuse;
 }
 
+void verify_rows(uint32_t kp, uint32_t ks, uint32_t s, int axis, const uint16_t* pulled_idx,
+                 uint32_t pulled, uint64_t blob_len, std::vector<VerifyRow>& rows) {
+  rows.clear();
+  std::vector<uint8_t> verified(kp, 0);
+  if (axis == RS2_AXIS_PRIMARY)
+    for (uint32_t i = 0; i < pulled; ++i)
+      if (pulled_idx[i] < kp) verified[pulled_idx[i]] = 1;
+  const uint64_t row = uint64_t(ks) * s;
+  for (uint32_t i = 0; i < kp; ++i) {
+    if (verified[i]) continue;
+    const uint64_t at = uint64_t(i) * row;
+    rows.push_back({i, uint32_t(blob_len > at ? std::min(row, blob_len - at) : 0)});
+  }
+}
+
+void verify_windows(const std::vector<uint64_t>& need, uint64_t budget, size_t max_blobs,
+                    std::vector<uint32_t>& ends) {
+  ends.clear();
+  uint64_t used = 0;
+  size_t held = 0;
+  for (size_t b = 0; b < need.size(); ++b) {
+    // (need[b] > budget - used, not used + need[b] > budget: the sum may wrap)
+    if (held && (held == max_blobs || used > budget || need[b] > budget - used)) {
+      ends.push_back(uint32_t(b));
+      used = 0;
+      held = 0;
+    }
+    used += need[b];
+    ++held;
+  }
+  if (held) ends.push_back(uint32_t(need.size()));
+}
+
 }  // namespace rs2

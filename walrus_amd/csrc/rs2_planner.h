@@ -304,4 +304,33 @@ void sliver_recover_spec(uint32_t k, uint32_t n, int symbol_size,
                          const std::vector<std::pair<uint16_t, uint32_t>>& chosen,
                          const uint8_t* src, uint8_t* dst, bool may_fuse, DecodeSpec& sp);
 
+// ---------------------------------------------------------------------------------------------
+// verified decode batches (rs2_decode_and_verify_batch_*): the rows the Default check hashes and
+// the windows a call's checks run in
+// ---------------------------------------------------------------------------------------------
+// A systematic primary row the Default check re-expands: row index i < K_p (also its sliver-pair
+// index) and how many of its K_s * s bytes lie inside the blob; the rest is the message's zero
+// padding (0 valid bytes: the row is all padding).
+struct VerifyRow {
+  uint32_t row = 0;
+  uint32_t valid = 0;
+};
+inline bool operator==(const VerifyRow& a, const VerifyRow& b) {
+  return a.row == b.row && a.valid == b.valid;
+}
+
+// The rows of the Default check of a blob of blob_len bytes decoded from slivers of `axis`
+// (config.rs:621-640), ascending: with primary slivers every row whose index is not among the
+// `pulled` input indices the decoder consumed (select_slivers' prefix of the caller's list, the
+// surplus item that found the workspace full included), with secondary slivers all K_p rows.
+void verify_rows(uint32_t kp, uint32_t ks, uint32_t s, int axis, const uint16_t* pulled_idx,
+                 uint32_t pulled, uint64_t blob_len, std::vector<VerifyRow>& rows);
+
+// Windows of a verified batch over slots 0 .. need.size(): need[b] is the check scratch of slot b
+// in bytes (0: nothing to check, or a refused blob).  Slots are taken in order; a window closes
+// before the slot that would make it hold more than max_blobs slots or more than `budget` bytes,
+// and always holds at least one slot.  ends[w] = one past window w's last slot.
+void verify_windows(const std::vector<uint64_t>& need, uint64_t budget, size_t max_blobs,
+                    std::vector<uint32_t>& ends);
+
 }  // namespace rs2

@@ -27,6 +27,7 @@ PRIMARY = "primary"
 SECONDARY = "secondary"
 _AXIS = {PRIMARY: AXIS_PRIMARY, SECONDARY: AXIS_SECONDARY}
 _ORTHOGONAL = {PRIMARY: SECONDARY, SECONDARY: PRIMARY}
+_CHECK = {"skip": _lib.CHECK_SKIP, "default": _lib.CHECK_DEFAULT, "strict": _lib.CHECK_STRICT}
 DIGEST_LEN = 32
 ENCODING_TYPE_RS2 = 1
 
@@ -688,6 +689,55 @@ class ReedSolomonEncodingConfig:
                 decode=True)
         return out[:blob_size].tobytes()
 
+    def decode_and_verify_batch(self, items: Sequence[Tuple[VerifiedBlobMetadataWithId,
+                                                            Iterable[SliverData]]],
+                                consistency_check: str = "default") -> List[Optional[bytes]]:
+        """decode_and_verify of many blobs, [(metadata, slivers), ...], one batched device call
+        per group of blobs that share a symbol size and an axis (rs2_decode_and_verify_batch).
+        Returns the blob per item, in input order, or None where the check rejected it; a blob
+        the decode itself refuses raises its DecodeError, as in decode_batch."""
+        check = _CHECK[consistency_check.lower()]
+        metas = [m for m, _ in items]
+        args = [(int(m.metadata.unencoded_length),) + self._decode_args(slivers)
+                for m, slivers in items]
+        groups: Dict[Tuple[int, str], List[int]] = {}
+        for i, a in enumerate(args):
+            if a[0] > self.max_blob_size():
+                self._decode_plan(a[0])  # raises DecodeDataTooLarge
+            groups.setdefault((self.symbol_size_for_blob(a[0]), a[1]), []).append(i)
+        out: List = [None] * len(args)
+        for (_, axis), members in groups.items():
+            for c0 in range(0, len(members), 65535):
+                chunk = members[c0:c0 + 65535]
+                B = len(chunk)
+                top = max(args[i][0] for i in chunk)
+                plan = self._decode_plan(top)
+                lens = (ctypes.c_uint64 * B)(*[args[i][0] for i in chunk])
+                counts = (ctypes.c_uint32 * B)(*[len(args[i][2]) for i in chunk])
+                keep = [a for i in chunk for a in args[i][3]]
+                m = max(len(keep), 1)
+                idx = (ctypes.c_uint16 * m)(*[s.index for i in chunk for s in args[i][2]])
+                ptrs = (ctypes.c_void_p * m)(*[a.ctypes.data for a in keep])
+                slens = (ctypes.c_uint64 * m)(*[len(a) for a in keep])
+                syms = (ctypes.c_uint16 * m)(*[min(s.symbol_size, 0xFFFF)
+                                               for i in chunk for s in args[i][2]])
+                hb = np.frombuffer(b"".join(metas[i].metadata.hashes_bytes() for i in chunk),
+                                   dtype=np.uint8)
+                ids = np.frombuffer(b"".join(bytes(metas[i].blob_id) for i in chunk),
+                                    dtype=np.uint8)
+                outs = [np.empty(max(args[i][0], 1), dtype=np.uint8) for i in chunk]
+                op = (ctypes.c_void_p * B)(*[o.ctypes.data for o in outs])
+                verdict = (ctypes.c_int32 * B)()
+                with plan.lock:
+                    plan.bind(top)
+                    _ok(_lib.lib().rs2_decode_and_verify_batch(
+                        plan.handle, _AXIS[axis], B, lens, counts, idx, ptrs, slens, syms,
+                        hb.ctypes.data, ids.ctypes.data, check, op, verdict, None), decode=True)
+                for k, i in enumerate(chunk):
+                    if verdict[k] == _lib.RS2_BLOB_MATCH:
+                        out[i] = outs[k][:args[i][0]].tobytes()
+        return out
+
     # -- 1D helpers (config.rs:660-707) ----------------------------------------------------------
     def _encoder(self, axis: str, data_len: int) -> ReedSolomonEncoder:
         k = self.n_source_symbols(axis)
@@ -878,6 +928,20 @@ def decode_batch_stats() -> Dict[str, int]:
     return dict(zip(("launches", "batched", "single"), (int(v) for v in out)))
 
 
+def verify_batch_stats() -> Dict[str, int]:
+    """rs2_verify_batch_stats: check windows of verified decode batches, blobs checked (Default
+    or Strict), rows hashed by Default, blobs re-encoded by Strict (process-wide)."""
+    out = (ctypes.c_uint64 * 4)()
+    _ok(_lib.lib().rs2_verify_batch_stats(out))
+    return dict(zip(("windows", "checked", "rows", "encoded"), (int(v) for v in out)))
+
+
+def set_verify_batch_budget(nbytes: int = 0) -> None:
+    """rs2_set_verify_batch_budget: check scratch a window of a verified decode batch may hold
+    (0 restores the 256 MiB default)."""
+    _ok(_lib.lib().rs2_set_verify_batch_budget(int(nbytes)))
+
+
 def recover_stats() -> Dict[str, int]:
     """rs2_recover_stats: batched sliver-recovery launches, slivers decoded inside them, and
     slivers of recovery calls that took the per-sliver path (process-wide)."""
@@ -970,6 +1034,34 @@ class DevicePlan:
             self.handle, _AXIS[axis], B, lens, counts,
             idx.ctypes.data_as(ctypes.POINTER(ctypes.c_uint16)), d_base,
             off.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), d_out, out_stride,
+            status, _stream(stream)), decode=True)
+        return [int(v) for v in status[:B]] if statuses else None
+
+    def decode_and_verify_batch_async(self, axis: str,
+                                      blobs: Sequence[Tuple[Sequence[int], Sequence[int]]],
+                                      d_base: int, d_out: int, out_stride: int, d_hashes: int,
+                                      d_blob_ids: int, check: str, d_verdict: int,
+                                      blob_lens: Optional[Sequence[int]] = None,
+                                      stream: Optional[int] = None,
+                                      statuses: bool = False) -> Optional[List[int]]:
+        """rs2_decode_and_verify_batch_device_async: decode_batch_async plus the consistency
+        check ("skip" / "default" / "strict") of every blob against its own device-resident
+        metadata (blob b's pair hashes at d_hashes + b*64n, its id at d_blob_ids + b*32; 0 for
+        the one the check does not read).  d_verdict receives an int32 per blob (RS2_BLOB_*);
+        nothing is read back and the stream is not synchronised."""
+        B = len(blobs)
+        counts = (ctypes.c_uint32 * max(B, 1))(*[len(ix) for ix, _ in blobs])
+        idx = np.concatenate([np.asarray(ix, dtype=np.uint16) for ix, _ in blobs] +
+                             [np.zeros(1, dtype=np.uint16)])
+        off = np.concatenate([np.asarray(of, dtype=np.uint64) for _, of in blobs] +
+                             [np.zeros(1, dtype=np.uint64)])
+        lens = (ctypes.c_uint64 * max(B, 1))(*blob_lens) if blob_lens is not None else None
+        status = (ctypes.c_int * max(B, 1))() if statuses else None
+        _ok(_lib.lib().rs2_decode_and_verify_batch_device_async(
+            self.handle, _AXIS[axis], B, lens, counts,
+            idx.ctypes.data_as(ctypes.POINTER(ctypes.c_uint16)), d_base,
+            off.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), d_hashes or None,
+            d_blob_ids or None, _CHECK[check.lower()], d_out, out_stride, d_verdict,
             status, _stream(stream)), decode=True)
         return [int(v) for v in status[:B]] if statuses else None
 
