@@ -462,6 +462,62 @@ int rs2_verifier_recovery_symbols_device_async(rs2_verifier* v, uint32_t count,
                                                void* d_symbols, void* d_proofs, void* d_nodes,
                                                void* stream);
 
+/* ---- recovery symbols in bulk: a target list per sliver, cached trees -------------------------
+ * The serving side of a sliver recovery as the node's recovery-symbol service runs it: the
+ * service keeps the MerkleTree per (blob, source sliver) (recovery_symbol_service.rs:132-159)
+ * because one source sliver is asked for many targets -- a recovering peer that holds several
+ * shards asks for one symbol per shard, and after an epoch change the same slivers are asked
+ * again.  One call takes n_slivers source slivers of the verifier's axis (back to back in
+ * d_slivers, as for rs2_verifier_roots_device_async) and a list of targets per sliver:
+ * target_counts[i] (HOST, 0 allowed) targets of sliver i, consecutive in target_sliver_index
+ * (HOST, orthogonal-axis indices, any order, repeats allowed).  Request j is a position in that
+ * concatenated list; with path_len and n_nodes from rs2_merkle_tree_shape(n_shards) and
+ * k = the verifier's symbols per sliver:
+ *   d_slivers  n_slivers*k*symbol_size bytes, 2-byte aligned, read only
+ *   d_symbols  request j's expanded symbol (slivers.rs:180-213) at + j*symbol_size; 2-byte aligned
+ *   d_proofs   request j's MerkleTree::get_proof(target) (merkle.rs:281-309) at + j*path_len*32;
+ *              16-byte aligned
+ *   d_nodes    sliver i's tree at + i*n_nodes*32 in MerkleTree::nodes order (as the call above
+ *              writes it); 16-byte aligned
+ * Nothing outside these extents is read or written.  Each sliver is expanded and hashed once,
+ * however many targets it has.  trees selects where the trees come from: */
+#define RS2_TREES_BUILD  0  /* hash every sliver's n leaves, build its tree (d_nodes: optional output) */
+#define RS2_TREES_CACHED 1  /* d_nodes holds the trees already (required, read only): no hashing     */
+/* BUILD: a sliver with targets, and with a non-NULL d_nodes every sliver (a call whose counts are
+ * all zero warms the cache), is expanded, hashed and its tree built; a sliver with no target and
+ * no d_nodes does no work.  CACHED: d_nodes is never written, nothing is hashed, and the codec
+ * runs only for slivers with a repair target (>= k) -- the expanded sliver is not kept, recompute
+ * is the reference's own trade (slivers.rs:180-213); a call whose targets are all systematic
+ * launches no codec, its symbols are copies out of the slivers.
+ * Checked on the host before anything is enqueued (outputs untouched on failure):
+ * RS2_E_INVALID_ARGUMENT for a NULL v or needed buffer, trees not one of the two values, CACHED
+ * with a NULL d_nodes, a misaligned pointer, n_slivers > 65535, more than 2^31-1 requests, a
+ * target >= n_shards (RecoverySymbolError::IndexTooLarge).  n_slivers 0: RS2_OK, nothing
+ * enqueued.  The host arrays may be reused as soon as the call returns.  Stream conventions as
+ * the other verifier calls; the call never synchronizes and reads nothing back.  Slivers are
+ * taken in windows whose device scratch (leaves, repair symbols, node arrays the caller does not
+ * take) stays within the budget below, one sliver at least: scratch does not grow with
+ * n_slivers. */
+int rs2_verifier_recovery_symbols_multi_device_async(
+    rs2_verifier* v, uint32_t n_slivers, const void* d_slivers, const uint32_t* target_counts,
+    const uint16_t* target_sliver_index, int trees, void* d_nodes, void* d_symbols, void* d_proofs,
+    void* stream);
+/* Host form (blocking, BUILD, pooled verifier and pinned staging like rs2_recovery_symbols):
+ * slivers[i] of sliver_len[i] bytes; a NULL or wrong-length sliver ->
+ * RS2_E_INCORRECT_DATA_LENGTH.  symbols_out / proofs_out laid out as d_symbols / d_proofs. */
+int rs2_recovery_symbols_multi(uint16_t n_shards, uint16_t symbol_size, int axis,
+                               uint32_t n_slivers, const uint8_t* const* slivers,
+                               const uint64_t* sliver_len, const uint32_t* target_counts,
+                               const uint16_t* target_sliver_index, uint8_t* symbols_out,
+                               uint8_t* proofs_out);
+/* Window scratch of the bulk call, process-wide, for calls made afterwards.  Default 256 MiB; 0
+ * restores it.  No reference counterpart. */
+int rs2_set_recovery_symbols_budget(uint64_t bytes);
+/* Process-wide counters of the bulk calls, stats_out[5]: windows, slivers expanded (codec lines
+ * launched), trees built, trees taken from the caller's cache (slivers of CACHED calls with at
+ * least one target), requests served.  No reference counterpart. */
+int rs2_recovery_symbols_stats(uint64_t* stats_out);
+
 /* ---- sliver recovery in bulk ------------------------------------------------------------------
  * SliverData::recover_sliver_or_generate_inconsistency_proof (slivers.rs:341-379, called per
  * missing sliver from walrus-service's request_futures.rs:436-497) for many slivers of the

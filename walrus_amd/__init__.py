@@ -33,6 +33,8 @@ from .encoding import (  # noqa: F401
     VerificationError,
     VerifiedBlobMetadataWithId,
     compute_symbol_size,
+    recovery_symbols_stats,
+    set_recovery_symbols_budget,
     set_verify_batch_budget,
     sliver_merkle_roots,
     source_symbols_for_n_shards,
@@ -49,6 +51,7 @@ from .recovery import (  # noqa: F401
     recover_slivers_or_generate_inconsistency_proofs,
     recovery_symbol_for_sliver,
     recovery_symbols_for_requests,
+    recovery_symbols_for_targets,
     try_recover_sliver_from_decoding_symbols,
     verify_recovery_symbols,
 )

@@ -34,6 +34,7 @@ AXIS_SECONDARY = 1
 CHECK_SKIP, CHECK_DEFAULT, CHECK_STRICT = 0, 1, 2
 RS2_SLIVER_MISMATCH, RS2_SLIVER_MATCH, RS2_SLIVER_SKIPPED = 0, 1, 2
 RS2_BLOB_MISMATCH, RS2_BLOB_MATCH, RS2_BLOB_SKIPPED = 0, 1, 2
+RS2_TREES_BUILD, RS2_TREES_CACHED = 0, 1
 
 # (name, restype, argtypes) for every function declared in include/walrus_rs2.h
 _u8p = ctypes.POINTER(ctypes.c_uint8)
@@ -148,6 +149,16 @@ SIGNATURES = {
          _u64p, _u16p, _vp, _vp]),
     "rs2_verifier_recovery_symbols_device_async": (
         ctypes.c_int, [_vp, ctypes.c_uint32, _vp, _u16p, _vp, _vp, _vp, _vp]),
+    "rs2_verifier_recovery_symbols_multi_device_async": (
+        ctypes.c_int,
+        [_vp, ctypes.c_uint32, _vp, ctypes.POINTER(ctypes.c_uint32), _u16p, ctypes.c_int, _vp, _vp,
+         _vp, _vp]),
+    "rs2_recovery_symbols_multi": (
+        ctypes.c_int,
+        [ctypes.c_uint16, ctypes.c_uint16, ctypes.c_int, ctypes.c_uint32, ctypes.POINTER(_vp),
+         _u64p, ctypes.POINTER(ctypes.c_uint32), _u16p, _vp, _vp]),
+    "rs2_set_recovery_symbols_budget": (ctypes.c_int, [ctypes.c_uint64]),
+    "rs2_recovery_symbols_stats": (ctypes.c_int, [ctypes.POINTER(ctypes.c_uint64)]),
     "rs2_verifier_recover_slivers_device_async": (
         ctypes.c_int,
         [_vp, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32), _u16p, _vp, _vp, _vp, _vp, _vp,

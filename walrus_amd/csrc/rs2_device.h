@@ -181,4 +181,12 @@ struct CheckSlot {
 constexpr uint32_t kCheckSkipped = 0xFFFFFFFFu;
 static_assert(sizeof(CheckRow) == 16 && sizeof(CheckSlot) == 8, "check tables are packed");
 
+// Bulk recovery symbols (symbol_requests_kernel): where each level of a sliver's MerkleTree::nodes
+// array starts, in nodes -- a path has at most kSymbolLevels siblings for n <= 65535 leaves.  By
+// value in the launch arguments (wave-uniform, read once per wave).
+constexpr int kSymbolLevels = 16;
+struct SymbolLevels {
+  uint32_t base[kSymbolLevels];
+};
+
 }  // namespace rs2

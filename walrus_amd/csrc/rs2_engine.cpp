@@ -1440,6 +1440,7 @@ struct rs2_verifier {
   DecodeSlot rdec[2];
   int rdec_slot = 0;
   DevBuf verdict_in, window_roots, per_sliver, sym_digests;
+  DevBuf requests;  // bulk recovery symbols: a chunk of the request table (at most kRequestChunk)
   rs2_plan::Prof prof;  // opt-in stage profiler of the recovery call (rs2_verifier_profile_*)
   // recorded on the caller's stream after each *_device_async call: destroy waits on it before
   // its buffers go back to the arena as quiesced (they may be handed out again at once)
@@ -3779,6 +3780,94 @@ int decode_batch_host(rs2_plan* plan, int axis, uint32_t n_blobs, const uint64_t
   return RS2_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// recovery symbols in bulk: many source slivers, a list of targets per sliver
+// ---------------------------------------------------------------------------------------------
+constexpr uint64_t kSymbolsBudget = uint64_t(256) << 20;
+std::atomic<uint64_t> g_sym_budget{kSymbolsBudget};
+std::atomic<uint64_t> g_sym_windows{0}, g_sym_expanded{0}, g_sym_built{0}, g_sym_cached{0},
+    g_sym_requests{0};
+// requests of one gather launch: the device copy of the request table never holds more
+constexpr uint32_t kRequestChunk = 1u << 20;
+
+// The windows of a planned bulk call (plan_symbol_requests) on st, one after the other: per run
+// of slivers to expand, the codec into the window's repair scratch and with BUILD the leaf hashes
+// and trees (node arrays into d_nodes, or into scratch when the caller takes none); then the
+// window's requests in chunks, table upload and gather.  The scratch is sized by the largest
+// window and reused in stream order.  With CACHED d_nodes is only read.
+int symbol_request_windows(rs2_verifier* v, const SymbolRequestPlan& plan,
+                           const uint32_t* target_counts, int trees, const uint8_t* d_slivers,
+                           uint8_t* d_nodes, uint8_t* d_symbols, uint8_t* d_proofs,
+                           hipStream_t st) {
+  const int64_t n = v->n, K = v->k, s = v->s, nn = int64_t(plan.n_nodes), L = plan.path_len;
+  const bool build = trees == RS2_TREES_BUILD;
+  // a previous call on another stream still owns the scratch buffers (verifier_leaves)
+  if (v->done) HIP_TRY(hipStreamWaitEvent(st, v->done, 0));
+  size_t widest = 0;
+  bool codec = false, runs = false;
+  for (const SymbolWindow& w : plan.windows) {
+    widest = std::max<size_t>(widest, w.n_slivers);
+    codec |= w.needs_codec;
+    runs |= !w.runs.empty();
+  }
+  if (codec) HIP_TRY(v->repair.ensure(widest * size_t(n - K) * s));
+  if (build && runs) {
+    HIP_TRY(v->leaves.ensure(widest * size_t(n) * 32));
+    HIP_TRY(v->roots.ensure(widest * 32));
+    if (!d_nodes) HIP_TRY(v->nodes.ensure(widest * size_t(nn) * 32));
+  }
+  if (plan.total)
+    HIP_TRY(v->requests.ensure(size_t(std::min<uint64_t>(plan.total, kRequestChunk)) * 4));
+  SymbolLevels lv;
+  std::copy(plan.level_base, plan.level_base + kSymbolLevels, lv.base);
+  uint64_t expanded = 0, built = 0;
+  for (const SymbolWindow& w : plan.windows) {
+    const uint8_t* din = d_slivers + int64_t(w.first_sliver) * K * s;
+    uint8_t* nodes = d_nodes ? d_nodes + int64_t(w.first_sliver) * nn * 32 : v->nodes.as<uint8_t>();
+    for (const auto& run : w.runs) {
+      const int64_t first = run.first, cnt = run.second;
+      const uint8_t* rin = din + first * K * s;
+      uint8_t* rep = nullptr;
+      if (n > K) {
+        rep = v->repair.as<uint8_t>() + first * (n - K) * s;
+        RS2_TRY(plan_encode(uint32_t(K), uint32_t(n - K), int(s), rin, K * s,
+                            [&](uint32_t i) { return int64_t(i) * s; }, rep, (n - K) * s,
+                            [&](uint32_t j) { return int64_t(j) * s; }, INT64_MAX, v->job));
+        RS2_TRY(bind_job(v->ctx, v->job, v->mem, st));
+        HIP_TRY(launch_job(v->job, int(cnt), st));
+        expanded += uint64_t(cnt);
+      }
+      if (!build) continue;
+      uint8_t* leaves = v->leaves.as<uint8_t>() + first * n * 32;
+      SymbolMap map{rin, rep, nullptr, int(n), int(cnt), int(K), int(s)};
+      HIP_TRY(rs2k_launch_leaf_hash(map, 4, cnt * n, 1, leaves, st));
+      HIP_TRY(rs2k_launch_merkle_trees(leaves, int(n), int(cnt), 0, n * 32, 32, 0, 0,
+                                       v->roots.as<uint8_t>() + first * 32, 32, st,
+                                       nodes + first * nn * 32, nn * 32));
+      built += uint64_t(cnt);
+    }
+    for (uint32_t c0 = 0; c0 < w.n_requests; c0 += kRequestChunk) {
+      const uint32_t cn = std::min(kRequestChunk, w.n_requests - c0);
+      const int64_t r0 = int64_t(w.first_request) + c0;
+      // through the pinned slot ring: the caller's arrays and the plan's table may go at once
+      RS2_TRY(upload_pieces(v->ctx, v->requests.p, plan.table.data() + r0, size_t(cn) * 4, st));
+      HIP_TRY(rs2k_launch_symbol_requests(din, v->repair.as<uint8_t>(), int(n), int(K), int(s),
+                                          nodes, nn * 32, v->requests.as<uint32_t>(), cn, int(L),
+                                          lv, d_symbols + r0 * s, d_proofs + r0 * L * 32, st));
+    }
+  }
+  uint64_t served_trees = 0;
+  if (!build)
+    for (const SymbolWindow& w : plan.windows)
+      for (uint32_t i = 0; i < w.n_slivers; ++i) served_trees += target_counts[w.first_sliver + i] > 0;
+  g_sym_windows.fetch_add(plan.windows.size(), std::memory_order_relaxed);
+  g_sym_expanded.fetch_add(expanded, std::memory_order_relaxed);
+  g_sym_built.fetch_add(built, std::memory_order_relaxed);
+  g_sym_cached.fetch_add(served_trees, std::memory_order_relaxed);
+  g_sym_requests.fetch_add(plan.total, std::memory_order_relaxed);
+  return RS2_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -4134,6 +4223,103 @@ int rs2_recovery_symbols(uint16_t n_shards, uint16_t symbol_size, int axis, uint
   HIP_TRY(hipStreamSynchronize(v->stream));
   std::memcpy(symbols_out, ho, sym_b);
   if (L) std::memcpy(proofs_out, ho + sym_b, prf_b);
+  return RS2_OK;
+}
+
+int rs2_verifier_recovery_symbols_multi_device_async(
+    rs2_verifier* v, uint32_t n_slivers, const void* d_slivers, const uint32_t* target_counts,
+    const uint16_t* target_sliver_index, int trees, void* d_nodes, void* d_symbols, void* d_proofs,
+    void* stream) {
+  if (!v) return fail(RS2_E_INVALID_ARGUMENT, "null verifier");
+  if (trees != RS2_TREES_BUILD && trees != RS2_TREES_CACHED)
+    return fail(RS2_E_INVALID_ARGUMENT, "trees must be RS2_TREES_BUILD or RS2_TREES_CACHED");
+  if (n_slivers == 0) return RS2_OK;
+  if (!d_slivers || !target_counts) return fail(RS2_E_INVALID_ARGUMENT, "null argument");
+  RS2_TRY(check_symbol_ptr(d_slivers, "d_slivers"));
+  RS2_TRY(check_symbol_ptr(d_symbols, "d_symbols"));
+  RS2_TRY(check_digest_ptr(d_proofs, "d_proofs"));
+  RS2_TRY(check_digest_ptr(d_nodes, "d_nodes"));
+  // every argument checked and the whole call planned before anything is enqueued (a target is
+  // remote input on a node)
+  SymbolRequestPlan plan;
+  RS2_TRY(plan_symbol_requests(v->n, v->k, v->s, n_slivers, target_counts, target_sliver_index,
+                               trees, d_nodes != nullptr,
+                               g_sym_budget.load(std::memory_order_relaxed), plan));
+  if (plan.total && (!d_symbols || (plan.path_len && !d_proofs)))
+    return fail(RS2_E_INVALID_ARGUMENT, "null argument");
+  HIP_TRY(hipSetDevice(v->ctx->device));
+  hipStream_t st = abi_stream(stream, v->stream);
+  RS2_TRY(symbol_request_windows(v, plan, target_counts, trees,
+                                 reinterpret_cast<const uint8_t*>(d_slivers),
+                                 reinterpret_cast<uint8_t*>(d_nodes),
+                                 reinterpret_cast<uint8_t*>(d_symbols),
+                                 reinterpret_cast<uint8_t*>(d_proofs), st));
+  return verifier_mark_done(v, st);
+}
+
+int rs2_recovery_symbols_multi(uint16_t n_shards, uint16_t symbol_size, int axis,
+                               uint32_t n_slivers, const uint8_t* const* slivers,
+                               const uint64_t* sliver_len, const uint32_t* target_counts,
+                               const uint16_t* target_sliver_index, uint8_t* symbols_out,
+                               uint8_t* proofs_out) {
+  if (n_slivers == 0) return RS2_OK;
+  if (n_slivers > 65535) return fail(RS2_E_INVALID_ARGUMENT, "more than 65535 slivers in a call");
+  if (!slivers || !sliver_len || !target_counts) return fail(RS2_E_INVALID_ARGUMENT, "null argument");
+  VerifierLease lease;
+  RS2_TRY(lease.get(n_shards, symbol_size, axis));
+  rs2_verifier* v = lease.v;
+  const uint64_t len = uint64_t(v->k) * symbol_size;
+  for (uint32_t i = 0; i < n_slivers; ++i)
+    if (!slivers[i] || sliver_len[i] != len)
+      return fail(RS2_E_INCORRECT_DATA_LENGTH, "sliver length does not match the encoder");
+  uint64_t total = 0;
+  for (uint32_t i = 0; i < n_slivers; ++i) {
+    total += target_counts[i];
+    if (total > 0x7FFFFFFFu) return fail(RS2_E_INVALID_ARGUMENT, "too many requests in a call");
+  }
+  if (total && !target_sliver_index) return fail(RS2_E_INVALID_ARGUMENT, "null argument");
+  for (uint64_t j = 0; j < total; ++j)
+    if (target_sliver_index[j] >= n_shards)  // slivers.rs check_index -> IndexTooLarge
+      return fail(RS2_E_INVALID_ARGUMENT, "target index too large");
+  const size_t L = size_t(merkle_path_len(n_shards));
+  if (total && (!symbols_out || (L && !proofs_out)))
+    return fail(RS2_E_INVALID_ARGUMENT, "null argument");
+  if (total == 0) return RS2_OK;  // no trees to hand out: nothing to do
+  HIP_TRY(hipSetDevice(v->ctx->device));
+  const size_t in_b = size_t(n_slivers) * len, sym_b = size_t(total) * symbol_size;
+  const size_t prf_b = size_t(total) * L * 32;
+  HIP_TRY(v->input.ensure(in_b));
+  HIP_TRY(v->sym_out.ensure(sym_b));
+  HIP_TRY(v->proof_out.ensure(std::max<size_t>(prf_b, 32)));
+  HIP_TRY(v->h_in.ensure(in_b));
+  HIP_TRY(v->h_out.ensure(sym_b + prf_b));
+  for (uint32_t i = 0; i < n_slivers; ++i)
+    std::memcpy(static_cast<uint8_t*>(v->h_in.p) + size_t(i) * len, slivers[i], len);
+  HIP_TRY(hipMemcpyAsync(v->input.p, v->h_in.p, in_b, hipMemcpyHostToDevice, v->stream));
+  RS2_TRY(rs2_verifier_recovery_symbols_multi_device_async(
+      v, n_slivers, v->input.p, target_counts, target_sliver_index, RS2_TREES_BUILD, nullptr,
+      v->sym_out.p, v->proof_out.p, nullptr));
+  uint8_t* ho = static_cast<uint8_t*>(v->h_out.p);
+  HIP_TRY(hipMemcpyAsync(ho, v->sym_out.p, sym_b, hipMemcpyDeviceToHost, v->stream));
+  if (L) HIP_TRY(hipMemcpyAsync(ho + sym_b, v->proof_out.p, prf_b, hipMemcpyDeviceToHost, v->stream));
+  HIP_TRY(hipStreamSynchronize(v->stream));
+  std::memcpy(symbols_out, ho, sym_b);
+  if (L) std::memcpy(proofs_out, ho + sym_b, prf_b);
+  return RS2_OK;
+}
+
+int rs2_set_recovery_symbols_budget(uint64_t bytes) {
+  g_sym_budget.store(bytes ? bytes : kSymbolsBudget, std::memory_order_relaxed);
+  return RS2_OK;
+}
+
+int rs2_recovery_symbols_stats(uint64_t* stats_out) {
+  if (!stats_out) return fail(RS2_E_INVALID_ARGUMENT, "null argument");
+  stats_out[0] = g_sym_windows.load(std::memory_order_relaxed);
+  stats_out[1] = g_sym_expanded.load(std::memory_order_relaxed);
+  stats_out[2] = g_sym_built.load(std::memory_order_relaxed);
+  stats_out[3] = g_sym_cached.load(std::memory_order_relaxed);
+  stats_out[4] = g_sym_requests.load(std::memory_order_relaxed);
   return RS2_OK;
 }
 

@@ -964,6 +964,72 @@ __global__ void __launch_bounds__(64)
   }
 }
 
+// Bulk form of the above (rs2_verifier_recovery_symbols_multi_device_async), one window of slivers
+// at a time: request r of the window is requests[r] = slot << 16 | target, the sliver at `slot` of
+// the window (sys / rep / nodes all start at the window's first sliver) and the leaf it wants.
+// One wave per request, kRequestWaves requests per workgroup; r, slot and target are wave-uniform.
+//   symbol: s bytes from sys + (slot * k + t) * s (t < k) or rep + (slot * (n - k) + t - k) * s to
+//     sym_out + r * s.  Both ends are only 2-byte aligned, so the copy is as wide as their common
+//     alignment allows: with source and destination congruent mod 16 (mod 4) the middle goes as
+//     aligned 16-byte (4-byte) pieces, a piece per lane, and the up to W - 2 bytes on either side
+//     as 2-byte pieces; otherwise all of it as 2-byte pieces.  No byte outside the symbol is read
+//     or written.
+//   proof: sibling l of the path is node lv.base[l] + ((t >> l) ^ 1) of the slot's tree
+//     (merkle.rs:293-305); lanes 2l and 2l + 1 move its two 16-byte halves (nodes and proofs are
+//     16-byte aligned).  The level bases come with the launch; a lane picks its own by compares,
+//     not by indexing the argument (that would send it through scratch memory).
+// Every byte offset is 64-bit: r * s passes 2^32 long before the request count passes 2^31.
+constexpr int kRequestWaves = 4;
+__global__ void __launch_bounds__(64 * kRequestWaves)
+    symbol_requests_kernel(const uint8_t* __restrict__ sys, const uint8_t* __restrict__ rep, int n,
+                           int k, int s, const uint8_t* __restrict__ nodes, int64_t nodes_stride,
+                           const uint32_t* __restrict__ requests, int64_t count, int path_len,
+                           SymbolLevels lv, uint8_t* __restrict__ sym_out,
+                           uint8_t* __restrict__ proof_out) {
+  const int lane = threadIdx.x & 63;
+  const int64_t r = int64_t(blockIdx.x) * kRequestWaves + (threadIdx.x >> 6);
+  if (r >= count) return;
+  const uint32_t e = requests[r];
+  const int64_t slot = e >> 16;
+  const int t = int(e & 0xFFFFu);
+  const uint8_t* src = t < k ? sys + (slot * k + t) * s : rep + (slot * (n - k) + (t - k)) * s;
+  uint8_t* dst = sym_out + r * s;
+  const uintptr_t apart = reinterpret_cast<uintptr_t>(src) ^ reinterpret_cast<uintptr_t>(dst);
+  const int W = (apart & 15) == 0 ? 16 : (apart & 3) == 0 ? 4 : 2;
+  // [0, head) and [mid_end, s) in 2-byte pieces, [head, mid_end) in W-byte pieces aligned on both
+  // sides
+  const int to_aligned = int((W - (reinterpret_cast<uintptr_t>(dst) & uintptr_t(W - 1))) & (W - 1));
+  const int head = to_aligned < s ? to_aligned : s;
+  const int mid = (s - head) / W;
+  const int mid_end = head + mid * W;
+  const int edge = (head + (s - mid_end)) / 2;
+  for (int i = lane; i < edge; i += 64) {
+    const int o = 2 * i < head ? 2 * i : 2 * i - head + mid_end;
+    *reinterpret_cast<uint16_t*>(dst + o) = *reinterpret_cast<const uint16_t*>(src + o);
+  }
+  if (W == 16) {
+    for (int i = lane; i < mid; i += 64)
+      reinterpret_cast<uint4*>(dst + head)[i] = reinterpret_cast<const uint4*>(src + head)[i];
+  } else if (W == 4) {
+    for (int i = lane; i < mid; i += 64)
+      reinterpret_cast<uint32_t*>(dst + head)[i] = reinterpret_cast<const uint32_t*>(src + head)[i];
+  } else {
+    for (int i = lane; i < mid; i += 64)
+      reinterpret_cast<uint16_t*>(dst + head)[i] = reinterpret_cast<const uint16_t*>(src + head)[i];
+  }
+  if (lane < 2 * path_len) {
+    const int l = lane >> 1;
+    uint32_t base = 0;
+    sfor<kSymbolLevels>([&](auto jj) {
+      constexpr int j = decltype(jj)::value;
+      base = l == j ? lv.base[j] : base;
+    });
+    const int64_t sib = int64_t(base) + ((t >> l) ^ 1);
+    const uint4* tn = reinterpret_cast<const uint4*>(nodes + slot * nodes_stride + sib * 32);
+    reinterpret_cast<uint4*>(proof_out + (r * path_len + l) * 32)[lane & 1] = tn[lane & 1];
+  }
+}
+
 // MerkleProof::compute_root (merkle.rs:150-169) for `count` proofs: start from leaf digest r,
 // climb path r (path_len nodes) by leaf_index[r]'s bits: inner(cur, sib) when the level index
 // is even, inner(sib, cur) when odd.  One lane per proof.
@@ -1351,6 +1417,22 @@ hipError_t rs2k_launch_proof_gather(const uint8_t* d_sys, const uint8_t* d_rep, 
   if (count <= 0) return hipSuccess;
   hipLaunchKernelGGL(rs2::proof_gather_kernel, dim3(unsigned(count)), dim3(64), 0, stream, d_sys,
                      d_rep, n, k, s, d_nodes, nodes_stride, d_targets, path_len, d_sym, d_proof);
+  return hipGetLastError();
+}
+
+hipError_t rs2k_launch_symbol_requests(const uint8_t* d_sys, const uint8_t* d_rep, int n, int k,
+                                       int s, const uint8_t* d_nodes, int64_t nodes_stride,
+                                       const uint32_t* d_requests, int64_t count, int path_len,
+                                       rs2::SymbolLevels levels, uint8_t* d_sym, uint8_t* d_proof,
+                                       hipStream_t stream) {
+  if (count <= 0) return hipSuccess;
+  if (count > 0x7FFFFFFF || path_len < 0 || path_len > rs2::kSymbolLevels || s < 2 || s % 2 ||
+      k < 1 || k > n)
+    return hipErrorInvalidValue;
+  const int64_t wgs = (count + rs2::kRequestWaves - 1) / rs2::kRequestWaves;
+  hipLaunchKernelGGL(rs2::symbol_requests_kernel, dim3(unsigned(wgs)),
+                     dim3(64 * rs2::kRequestWaves), 0, stream, d_sys, d_rep, n, k, s, d_nodes,
+                     nodes_stride, d_requests, count, path_len, levels, d_sym, d_proof);
   return hipGetLastError();
 }
 

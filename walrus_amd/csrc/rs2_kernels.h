@@ -55,6 +55,13 @@ hipError_t rs2k_launch_proof_gather(const uint8_t* d_sys, const uint8_t* d_rep, 
                                     int s, const uint8_t* d_nodes, int64_t nodes_stride,
                                     const uint16_t* d_targets, int count, int path_len,
                                     uint8_t* d_sym, uint8_t* d_proof, hipStream_t stream);
+// one window of a bulk recovery-symbol call: d_sys / d_rep / d_nodes at the window's first sliver,
+// d_requests its `count` entries (slot << 16 | target), d_sym / d_proof at its first request
+hipError_t rs2k_launch_symbol_requests(const uint8_t* d_sys, const uint8_t* d_rep, int n, int k,
+                                       int s, const uint8_t* d_nodes, int64_t nodes_stride,
+                                       const uint32_t* d_requests, int64_t count, int path_len,
+                                       rs2::SymbolLevels levels, uint8_t* d_sym, uint8_t* d_proof,
+                                       hipStream_t stream);
 hipError_t rs2k_launch_proof_roots(const uint8_t* d_leaf_digests, const uint32_t* d_leaf_index,
                                    const uint8_t* d_paths, int path_len, int count,
                                    uint8_t* d_roots, hipStream_t stream);

@@ -669,4 +669,74 @@ void verify_windows(const std::vector<uint64_t>& need, uint64_t budget, size_t m
   if (held) ends.push_back(uint32_t(need.size()));
 }
 
+int merkle_level_bases(uint32_t n, uint32_t* level_base, uint64_t* n_nodes) {
+  uint64_t cnt = n, base = 0;
+  int l = 0;
+  while (cnt > 1) {
+    if (l < kSymbolLevels) level_base[l] = uint32_t(base);
+    cnt += cnt & 1;
+    base += cnt;
+    cnt /= 2;
+    ++l;
+  }
+  for (int j = l; j < kSymbolLevels; ++j) level_base[j] = uint32_t(base);
+  if (n_nodes) *n_nodes = base + cnt;
+  return l;
+}
+
+int plan_symbol_requests(uint32_t n, uint32_t k, uint32_t s, uint32_t n_slivers,
+                         const uint32_t* target_counts, const uint16_t* targets, int trees,
+                         bool have_nodes, uint64_t budget, SymbolRequestPlan& plan) {
+  plan = SymbolRequestPlan{};
+  if (trees != RS2_TREES_BUILD && trees != RS2_TREES_CACHED)
+    return fail(RS2_E_INVALID_ARGUMENT, "trees must be RS2_TREES_BUILD or RS2_TREES_CACHED");
+  const bool build = trees == RS2_TREES_BUILD;
+  if (!build && !have_nodes)
+    return fail(RS2_E_INVALID_ARGUMENT, "RS2_TREES_CACHED needs the trees in d_nodes");
+  if (n_slivers > 65535) return fail(RS2_E_INVALID_ARGUMENT, "more than 65535 slivers in a call");
+  if (n == 0 || n > 65535 || k == 0 || k > n)
+    return fail(RS2_E_INVALID_ARGUMENT, "not a sliver's code");
+  if (n_slivers && !target_counts) return fail(RS2_E_INVALID_ARGUMENT, "null argument");
+  uint64_t total = 0;
+  for (uint32_t i = 0; i < n_slivers; ++i) {
+    total += target_counts[i];
+    if (total > 0x7FFFFFFFu) return fail(RS2_E_INVALID_ARGUMENT, "too many requests in a call");
+  }
+  if (total && !targets) return fail(RS2_E_INVALID_ARGUMENT, "null argument");
+  for (uint64_t j = 0; j < total; ++j)
+    if (targets[j] >= n)  // slivers.rs check_index -> RecoverySymbolError::IndexTooLarge
+      return fail(RS2_E_INVALID_ARGUMENT, "target index too large");
+  plan.total = total;
+  plan.path_len = merkle_level_bases(n, plan.level_base, &plan.n_nodes);
+  plan.per_sliver = uint64_t(n - k) * s;
+  if (build) plan.per_sliver += uint64_t(n) * 32 + (have_nodes ? 0 : plan.n_nodes * 32);
+  const uint64_t fit = plan.per_sliver ? budget / plan.per_sliver : 65535;
+  const uint32_t per_window = uint32_t(std::min<uint64_t>(std::max<uint64_t>(fit, 1), 65535));
+  plan.table.resize(size_t(total));
+  uint64_t req = 0;
+  for (uint32_t first = 0; first < n_slivers; first += per_window) {
+    SymbolWindow w;
+    w.first_sliver = first;
+    w.n_slivers = std::min(per_window, n_slivers - first);
+    w.first_request = req;
+    for (uint32_t slot = 0; slot < w.n_slivers; ++slot) {
+      const uint32_t cnt = target_counts[first + slot];
+      bool expand = build && (have_nodes || cnt > 0);
+      for (uint32_t q = 0; q < cnt; ++q, ++req) {
+        plan.table[size_t(req)] = slot << 16 | targets[req];
+        expand |= targets[req] >= k;
+      }
+      if (!expand) continue;
+      if (!w.runs.empty() && w.runs.back().first + w.runs.back().second == slot)
+        ++w.runs.back().second;
+      else
+        w.runs.emplace_back(slot, 1u);
+    }
+    w.n_requests = uint32_t(req - w.first_request);
+    w.needs_codec = !w.runs.empty() && n > k;
+    plan.windows.push_back(std::move(w));
+  }
+  return RS2_OK;
+}
+
 }  // namespace rs2

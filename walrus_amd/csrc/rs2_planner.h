@@ -333,4 +333,51 @@ void verify_rows(uint32_t kp, uint32_t ks, uint32_t s, int axis, const uint16_t*
 void verify_windows(const std::vector<uint64_t>& need, uint64_t budget, size_t max_blobs,
                     std::vector<uint32_t>& ends);
 
+// ---------------------------------------------------------------------------------------------
+// recovery symbols in bulk (rs2_verifier_recovery_symbols_multi_device_async): a list of targets
+// per source sliver, the slivers taken in windows of bounded scratch
+// ---------------------------------------------------------------------------------------------
+// Level l of a MerkleTree over n leaves starts at node level_base[l] of MerkleTree::nodes
+// (merkle.rs:216-266: levels from the leaves, each but the root padded to even with the zero
+// node).  Returns the path length (merkle.rs path_length; at most 16 for n <= 65535); level_base
+// has kSymbolLevels entries, those from the path length on hold the root's index.  n_nodes (may be
+// null) receives the node count.
+int merkle_level_bases(uint32_t n, uint32_t* level_base, uint64_t* n_nodes);
+
+// One window of a bulk recovery-symbol call: slivers first_sliver .. + n_slivers (its slots
+// 0 .. n_slivers) and their requests first_request .. + n_requests of the concatenated list.
+// runs: the slots whose slivers are expanded, as maximal (first slot, count) runs in order --
+// BUILD: every sliver with a request, and every sliver when the trees go to the caller (warming);
+// CACHED: the slivers with a repair target (>= k).  BUILD also hashes the leaves of those runs and
+// builds their trees.
+struct SymbolWindow {
+  uint32_t first_sliver = 0, n_slivers = 0;
+  uint64_t first_request = 0;
+  uint32_t n_requests = 0;
+  bool needs_codec = false;  // some run launches the codec (runs not empty and n > k)
+  std::vector<std::pair<uint32_t, uint32_t>> runs;
+};
+
+struct SymbolRequestPlan {
+  std::vector<SymbolWindow> windows;
+  std::vector<uint32_t> table;       // per request: slot in its window << 16 | target
+  uint32_t level_base[kSymbolLevels] = {};
+  int path_len = 0;
+  uint64_t n_nodes = 0;
+  uint64_t total = 0;                // requests of the call
+  uint64_t per_sliver = 0;           // scratch bytes a sliver of a window holds
+};
+
+// Validate and plan a bulk call over slivers of k symbols of s bytes expanded to n: the refusals
+// of include/walrus_rs2.h that need no pointer (trees not one of the two modes, CACHED without
+// nodes, more than 65535 slivers, more than 2^31-1 requests summed in 64 bits, a target >= n:
+// RS2_E_INVALID_ARGUMENT, as are null arrays), then the windows.  A sliver's scratch is
+// (n - k) * s of repair symbols, with BUILD n * 32 of leaves and, when the trees stay inside
+// (have_nodes false), n_nodes * 32; a window takes budget / that many slivers, at least one and at
+// most 65535 (the slot is 16 bits of a table entry), so every window but the last has the same
+// count.  targets may be null when every count is zero.
+int plan_symbol_requests(uint32_t n, uint32_t k, uint32_t s, uint32_t n_slivers,
+                         const uint32_t* target_counts, const uint16_t* targets, int trees,
+                         bool have_nodes, uint64_t budget, SymbolRequestPlan& plan);
+
 }  // namespace rs2

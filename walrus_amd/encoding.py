@@ -845,6 +845,25 @@ class SliverVerifier:
             self.handle, count, d_slivers, tg, d_symbols, d_proofs, d_nodes or None,
             _stream(stream)))
 
+    def recovery_symbols_multi_async(self, d_slivers: int,
+                                     targets_per_sliver: Sequence[Sequence[int]],
+                                     d_symbols: int, d_proofs: int, d_nodes: int = 0,
+                                     trees: str = "build", stream: Optional[int] = None) -> int:
+        """rs2_verifier_recovery_symbols_multi_device_async (returns the status code): source
+        sliver i (back to back in d_slivers) serves targets_per_sliver[i] (orthogonal-axis
+        indices); request j of the concatenated lists gets its symbol at d_symbols + j*s and its
+        Merkle path at d_proofs + j*path_len*32.  trees "build": every sliver is expanded and
+        hashed once and its tree built (into d_nodes when given, which also warms slivers
+        without targets); "cached": the trees are read from d_nodes and nothing is hashed."""
+        m = len(targets_per_sliver)
+        counts = (ctypes.c_uint32 * max(m, 1))(*[len(x) for x in targets_per_sliver])
+        flat = [t for x in targets_per_sliver for t in x]
+        tg = (ctypes.c_uint16 * max(len(flat), 1))(*flat)
+        mode = {"build": _lib.RS2_TREES_BUILD, "cached": _lib.RS2_TREES_CACHED}.get(trees, trees)
+        return _lib.lib().rs2_verifier_recovery_symbols_multi_device_async(
+            self.handle, m, d_slivers or None, counts, tg, mode, d_nodes or None,
+            d_symbols or None, d_proofs or None, _stream(stream))
+
     def recover_slivers_async(self, index_lists: Sequence[Sequence[int]], d_symbols: int,
                               d_slivers_out: int, expected_roots: Optional[bytes] = None,
                               d_roots: int = 0, d_verdict: int = 0,
@@ -948,6 +967,21 @@ def recover_stats() -> Dict[str, int]:
     out = (ctypes.c_uint64 * 3)()
     _ok(_lib.lib().rs2_recover_stats(out))
     return dict(zip(("launches", "batched", "single"), (int(v) for v in out)))
+
+
+def recovery_symbols_stats() -> Dict[str, int]:
+    """rs2_recovery_symbols_stats: windows of the bulk recovery-symbol calls, slivers expanded,
+    trees built, trees taken from the caller's cache, requests served (process-wide)."""
+    out = (ctypes.c_uint64 * 5)()
+    _ok(_lib.lib().rs2_recovery_symbols_stats(out))
+    return dict(zip(("windows", "expanded", "built", "cached", "requests"),
+                    (int(v) for v in out)))
+
+
+def set_recovery_symbols_budget(nbytes: int = 0) -> None:
+    """rs2_set_recovery_symbols_budget: device scratch a window of a bulk recovery-symbol call
+    may hold (0 restores the 256 MiB default)."""
+    _ok(_lib.lib().rs2_set_recovery_symbols_budget(int(nbytes)))
 
 
 def device_memory_trim(device: int = 0) -> int:

@@ -11,6 +11,8 @@ Host-side mirror of the walrus-core types over the device engine (include/walrus
   try_recover_sliver_from_decoding_symbols           encoding/slivers.rs:303-327
   recovery_symbols_for_requests  the storage node's recovery-symbol service, batched
                                  (walrus-service/src/node/recovery_symbol_service.rs:161-235)
+  recovery_symbols_for_targets   the same service with a list of targets per source sliver:
+                                 each sliver expanded and hashed once (:132-159)
 
 Every expansion, tree and proof root runs on the GPU (rs2_recovery_symbols,
 rs2_merkle_proof_roots); only index bookkeeping is done here.
@@ -230,6 +232,50 @@ def recovery_symbols_for_requests(config, slivers: Sequence[SliverData],
             out[i] = RecoverySymbol(orth, slivers[i].index, sb[k * s:(k + 1) * s],
                                     MerkleProof(path))
     return out  # type: ignore[return-value]
+
+
+def recovery_symbols_for_targets(config, slivers: Sequence[SliverData],
+                                 targets_per_sliver: Sequence[Sequence[int]]
+                                 ) -> List[List[RecoverySymbol]]:
+    """recovery_symbol_for_sliver (slivers.rs:180-213) for a list of target pair indices per
+    source sliver, as the node's recovery-symbol service is asked (one source sliver, many
+    targets: recovery_symbol_service.rs:132-235): one device call per (axis, symbol size) group
+    expands and hashes every source sliver once, builds its tree once and gathers every target's
+    symbol and sibling path (rs2_recovery_symbols_multi).  Returns one list per sliver, in the
+    order of its targets; types and index conventions as recovery_symbols_for_requests."""
+    n = config.n_shards
+    L = path_length(n)
+    out: List[List[RecoverySymbol]] = [[] for _ in slivers]
+    groups = {}
+    for i, (sl, tps) in enumerate(zip(slivers, targets_per_sliver)):
+        if any(tp >= n for tp in tps):
+            raise RecoverySymbolError("IndexTooLarge")
+        groups.setdefault((sl.axis, sl.symbol_size), []).append(i)
+    for (axis, s), members in groups.items():
+        orth = _ORTHOGONAL[axis]
+        m = len(members)
+        keep = [np.frombuffer(slivers[i].symbols.data, dtype=np.uint8) for i in members]
+        ptrs = (ctypes.c_void_p * m)(*[a.ctypes.data for a in keep])
+        lens = (ctypes.c_uint64 * m)(*[len(a) for a in keep])
+        counts = (ctypes.c_uint32 * m)(*[len(targets_per_sliver[i]) for i in members])
+        tgt = [tp if orth == PRIMARY else n - 1 - tp
+               for i in members for tp in targets_per_sliver[i]]
+        total = len(tgt)
+        ta = (ctypes.c_uint16 * max(total, 1))(*tgt)
+        syms = np.zeros(max(total * s, 1), dtype=np.uint8)
+        proofs = np.zeros(max(total * L * 32, 1), dtype=np.uint8)
+        _ok(_lib.lib().rs2_recovery_symbols_multi(n, s, _AXIS[axis], m, ptrs, lens, counts, ta,
+                                                  syms.ctypes.data, proofs.ctypes.data),
+            expected=len(keep[0]))
+        sb, pb = syms.tobytes(), proofs.tobytes()
+        j = 0
+        for i in members:
+            for _ in targets_per_sliver[i]:
+                path = [pb[(j * L + l) * 32:(j * L + l + 1) * 32] for l in range(L)]
+                out[i].append(RecoverySymbol(orth, slivers[i].index, sb[j * s:(j + 1) * s],
+                                             MerkleProof(path)))
+                j += 1
+    return out
 
 
 def recovery_symbol_for_sliver(sliver: SliverData, target_pair_index: int,
