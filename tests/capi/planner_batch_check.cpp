@@ -5,7 +5,8 @@
 // re-strided mixing tables with the planned job.  One line per case; a breach exits non-zero.
 // With a file argument (lines `k n limit s q0 q1 ...`, the k present shards of an n-shard code)
 // the cases are the file's patterns instead of the built-in ones, through the same checks, and
-// each line also reports how many output blocks the planner paired.
+// each line also reports how many output blocks the planner paired.  With `--chunks` it checks
+// the chunk cut rule (cut_batch_chunks) on a fixed list of small windows instead.
 #include "../../walrus_amd/csrc/rs2_planner.h"
 
 #include <cstdio>
@@ -244,9 +245,87 @@ int run_file(const char* path) {
   return 0;
 }
 
+// The chunk cut rule (cut_batch_chunks) on one window: prints `label chunks=a,b|c demoted=d`
+// (job indices; "-" for none) after the properties any cut satisfies.
+void check_cut(const char* label, const std::vector<ChunkJob>& jobs, size_t budget) {
+  ChunkCut cut;
+  cut.members.assign(3, 99);  // stale contents must not survive
+  cut.ends.assign(2, 99);
+  cut.demoted.assign(1, 99);
+  cut_batch_chunks(jobs, budget, cut);
+  // every eligible job is in exactly one chunk or demoted, never both; no other job is in either
+  std::vector<int> in_chunk(jobs.size(), 0), is_demoted(jobs.size(), 0);
+  for (uint32_t m : cut.members) {
+    CHECK(m < jobs.size());
+    ++in_chunk[m];
+  }
+  for (uint32_t d : cut.demoted) {
+    CHECK(d < jobs.size());
+    ++is_demoted[d];
+  }
+  for (size_t i = 0; i < jobs.size(); ++i)
+    CHECK(in_chunk[i] + is_demoted[i] == (jobs[i].eligible ? 1 : 0));
+  // the ranges are half-open, in order, non-empty and cover the members
+  CHECK(cut.ends.empty() ? cut.members.empty() : cut.ends.back() == cut.members.size());
+  for (size_t i = 1; i < cut.members.size(); ++i) CHECK(cut.members[i - 1] < cut.members[i]);
+  for (size_t i = 1; i < cut.demoted.size(); ++i) CHECK(cut.demoted[i - 1] < cut.demoted[i]);
+  size_t at = 0;
+  for (uint32_t end : cut.ends) {
+    CHECK(end > at);
+    // one geometry per chunk; within the budget unless the chunk is a single job
+    size_t bytes = 0;
+    for (size_t m = at; m < end; ++m) {
+      const ChunkJob& j = jobs[cut.members[m]];
+      CHECK(j.C == jobs[cut.members[at]].C && j.pairs_span == jobs[cut.members[at]].pairs_span);
+      bytes += j.n_logs * kTabU16 * 2;
+    }
+    CHECK(end - at == 1 || bytes <= budget);
+    at = end;
+  }
+  std::printf("%s chunks=", label);
+  at = 0;
+  for (size_t c = 0; c < cut.ends.size(); at = cut.ends[c++]) {
+    if (c) std::printf("|");
+    for (size_t m = at; m < cut.ends[c]; ++m)
+      std::printf("%s%u", m > at ? "," : "", unsigned(cut.members[m]));
+  }
+  if (cut.ends.empty()) std::printf("-");
+  std::printf(" demoted=");
+  for (size_t i = 0; i < cut.demoted.size(); ++i)
+    std::printf("%s%u", i ? "," : "", unsigned(cut.demoted[i]));
+  if (cut.demoted.empty()) std::printf("-");
+  std::printf("\n");
+  ++g_cases;
+}
+
+// The smallest windows at which the cut can go wrong.  A job of 3 logs has 3 * 256 = 768 table
+// bytes, so a budget of 1600 fits two of them and 2400 fits three.
+void run_cuts() {
+  const ChunkJob a{true, 64, 10, 3}, off{false, 64, 10, 3};
+  const ChunkJob other_c{true, 128, 10, 3}, other_span{true, 64, 12, 3}, big{true, 64, 10, 7};
+  check_cut("empty", {}, 1600);
+  check_cut("none_eligible", {off, off}, 1600);
+  check_cut("three_fit", {a, a, a}, 2400);
+  check_cut("three_exact", {a, a, a}, 2304);
+  check_cut("two_fit", {a, a, a}, 1600);
+  check_cut("one_above_budget", {big}, 1600);
+  check_cut("above_budget_between", {a, big, a}, 1600);
+  check_cut("other_c_between", {a, other_c, a}, 2400);
+  check_cut("other_span_between", {a, other_span, a}, 2400);
+  check_cut("ineligible_first", {off, other_c, a, other_c}, 2400);
+  check_cut("demoted_does_not_count", {a, other_c, a, a}, 1600);
+  check_cut("geometry_of_each_chunk", {a, a, a, other_c}, 1600);
+  check_cut("zero_budget", {a, a}, 0);
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
+  if (argc > 1 && std::strcmp(argv[1], "--chunks") == 0) {
+    run_cuts();
+    std::fprintf(stderr, "planner_batch_check: %d cuts\n", g_cases);
+    return 0;
+  }
   if (argc > 1) {
     const int rc = run_file(argv[1]);
     std::fprintf(stderr, "planner_batch_check: %d cases\n", g_cases);

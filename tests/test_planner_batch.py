@@ -89,6 +89,39 @@ def test_built_in_cases_unchanged(programs):
     assert hashlib.sha256(run.stdout).hexdigest() == BUILT_IN_OUTPUT
 
 
+def test_chunk_cut_rule(programs):
+    """cut_batch_chunks, the rule that packs a window's eligible jobs into launches, on the
+    smallest windows at which it can go wrong (`--chunks`; jobs of 3 logs = 768 table bytes, one of
+    7 logs = 1792).  The program checks for each that every eligible job is in exactly one chunk or
+    demoted and no other job in either, that a chunk has one geometry and stays within the budget
+    unless it is a single job; the expected cuts below are what the loop this rule replaced (in
+    decode_batch_items and recover_items) gives: demotion against the chunk's first job, the cut
+    before the job that would pass the budget, a demoted job's tables not counted."""
+    expected = {
+        "empty": ("-", "-"),
+        "none_eligible": ("-", "-"),
+        "three_fit": ("0,1,2", "-"),
+        "three_exact": ("0,1,2", "-"),             # the budget itself is not past the budget
+        "two_fit": ("0,1|2", "-"),                 # the cut falls before the job that overflows
+        "one_above_budget": ("0", "-"),            # still a chunk of its own
+        "above_budget_between": ("0|1|2", "-"),
+        "other_c_between": ("0,2", "1"),           # demoted; its neighbours share one chunk
+        "other_span_between": ("0,2", "1"),
+        "ineligible_first": ("1,3", "2"),          # the first eligible job defines the geometry
+        "demoted_does_not_count": ("0,2|3", "1"),
+        "geometry_of_each_chunk": ("0,1|2", "3"),  # compared with the open chunk's first job
+        "zero_budget": ("0|1", "-"),
+    }
+    lines = _run(programs[0], "--chunks")
+    got = {}
+    for ln in lines:
+        m = re.fullmatch(r"(\w+) chunks=(\S+) demoted=(\S+)", ln)
+        assert m, ln
+        got[m.group(1)] = (m.group(2), m.group(3))
+    assert got == expected
+    assert _run(programs[1], "--chunks") == lines   # the same under the host sanitizers
+
+
 def test_families_of_the_batch_geometries(programs, tmp_path):
     """Every family pattern of every BATCH_GEOMETRIES entry (s = 6) through the program's file
     form, plain and under the host sanitizers: the planner's n_in, n_out and eligibility equal

@@ -23,6 +23,7 @@
 #include <deque>
 #include <functional>
 #include <mutex>
+#include <numeric>
 #include <string>
 #include <thread>
 #include <vector>
@@ -340,6 +341,28 @@ struct PinnedBuf {
   }
 };
 
+// A timing-disabled event, created on first use.  Unset it orders nothing: wait_on and sync
+// return at once.  Destroying it waits for nothing.
+struct Event {
+  hipEvent_t ev = nullptr;
+  Event() = default;
+  Event(const Event&) = delete;
+  Event& operator=(const Event&) = delete;
+  ~Event() {
+    if (ev) (void)hipEventDestroy(ev);
+  }
+  bool set() const { return ev != nullptr; }
+  hipError_t record(hipStream_t st) {
+    if (!ev) {
+      const hipError_t e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+      if (e != hipSuccess) return e;
+    }
+    return hipEventRecord(ev, st);
+  }
+  hipError_t wait_on(hipStream_t st) const { return ev ? hipStreamWaitEvent(st, ev, 0) : hipSuccess; }
+  hipError_t sync() const { return ev ? hipEventSynchronize(ev) : hipSuccess; }
+};
+
 // Host worker threads for the pinned staging of the host-buffer ABI: copies between the
 // caller's pageable buffers and pinned slots run on several cores while the DMA engine moves
 // the previous slot (one core's memcpy would cap the path at ~10 GB/s).  Shared by every plan
@@ -459,6 +482,19 @@ void par_copy(HostPool& pool, const std::vector<Seg>& segs, bool to_host) {
       }
     });
   }
+  pool.run(tasks);
+}
+
+// fn(i) for every i < cnt, strided over the pool's threads
+template <class F>
+void pool_for_each(HostPool& pool, size_t cnt, F fn) {
+  if (!cnt) return;
+  const size_t T = std::min<size_t>(size_t(pool.threads()), cnt);
+  std::vector<std::function<void()>> tasks;
+  for (size_t t = 0; t < T; ++t)
+    tasks.emplace_back([&fn, t, T, cnt] {
+      for (size_t i = t; i < cnt; i += T) fn(i);
+    });
   pool.run(tasks);
 }
 
@@ -1009,18 +1045,12 @@ struct DecodeSlot {
   // and the host vectors they are uploaded from, alive until `done`
   DevBuf copy_src, copy_dst;
   std::vector<int64_t> copy_src_h, copy_dst_h;
-  hipEvent_t done = nullptr;
+  Event done;
   // the erasure pattern / buffers the slot's job was planned for: a repeat decode with the same
   // key reuses the slot's tables and offsets on the device instead of re-planning (empty: the
   // slot is never reused that way)
   std::vector<int64_t> key;
   bool fused = false;  // the job writes the present originals from its own loads
-  DecodeSlot() = default;
-  DecodeSlot(const DecodeSlot&) = delete;
-  DecodeSlot& operator=(const DecodeSlot&) = delete;
-  ~DecodeSlot() {
-    if (done) (void)hipEventDestroy(done);
-  }
 };
 
 // One chunk of a decode batch: the concatenated position (and copy) offsets, multiplier logs,
@@ -1028,13 +1058,7 @@ struct DecodeSlot {
 // in turn; a slot is rewritten only after `done`, the event of its last launch.
 struct BatchDecodeSlot {
   DevBuf offs, logs, tabs, mix, jobs;
-  hipEvent_t done = nullptr;
-  BatchDecodeSlot() = default;
-  BatchDecodeSlot(const BatchDecodeSlot&) = delete;
-  BatchDecodeSlot& operator=(const BatchDecodeSlot&) = delete;
-  ~BatchDecodeSlot() {
-    if (done) (void)hipEventDestroy(done);
-  }
+  Event done;
 };
 // Jobs of one chunk: what fits one upload slot; and the per-position tables of one chunk
 // (256 bytes per multiplier log), so the device memory of a call does not grow with n_blobs.
@@ -1059,6 +1083,13 @@ size_t tree_scratch_bytes(int64_t trees, int64_t n) {
   int L = 1;
   while (((n + (int64_t(1) << L) - 1) >> L) > kMerkleMaxLeaves) ++L;
   return size_t(trees) * size_t((n + (int64_t(1) << L) - 1) >> L) * 32;
+}
+
+// digests (32 B each, at d_out) of `count` symbols of s bytes back to back at d_symbols
+inline hipError_t hash_symbols(const void* d_symbols, int64_t count, int s, void* d_out,
+                               hipStream_t st) {
+  SymbolMap map{reinterpret_cast<const uint8_t*>(d_symbols), nullptr, nullptr, 0, 0, 0, s};
+  return rs2k_launch_leaf_hash(map, 1, count, 1, reinterpret_cast<uint8_t*>(d_out), st);
 }
 
 // Root of n leaf digests (32 B each, contiguous) by one level launch per tree level
@@ -1092,20 +1123,8 @@ struct Stager {
   static constexpr int kSlots = 4;
   size_t slot_bytes = size_t(32) << 20;
   PinnedBuf ring;
-  hipEvent_t ev[kSlots] = {};
-  Stager() = default;
-  Stager(const Stager&) = delete;
-  Stager& operator=(const Stager&) = delete;
-  ~Stager() {
-    for (auto& e : ev)
-      if (e) (void)hipEventDestroy(e);
-  }
-  int init() {
-    if (ring.p) return RS2_OK;
-    HIP_TRY(ring.ensure(slot_bytes * kSlots));
-    for (auto& e : ev) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    return RS2_OK;
-  }
+  Event ev[kSlots];  // each slot's last DMA
+  int init() { HIP_TRY(ring.ensure(slot_bytes * kSlots)); return RS2_OK; }
   uint8_t* slot(int k) { return static_cast<uint8_t*>(ring.p) + size_t(k % kSlots) * slot_bytes; }
 };
 
@@ -1276,10 +1295,10 @@ int stage_h2d(Context* ctx, Stager& sg, const std::vector<Seg>& segs_all, hipStr
   const std::vector<Piece> pcs = cut_pieces(segs, sg.slot_bytes);
   for (size_t k = 0; k < pcs.size(); ++k) {
     const int sl = int(k % Stager::kSlots);
-    HIP_TRY(hipEventSynchronize(sg.ev[sl]));
+    HIP_TRY(sg.ev[sl].sync());
     par_copy(ctx->pool, slot_view(pcs[k], sg.slot(sl)), false);
     HIP_TRY(piece_dma(pcs[k], sg.slot(sl), false, st));
-    HIP_TRY(hipEventRecord(sg.ev[sl], st));
+    HIP_TRY(sg.ev[sl].record(st));
   }
   return RS2_OK;
 }
@@ -1298,21 +1317,37 @@ int stage_d2h(Context* ctx, Stager& sg, const std::vector<Seg>& segs_all, hipStr
   const std::vector<Piece> pcs = cut_pieces(segs, sg.slot_bytes);
   auto issue = [&](size_t k) -> int {
     const int sl = int(k % Stager::kSlots);
-    HIP_TRY(hipEventSynchronize(sg.ev[sl]));
+    HIP_TRY(sg.ev[sl].sync());
     HIP_TRY(piece_dma(pcs[k], sg.slot(sl), true, st));
-    HIP_TRY(hipEventRecord(sg.ev[sl], st));
+    HIP_TRY(sg.ev[sl].record(st));
     return RS2_OK;
   };
   for (size_t k = 0; k < pcs.size() && k < size_t(Stager::kSlots); ++k)
     RS2_TRY(issue(k));
   for (size_t k = 0; k < pcs.size(); ++k) {
     const int sl = int(k % Stager::kSlots);
-    HIP_TRY(hipEventSynchronize(sg.ev[sl]));
+    HIP_TRY(sg.ev[sl].sync());
     par_copy(ctx->pool, slot_view(pcs[k], sg.slot(sl)), true);
     if (k + Stager::kSlots < pcs.size()) RS2_TRY(issue(k + Stager::kSlots));
   }
   return RS2_OK;
 }
+
+// Opt-in stage profiler of a plan or a verifier: events recorded between launches on a stream.
+struct Prof {
+  bool on = false;
+  std::vector<hipEvent_t> free_events;
+  std::vector<std::pair<std::string, hipEvent_t>> pending;  // "" = start mark
+  std::map<std::string, std::pair<double, uint32_t>> acc;   // name -> (total ms, launches)
+  std::vector<std::string> order;
+  Prof() = default;
+  Prof(const Prof&) = delete;
+  Prof& operator=(const Prof&) = delete;
+  ~Prof() {
+    for (auto& e : free_events) (void)hipEventDestroy(e);
+    for (auto& pe : pending) (void)hipEventDestroy(pe.second);
+  }
+};
 
 }  // namespace
 }  // namespace rs2
@@ -1330,13 +1365,13 @@ struct rs2_plan {
   // the same role for split encodes (rs2_encode_device_split_async), at the device's greatest
   // stream priority; created on first use
   hipStream_t side_hi = nullptr;
-  hipEvent_t fork_ev = nullptr, join_ev = nullptr, copy_ev = nullptr;
+  Event fork_ev, join_ev, copy_ev;
   // the row codec's padded tail rows (a few workgroups) beside its main launch; created on
   // first use
   hipStream_t aux = nullptr;
-  hipEvent_t aux_ev = nullptr;
-  hipEvent_t leaf_ev = nullptr;        // the side stream's leaf hashes (run A) are done
-  hipEvent_t enc_done = nullptr;       // the last encode's work (guards re-binding its arrays)
+  Event aux_ev;
+  Event leaf_ev;                       // the side stream's leaf hashes (run A) are done
+  Event enc_done;                      // the last encode's work (guards re-binding its arrays)
   uint16_t n = 0, kp = 0, ks = 0, s = 0;
   uint64_t blob_len = 0;
   // encode
@@ -1382,31 +1417,10 @@ struct rs2_plan {
   // which the next call's stream waits for before it reuses them.
   DevBuf vb_row_tab, vb_slot_tab, vb_rows, vb_roots, vb_primary, vb_secondary, vb_hashes, vb_ids,
       vb_lens, vb_h_hashes, vb_h_ids, vb_h_verdict;
-  hipEvent_t vb_done = nullptr;
-  // opt-in stage profiler: events recorded between consecutive launches on the stream
-  struct Prof {
-    bool on = false;
-    std::vector<hipEvent_t> free_events;
-    std::vector<std::pair<std::string, hipEvent_t>> pending;  // "" = start mark
-    std::map<std::string, std::pair<double, uint32_t>> acc;   // name -> (total ms, launches)
-    std::vector<std::string> order;
-    Prof() = default;
-    Prof(const Prof&) = delete;
-    Prof& operator=(const Prof&) = delete;
-    ~Prof() {
-      for (auto& e : free_events) (void)hipEventDestroy(e);
-      for (auto& pe : pending) (void)hipEventDestroy(pe.second);
-    }
-  } prof;
-  ~rs2_plan() {
-    if (fork_ev) (void)hipEventDestroy(fork_ev);
-    if (join_ev) (void)hipEventDestroy(join_ev);
-    if (copy_ev) (void)hipEventDestroy(copy_ev);
-    if (aux_ev) (void)hipEventDestroy(aux_ev);
-    if (leaf_ev) (void)hipEventDestroy(leaf_ev);
+  Event vb_done;
+  Prof prof;  // opt-in stage profiler (rs2_profile_*)
+  ~rs2_plan() {  // (the Event members go after this body: after every stream, as dec[].done always did)
     if (aux) (void)hipStreamDestroy(aux);
-    if (enc_done) (void)hipEventDestroy(enc_done);
-    if (vb_done) (void)hipEventDestroy(vb_done);
     if (side) (void)hipStreamDestroy(side);
     if (side_hi) (void)hipStreamDestroy(side_hi);
     if (io) (void)hipStreamDestroy(io);
@@ -1441,12 +1455,11 @@ struct rs2_verifier {
   int rdec_slot = 0;
   DevBuf verdict_in, window_roots, per_sliver, sym_digests;
   DevBuf requests;  // bulk recovery symbols: a chunk of the request table (at most kRequestChunk)
-  rs2_plan::Prof prof;  // opt-in stage profiler of the recovery call (rs2_verifier_profile_*)
+  Prof prof;  // opt-in stage profiler of the recovery call (rs2_verifier_profile_*)
   // recorded on the caller's stream after each *_device_async call: destroy waits on it before
   // its buffers go back to the arena as quiesced (they may be handed out again at once)
-  hipEvent_t done = nullptr;
+  Event done;
   ~rs2_verifier() {
-    if (done) (void)hipEventDestroy(done);
     if (stream) (void)hipStreamDestroy(stream);
   }
 };
@@ -1462,19 +1475,16 @@ struct rs2_codec {
   PlannedJob enc;
   JobMem enc_mem;
   int64_t enc_key[4] = {-1, -1, -1, -1};
-  hipEvent_t enc_done = nullptr;
+  Event enc_done;
   DecodeSlot dec[2];
   int dec_slot = 0;
-  ~rs2_codec() {
-    if (enc_done) (void)hipEventDestroy(enc_done);
-  }
 };
 
 namespace {
 
 // Record a stage boundary on `st` (no-op unless profiling).  The stage's time is the span
 // from the previous mark on this plan; a mark named "" only starts a span.
-void mark(rs2_plan::Prof* prof, const char* name, hipStream_t st) {
+void mark(Prof* prof, const char* name, hipStream_t st) {
   auto& pr = *prof;
   if (!pr.on) return;
   hipEvent_t e;
@@ -1491,7 +1501,7 @@ void mark(rs2_plan::Prof* prof, const char* name, hipStream_t st) {
 void mark(rs2_plan* p, const char* name, hipStream_t st) { mark(&p->prof, name, st); }
 
 // one more span of `ms` under `name` in the profiler's histogram
-void prof_add(rs2_plan::Prof& pr, const std::string& name, double ms) {
+void prof_add(Prof& pr, const std::string& name, double ms) {
   auto it = pr.acc.find(name);
   if (it == pr.acc.end()) {
     pr.order.push_back(name);
@@ -1502,7 +1512,7 @@ void prof_add(rs2_plan::Prof& pr, const std::string& name, double ms) {
 }
 
 // host time since t0 under `name` (profiling on): the erasure-pattern planning of a decode
-void prof_host(rs2_plan::Prof* prof, const char* name,
+void prof_host(Prof* prof, const char* name,
                std::chrono::steady_clock::time_point t0) {
   auto& pr = *prof;
   if (!pr.on) return;
@@ -1516,7 +1526,7 @@ void prof_host(rs2_plan* p, const char* name, std::chrono::steady_clock::time_po
   prof_host(&p->prof, name, t0);
 }
 
-void prof_collect(rs2_plan::Prof& pr) {
+void prof_collect(Prof& pr) {
   hipEvent_t prev = nullptr;
   for (auto& pe : pr.pending) {
     (void)hipEventSynchronize(pe.second);
@@ -1530,8 +1540,71 @@ void prof_collect(rs2_plan::Prof& pr) {
   pr.pending.clear();
 }
 
-int prof_read(rs2_plan::Prof& pr, uint32_t max_stages, char* names, double* total_ms,
-              uint32_t* launches, uint32_t* n_stages);
+// Synchronise on the pending marks, hand out the per-stage totals (names: 32-byte NUL-padded
+// slots) and reset them.
+int prof_read(Prof& pr, uint32_t max_stages, char* names, double* total_ms, uint32_t* launches,
+              uint32_t* n_stages) {
+  prof_collect(pr);
+  uint32_t k = 0;
+  for (const auto& name : pr.order) {
+    if (k >= max_stages) break;
+    const auto& v = pr.acc[name];
+    if (names) {
+      std::memset(names + 32 * size_t(k), 0, 32);
+      std::strncpy(names + 32 * size_t(k), name.c_str(), 31);
+    }
+    if (total_ms) total_ms[k] = v.first;
+    if (launches) launches[k] = v.second;
+    ++k;
+  }
+  *n_stages = k;
+  pr.acc.clear();
+  pr.order.clear();
+  return RS2_OK;
+}
+
+int check_axis(int axis) {
+  if (axis == RS2_AXIS_PRIMARY || axis == RS2_AXIS_SECONDARY) return RS2_OK;
+  return fail(RS2_E_INVALID_ARGUMENT, "bad axis");
+}
+int check_value(int check) {
+  if (check == RS2_CHECK_SKIP || check == RS2_CHECK_DEFAULT || check == RS2_CHECK_STRICT)
+    return RS2_OK;
+  return fail(RS2_E_INVALID_ARGUMENT, "bad consistency check");
+}
+
+// The count rule of a batch call (`what`: "blobs in a batch", "slivers in a call"): n == 0 sets
+// *empty (the call returns RS2_OK); above 65535: refused; then !required is "null argument".
+int batch_count(uint32_t n, const char* what, bool required, bool* empty) {
+  *empty = n == 0;
+  if (n <= 65535) return n == 0 || required ? RS2_OK : fail(RS2_E_INVALID_ARGUMENT, "null argument");
+  return fail(RS2_E_INVALID_ARGUMENT, std::string("more than 65535 ") + what);
+}
+// The outcome of slot i's validation code rc: stored in status_out[i], or returned when status_out
+// is null and rc is an error; *accepted says whether the item takes part in the call.
+int slot_outcome(int rc, int* status_out, size_t i, bool* accepted) {
+  *accepted = rc == RS2_OK;
+  if (status_out) status_out[i] = rc;
+  return status_out ? RS2_OK : rc;
+}
+// fn(a, b) for every maximal run [a, b) of [first, last) whose slots (slot_of(i)) are
+// neighbours; stops at fn's first error.
+template <class SlotOf, class Fn>
+int for_each_run(size_t first, size_t last, SlotOf slot_of, Fn fn) {
+  for (size_t a = first; a < last;) {
+    size_t b = a + 1;
+    while (b < last && slot_of(b) == slot_of(b - 1) + 1) ++b;
+    RS2_TRY(fn(a, b));
+    a = b;
+  }
+  return RS2_OK;
+}
+// stats_out[i] = the i-th counter ("null argument" without stats_out)
+int read_stats(uint64_t* stats_out, std::initializer_list<const std::atomic<uint64_t>*> counters) {
+  if (!stats_out) return fail(RS2_E_INVALID_ARGUMENT, "null argument");
+  for (const auto* c : counters) *stats_out++ = c->load(std::memory_order_relaxed);
+  return RS2_OK;
+}
 
 int64_t primary_len(const rs2_plan* p) { return int64_t(p->ks) * p->s; }
 int64_t secondary_len(const rs2_plan* p) { return int64_t(p->kp) * p->s; }
@@ -1546,7 +1619,7 @@ int bind_encode_buffers(rs2_plan* p, uint8_t* d_primary, uint8_t* d_secondary, h
   if (p->bound_primary == d_primary && p->bound_secondary == d_secondary &&
       p->bound_both == d_both)
     return RS2_OK;
-  if (p->enc_done) HIP_TRY(hipEventSynchronize(p->enc_done));
+  HIP_TRY(p->enc_done.sync());
   p->bound_primary = p->bound_secondary = p->bound_both = nullptr;  // valid after a full rebind
   const int64_t s = p->s, n = p->n, kp = p->kp, ks = p->ks;
   // rows: secondary encoding (K = K_s) of primary slivers 0..K_p -> secondary slivers K_s..n
@@ -1604,7 +1677,7 @@ int encode_device(rs2_plan* p, const uint8_t* d_blob, uint8_t* d_primary, uint8_
   RS2_TRY(bind_encode_buffers(p, d_primary, d_secondary, st));
   // The plan's buffers (repair quadrant, leaves, tile counters) serve one encode at a time: an
   // encode queued on another stream than the previous one's runs after it on the device.
-  if (p->enc_done) HIP_TRY(hipStreamWaitEvent(st, p->enc_done, 0));
+  HIP_TRY(p->enc_done.wait_on(st));
   // A split encode's primary slivers (blob copy + systematic-column codec on the side stream)
   // are the critical path of the caller's next step (a decode, a send).  Round 1 ran them on a
   // high-priority side stream; with the bench's steps correctly ordered (round 2: each encode
@@ -1650,8 +1723,8 @@ int encode_device(rs2_plan* p, const uint8_t* d_blob, uint8_t* d_primary, uint8_
     mark(p, "enc_tail_rows", st);
     tail_base = tail - r_full * ks * s;  // row r >= r_full at tail_base + r * K_s * s
   }
-  HIP_TRY(hipEventRecord(p->fork_ev, st));
-  HIP_TRY(hipStreamWaitEvent(side, p->fork_ev, 0));
+  HIP_TRY(p->fork_ev.record(st));
+  HIP_TRY(p->fork_ev.wait_on(side));
   mark(p, "", side);
   if (p->prim_fused) {
     CodecJobBig cj = p->col_sys.job;
@@ -1675,15 +1748,15 @@ int encode_device(rs2_plan* p, const uint8_t* d_blob, uint8_t* d_primary, uint8_
     if (uint64_t(msg) > p->blob_len)
       HIP_TRY(hipMemsetAsync(d_primary + p->blob_len, 0, msg - p->blob_len, side));
     mark(p, "enc_blob_copy", side);
-    HIP_TRY(hipEventRecord(p->copy_ev, side));
+    HIP_TRY(p->copy_ev.record(side));
     HIP_TRY(launch_job(p->col_sys, int(ks), side, ctr));
   }
   mark(p, "enc_cols_sys_codec", side);
-  HIP_TRY(hipEventRecord(p->join_ev, side));
+  HIP_TRY(p->join_ev.record(side));
   // all primary slivers are final here (systematic rows + the column code's repair rows):
   // work the caller queues on prim_st next (a decode, a D2H to the NIC) starts now, beside
   // the secondary codecs and the hashing still running on st
-  if (prim_st) HIP_TRY(hipStreamWaitEvent(prim_st, p->join_ev, 0));
+  if (prim_st) HIP_TRY(p->join_ev.wait_on(prim_st));
   // RS2_TAIL_AUX=1 (A/B): the padded tail rows (a few workgroups) on a stream of their own
   // beside the main row launch instead of after it, the repair-column codec waiting for both.
   // Off by default since round 5: beside the persistent row kernel the tail's workgroups wait
@@ -1697,11 +1770,8 @@ int encode_device(rs2_plan* p, const uint8_t* d_blob, uint8_t* d_primary, uint8_
   const bool big = msg >= kBigMessage;
   const bool aux_tail = p->prim_fused && r_full < kp && r_full > 0 && tail_aux && big;
   if (aux_tail) {
-    if (!p->aux) {
-      HIP_TRY(hipStreamCreateWithFlags(&p->aux, hipStreamNonBlocking));
-      HIP_TRY(hipEventCreateWithFlags(&p->aux_ev, hipEventDisableTiming));
-    }
-    HIP_TRY(hipStreamWaitEvent(p->aux, p->fork_ev, 0));
+    if (!p->aux) HIP_TRY(hipStreamCreateWithFlags(&p->aux, hipStreamNonBlocking));
+    HIP_TRY(p->fork_ev.wait_on(p->aux));
     mark(p, "", p->aux);
     CodecJobBig tail = p->row.job;
     tail.line_base = int(r_full);
@@ -1709,7 +1779,7 @@ int encode_device(rs2_plan* p, const uint8_t* d_blob, uint8_t* d_primary, uint8_
     HIP_TRY(launch_codec_c(p->row.C, tail, int(kp - r_full), p->row.n_z, p->row.mode, p->aux, 1,
                            0, 0, 0, ctr + 2 * kTileCtrWords));
     mark(p, "enc_rows_tail", p->aux);
-    HIP_TRY(hipEventRecord(p->aux_ev, p->aux));
+    HIP_TRY(p->aux_ev.record(p->aux));
   }
   mark(p, "", st);
   if (r_full > 0) {
@@ -1719,14 +1789,14 @@ int encode_device(rs2_plan* p, const uint8_t* d_blob, uint8_t* d_primary, uint8_
                            0, ctr + kTileCtrWords));
   }
   if (aux_tail) {
-    HIP_TRY(hipStreamWaitEvent(st, p->aux_ev, 0));
+    HIP_TRY(p->aux_ev.wait_on(st));
   } else if (r_full < kp) {
     CodecJobBig tail = p->row.job;
     tail.line_base = int(r_full);
     if (p->prim_fused)  // the padded rows from the tail buffer (filled above, on st)
       for (int b = 0; b < tail.n_in; ++b) tail.in[b].base = tail_base;
     else  // from the systematic primary slivers once the side stream's copy has landed
-      HIP_TRY(hipStreamWaitEvent(st, p->copy_ev, 0));
+      HIP_TRY(p->copy_ev.wait_on(st));
     HIP_TRY(launch_codec_c(p->row.C, tail, int(kp - r_full), p->row.n_z, p->row.mode, st, 1, 0, 0,
                            0, ctr + 2 * kTileCtrWords));
   }
@@ -1745,7 +1815,7 @@ int encode_device(rs2_plan* p, const uint8_t* d_blob, uint8_t* d_primary, uint8_
     // whole rows in place, its zero-padded tail rows in the tail buffer, the repair rows K_p..n
     // in the primary scratch; then runs B and C (the secondary side) as below
     hipStream_t sa = split ? side : st;
-    if (!split) HIP_TRY(hipStreamWaitEvent(st, p->join_ev, 0));
+    if (!split) HIP_TRY(p->join_ev.wait_on(st));
     mark(p, "", sa);
     auto rows_run = [&](const uint8_t* base, int64_t r0, int64_t rows) -> int {
       if (rows <= 0) return RS2_OK;
@@ -1758,22 +1828,22 @@ int encode_device(rs2_plan* p, const uint8_t* d_blob, uint8_t* d_primary, uint8_
     if (rc2 == RS2_OK) rc2 = rows_run(d_primary + kp * ks * s, kp, n - kp);
     if (rc2 != RS2_OK) return rc2;
     mark(p, "enc_leaf_hash_a", sa);
-    if (split) HIP_TRY(hipEventRecord(p->leaf_ev, side));
+    if (split) HIP_TRY(p->leaf_ev.record(side));
     mark(p, "", st);
     HIP_TRY(rs2k_launch_leaf_hash(map, 3, n * n, 1, p->leaves.as<uint8_t>(), st));
     mark(p, "enc_leaf_hash", st);
-    if (split) HIP_TRY(hipStreamWaitEvent(st, p->leaf_ev, 0));
+    if (split) HIP_TRY(p->leaf_ev.wait_on(st));
   } else if (split) {
     mark(p, "", side);
     HIP_TRY(rs2k_launch_leaf_hash(map, 2, n * n, 1, p->leaves.as<uint8_t>(), side));
     mark(p, "enc_leaf_hash_a", side);
-    HIP_TRY(hipEventRecord(p->leaf_ev, side));
+    HIP_TRY(p->leaf_ev.record(side));
     mark(p, "", st);
     HIP_TRY(rs2k_launch_leaf_hash(map, 3, n * n, 1, p->leaves.as<uint8_t>(), st));
     mark(p, "enc_leaf_hash", st);
-    HIP_TRY(hipStreamWaitEvent(st, p->leaf_ev, 0));  // after join_ev on the side stream
+    HIP_TRY(p->leaf_ev.wait_on(st));  // after join_ev on the side stream
   } else {
-    HIP_TRY(hipStreamWaitEvent(st, p->join_ev, 0));
+    HIP_TRY(p->join_ev.wait_on(st));
     mark(p, "", st);
     if (!p->sys_fused) {
       // systematic secondary slivers: secondary c, row r = primary r, column c (c < K_s)
@@ -1798,8 +1868,17 @@ int encode_device(rs2_plan* p, const uint8_t* d_blob, uint8_t* d_primary, uint8_
   HIP_TRY(rs2k_launch_merkle_root(pairs, int(n), p->blob_len,
                                   d_blob_id ? d_blob_id : p->blob_id.as<uint8_t>(), st));
   mark(p, "enc_merkle_root", st);
-  HIP_TRY(hipEventRecord(p->enc_done, st));  // st has joined the side stream above
+  HIP_TRY(p->enc_done.record(st));  // st has joined the side stream above
   return RS2_OK;
+}
+
+// The metadata alone (BlobEncoder::compute_metadata): the slivers go to the plan's own buffers.
+int encode_metadata(rs2_plan* p, const uint8_t* d_blob, uint8_t* d_hashes, uint8_t* d_blob_id,
+                    hipStream_t st) {
+  HIP_TRY(p->int_primary.ensure(size_t(p->n) * primary_len(p)));
+  HIP_TRY(p->int_secondary.ensure(size_t(p->n) * secondary_len(p)));
+  return encode_device(p, d_blob, p->int_primary.as<uint8_t>(), p->int_secondary.as<uint8_t>(),
+                       d_hashes, d_blob_id, st, false);
 }
 
 // Blob batch (the upload relay's many-blob encode, walrus-upload-relay/src/controller.rs:177;
@@ -1816,10 +1895,10 @@ int encode_batch_device(rs2_plan* p, uint32_t n_blobs, const uint8_t* d_blobs, i
                         const uint64_t* d_lens_ready = nullptr) {
   const int64_t s = p->s, n = p->n, kp = p->kp, ks = p->ks;
   const int64_t msg = kp * ks * s, pl = ks * s, sl = kp * s;
-  if (n_blobs == 0) return RS2_OK;
-  if (n_blobs > 65535) return fail(RS2_E_INVALID_ARGUMENT, "more than 65535 blobs in a batch");
-  if (!d_primary || !d_secondary || !d_hashes || !d_blob_ids)
-    return fail(RS2_E_INVALID_ARGUMENT, "null argument");
+  bool empty;
+  RS2_TRY(batch_count(n_blobs, "blobs in a batch",
+                      d_primary && d_secondary && d_hashes && d_blob_ids, &empty));
+  if (empty) return RS2_OK;
   if (p_stride < n * pl || s_stride < n * sl)
     return fail(RS2_E_INVALID_ARGUMENT, "sliver stride smaller than a blob's slivers");
   std::vector<uint64_t> lv(n_blobs, p->blob_len);
@@ -1841,7 +1920,7 @@ int encode_batch_device(rs2_plan* p, uint32_t n_blobs, const uint8_t* d_blobs, i
   // d_lens_ready: the caller has the same lengths on the device already (a verified decode
   // batch uploads its call's lengths once, so no run of a window waits for the one before)
   if (!d_lens_ready && lv != p->batch_lens_h) {  // upload the lengths (the host copy stays alive until it lands)
-    if (p->enc_done) HIP_TRY(hipEventSynchronize(p->enc_done));
+    HIP_TRY(p->enc_done.sync());
     p->batch_lens_h = lv;
     HIP_TRY(p->batch_lens.ensure(lv.size() * 8));
     HIP_TRY(p->ctx->upload(p->batch_lens.p, p->batch_lens_h.data(), lv.size() * 8, st));
@@ -1885,7 +1964,7 @@ int encode_batch_device(rs2_plan* p, uint32_t n_blobs, const uint8_t* d_blobs, i
   mark(p, "enc_merkle_trees", st);
   HIP_TRY(rs2k_launch_merkle_root(d_hashes, int(n), p->blob_len, d_blob_ids, st, B, d_lens));
   mark(p, "enc_merkle_root", st);
-  HIP_TRY(hipEventRecord(p->enc_done, st));
+  HIP_TRY(p->enc_done.record(st));
   return RS2_OK;
 }
 
@@ -1933,12 +2012,12 @@ int select_slivers(const rs2_plan* p, int axis, uint32_t count, const uint16_t* 
 // bytes written are the same).  A source offset of 2^63 or more is negative in sp.present and
 // so counts as absent here, as it always did for the decode plan itself.
 int run_decode(Context* ctx, DecodeSlot (&slots)[2], int& cursor, DecodeSpec& sp,
-               std::vector<int64_t> key, bool may_fuse, int lines, rs2_plan::Prof* prof,
+               std::vector<int64_t> key, bool may_fuse, int lines, Prof* prof,
                hipStream_t st) {
   DecodeSlot& sl = slots[cursor];
   cursor ^= 1;
   const auto wait_t0 = std::chrono::steady_clock::now();
-  if (sl.done) HIP_TRY(hipEventSynchronize(sl.done));
+  HIP_TRY(sl.done.sync());
   if (prof) prof_host(prof, "dec_host_slotwait", wait_t0);
   std::vector<int64_t>& copy_src = sl.copy_src_h;
   std::vector<int64_t>& copy_dst = sl.copy_dst_h;
@@ -1990,8 +2069,7 @@ int run_decode(Context* ctx, DecodeSlot (&slots)[2], int& cursor, DecodeSpec& sp
     HIP_TRY(launch_job(pj, lines, st));
     if (prof) mark(prof, "dec_codec", st);
   }
-  if (!sl.done) HIP_TRY(hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
-  HIP_TRY(hipEventRecord(sl.done, st));
+  HIP_TRY(sl.done.record(st));
   sl.key = std::move(key);
   sl.fused = fused;
   return RS2_OK;
@@ -2044,10 +2122,6 @@ int decode_device(rs2_plan* p, int axis, const std::vector<std::pair<uint16_t, u
   return run_decode(p->ctx, p->dec, p->dec_slot, sp, std::move(key), decode_may_fuse(), lines,
                     &p->prof,
                     st);
-}
-int decode_device(rs2_plan* p, int axis, const std::vector<std::pair<uint16_t, uint32_t>>& chosen,
-                  const uint8_t* base, const uint64_t* off, uint8_t* d_out, hipStream_t st) {
-  return decode_device(p, axis, chosen, base, off, d_out, st, p->blob_len);
 }
 
 // Stream argument of the plan / verifier ABI: NULL = the object's own stream,
@@ -2129,20 +2203,6 @@ struct BatchBlob {
   std::vector<int> in_sd, out_sd;
 };
 
-void plan_batch_spec(const DecodeSpec& sp, uint32_t originals, BatchBlob& bb);
-
-void plan_batch_blob(const rs2_plan* p, int axis, const BatchItem& it, const uint8_t* base,
-                     BatchBlob& bb) {
-  DecodeSpec sp;
-  std::vector<int64_t> key;
-  blob_decode_spec(p, axis, it.chosen, base, it.off, it.out, it.len, sp, key);
-  uint32_t originals = 0;
-  for (uint32_t i = 0; i < sp.K; ++i) originals += sp.present[i] >= 0;
-  if (originals == sp.K) return;  // nothing erased: a copy (the per-blob path)
-  sp.copy_present = originals > 0 && sp.symbol_size >= 4 && decode_may_fuse();
-  plan_batch_spec(sp, originals, bb);
-}
-
 // Plan `sp` (with `originals` of its K originals present, not all of them, and copy_present set
 // by the caller's rule) as a job of a batch launch; bb.eligible stays false when it cannot be one.
 void plan_batch_spec(const DecodeSpec& sp, uint32_t originals, BatchBlob& bb) {
@@ -2165,6 +2225,18 @@ void plan_batch_spec(const DecodeSpec& sp, uint32_t originals, BatchBlob& bb) {
   bb.in_sd = std::move(pj.in_sd);
   bb.out_sd = std::move(pj.out_sd);
   bb.eligible = true;
+}
+
+void plan_batch_blob(const rs2_plan* p, int axis, const BatchItem& it, const uint8_t* base,
+                     BatchBlob& bb) {
+  DecodeSpec sp;
+  std::vector<int64_t> key;
+  blob_decode_spec(p, axis, it.chosen, base, it.off, it.out, it.len, sp, key);
+  uint32_t originals = 0;
+  for (uint32_t i = 0; i < sp.K; ++i) originals += sp.present[i] >= 0;
+  if (originals == sp.K) return;  // nothing erased: a copy (the per-blob path)
+  sp.copy_present = originals > 0 && sp.symbol_size >= 4 && decode_may_fuse();
+  plan_batch_spec(sp, originals, bb);
 }
 
 // Upload through the slot ring in pieces of at most a slot (never the runtime's copy from
@@ -2193,17 +2265,26 @@ hipError_t launch_decode_batch(int C, const CodecJobBatch* d_jobs, int n_blobs, 
   }
 }
 
+// What a window of a batched call runs with: its owner's (a blob plan's, a verifier's) slot pair,
+// cursor, lines per job, profiler and planning stage name, and counters: launches, batched, single.
+struct BatchRun {
+  Context* ctx;
+  BatchDecodeSlot (&slots)[2];
+  int& cursor;
+  int lines;
+  Prof* prof;
+  const char* plan_stage;
+  std::atomic<uint64_t>&launches, &batched, &single;
+};
+
 // One chunk: the blobs' arrays concatenated into the slot's device arrays, every job pointed
-// at its own part, one table build over all the logs, one launch.  The slot pair and its cursor
-// belong to the caller (a blob plan, or a verifier recovering slivers); `prof` (may be null) is
-// the caller's stage profiler.
-int launch_batch_chunk(Context* ctx, BatchDecodeSlot (&slots)[2], int& cursor,
-                       std::vector<BatchBlob*>& ch, int lines, rs2_plan::Prof* prof,
-                       hipStream_t st) {
-  BatchDecodeSlot& sl = slots[cursor];
-  cursor ^= 1;
-  if (sl.done) HIP_TRY(hipEventSynchronize(sl.done));
-  if (prof) mark(prof, "", st);
+// at its own part, one table build over all the logs, one launch.
+int launch_batch_chunk(const BatchRun& run, std::vector<BatchBlob*>& ch, hipStream_t st) {
+  Context* ctx = run.ctx;
+  BatchDecodeSlot& sl = run.slots[run.cursor];
+  run.cursor ^= 1;
+  HIP_TRY(sl.done.sync());
+  if (run.prof) mark(run.prof, "", st);
   size_t n_offs = 0, n_logs = 0, n_mix = 0;
   for (const BatchBlob* bb : ch) {
     n_offs += bb->offs.size();
@@ -2223,7 +2304,7 @@ int launch_batch_chunk(Context* ctx, BatchDecodeSlot (&slots)[2], int& cursor,
   HIP_TRY(sl.mix.ensure(std::max<size_t>(n_mix * 2, 16)));
   HIP_TRY(sl.jobs.ensure(ch.size() * sizeof(CodecJobBatch)));
   const int C = ch[0]->C;
-  const int64_t per_blob = (int64_t(lines) * ch[0]->job.pairs_span + 63) / 64;
+  const int64_t per_blob = (int64_t(run.lines) * ch[0]->job.pairs_span + 63) / 64;
   if (per_blob < 1 || per_blob * int64_t(ch.size()) > 0x7FFFFFFF)
     return fail(RS2_E_UNSUPPORTED, "decode batch chunk exceeds the launch grid");
   int n_z = 1;
@@ -2258,7 +2339,7 @@ int launch_batch_chunk(Context* ctx, BatchDecodeSlot (&slots)[2], int& cursor,
     }
     j.mix_tab = bb->mix.empty() ? nullptr : sl.mix.as<uint16_t>() + h_mix.size();
     // the launch's fields (set_launch_shape): this blob alone, lines folded into the tiles
-    j.n_lines = lines;
+    j.n_lines = run.lines;
     j.line_base = 0;
     j.tiles_per_blob = 0;
     j.in_blob_stride = j.out_blob_stride = j.copy_blob_stride = 0;
@@ -2277,12 +2358,42 @@ int launch_batch_chunk(Context* ctx, BatchDecodeSlot (&slots)[2], int& cursor,
   HIP_TRY(rs2k_launch_build_mul_tables(ctx->exp_t.as<uint16_t>(), ctx->log_t.as<uint16_t>(),
                                        sl.logs.as<uint16_t>(), int(h_logs.size()),
                                        sl.tabs.as<uint16_t>(), st));
-  if (prof) mark(prof, "dec_batch_setup", st);
+  if (run.prof) mark(run.prof, "dec_batch_setup", st);
   HIP_TRY(launch_decode_batch(C, sl.jobs.as<CodecJobBatch>(), int(ch.size()), int(per_blob), n_z,
                               st));
-  if (prof) mark(prof, "dec_batch_codec", st);
-  if (!sl.done) HIP_TRY(hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
-  HIP_TRY(hipEventRecord(sl.done, st));
+  if (run.prof) mark(run.prof, "dec_batch_codec", st);
+  HIP_TRY(sl.done.record(st));
+  return RS2_OK;
+}
+
+// One window of cnt items: plan(i, job) for every item on the host pool; the eligible jobs in
+// chunks (cut_batch_chunks within kBatchTableBytes), one launch each on st; every other item,
+// those the cut demotes included, through single(i) on the same stream.
+template <class Plan, class Single>
+int run_batch_window(const BatchRun& run, size_t cnt, hipStream_t st, Plan plan, Single single) {
+  std::vector<BatchBlob> jobs(cnt);
+  const auto host_t0 = std::chrono::steady_clock::now();
+  pool_for_each(run.ctx->pool, cnt, [&](size_t i) { plan(i, jobs[i]); });
+  prof_host(run.prof, run.plan_stage, host_t0);
+  std::vector<ChunkJob> geo(cnt);
+  for (size_t i = 0; i < cnt; ++i)
+    geo[i] = {jobs[i].eligible, jobs[i].C, jobs[i].job.pairs_span, jobs[i].logs.size()};
+  ChunkCut cut;
+  cut_batch_chunks(geo, kBatchTableBytes, cut);
+  for (uint32_t i : cut.demoted) jobs[i].eligible = false;
+  std::vector<BatchBlob*> ch;
+  for (size_t c = 0, at = 0; c < cut.ends.size(); at = cut.ends[c++]) {
+    ch.clear();
+    for (size_t m = at; m < cut.ends[c]; ++m) ch.push_back(&jobs[cut.members[m]]);
+    RS2_TRY(launch_batch_chunk(run, ch, st));
+    run.launches.fetch_add(1, std::memory_order_relaxed);
+    run.batched.fetch_add(ch.size(), std::memory_order_relaxed);
+  }
+  for (size_t i = 0; i < cnt; ++i) {
+    if (jobs[i].eligible) continue;
+    RS2_TRY(single(i));
+    run.single.fetch_add(1, std::memory_order_relaxed);
+  }
   return RS2_OK;
 }
 
@@ -2291,50 +2402,18 @@ int launch_batch_chunk(Context* ctx, BatchDecodeSlot (&slots)[2], int& cursor,
 // per-blob decode on the same stream.
 int decode_batch_items(rs2_plan* p, int axis, const std::vector<BatchItem>& items,
                        const uint8_t* base, hipStream_t st) {
-  Context* ctx = p->ctx;
   const int lines = axis == RS2_AXIS_PRIMARY ? int(p->ks) : int(p->kp);
+  const BatchRun run{p->ctx, p->dbatch, p->dbatch_slot, lines, &p->prof, "dec_batch_plan_host",
+                     g_batch_launches, g_batch_blobs, g_batch_single};
   for (size_t w0 = 0; w0 < items.size(); w0 += kBatchChunkJobs) {
     const size_t cnt = std::min(kBatchChunkJobs, items.size() - w0);
-    std::vector<BatchBlob> blobs(cnt);
-    const auto host_t0 = std::chrono::steady_clock::now();
-    {
-      const size_t T = std::min<size_t>(size_t(ctx->pool.threads()), cnt);
-      std::vector<std::function<void()>> tasks;
-      for (size_t t = 0; t < T; ++t)
-        tasks.emplace_back([&, t] {
-          for (size_t i = t; i < cnt; i += T) plan_batch_blob(p, axis, items[w0 + i], base, blobs[i]);
-        });
-      ctx->pool.run(tasks);
-    }
-    prof_host(p, "dec_batch_plan_host", host_t0);
-    std::vector<BatchBlob*> ch;
-    size_t tab_bytes = 0;
-    for (size_t i = 0; i <= cnt; ++i) {
-      BatchBlob* bb = i < cnt && blobs[i].eligible ? &blobs[i] : nullptr;
-      // a blob whose lane space or block size differs from the first eligible blob's cannot
-      // share its launch geometry
-      if (bb && !ch.empty() &&
-          (bb->C != ch[0]->C || bb->job.pairs_span != ch[0]->job.pairs_span))
-        bb->eligible = false, bb = nullptr;
-      const size_t need = bb ? bb->logs.size() * kTabU16 * 2 : 0;
-      if (!ch.empty() && (i == cnt || (bb && tab_bytes + need > kBatchTableBytes))) {
-        RS2_TRY(launch_batch_chunk(ctx, p->dbatch, p->dbatch_slot, ch, lines, &p->prof, st));
-        g_batch_launches.fetch_add(1, std::memory_order_relaxed);
-        g_batch_blobs.fetch_add(ch.size(), std::memory_order_relaxed);
-        ch.clear();
-        tab_bytes = 0;
-      }
-      if (bb) {
-        ch.push_back(bb);
-        tab_bytes += need;
-      }
-    }
-    for (size_t i = 0; i < cnt; ++i) {
-      if (blobs[i].eligible) continue;
-      const BatchItem& it = items[w0 + i];
-      RS2_TRY(decode_device(p, axis, it.chosen, base, it.off, it.out, st, it.len));
-      g_batch_single.fetch_add(1, std::memory_order_relaxed);
-    }
+    RS2_TRY(run_batch_window(
+        run, cnt, st,
+        [&](size_t i, BatchBlob& bb) { plan_batch_blob(p, axis, items[w0 + i], base, bb); },
+        [&](size_t i) {
+          const BatchItem& it = items[w0 + i];
+          return decode_device(p, axis, it.chosen, base, it.off, it.out, st, it.len);
+        }));
   }
   return RS2_OK;
 }
@@ -2375,25 +2454,12 @@ int validate_batch_device(const rs2_plan* plan, int axis, uint32_t n_blobs,
       return select_slivers(plan, axis, counts[b], it.idx, nullptr, nullptr, it.chosen,
                             &it.pulled);
     };
-    const int rc = validate();
-    if (status_out)
-      status_out[b] = rc;
-    else if (rc != RS2_OK)
-      return rc;
-    if (rc == RS2_OK) items.push_back(std::move(it));
+    bool ok;
+    RS2_TRY(slot_outcome(validate(), status_out, b, &ok));
+    if (ok) items.push_back(std::move(it));
   }
   return RS2_OK;
 }
-
-// The host-buffer batch decode, plain (check == kNoCheck: rs2_decode_batch) or verified
-// (rs2_decode_and_verify_batch); defined with the verified batch below.
-constexpr int kNoCheck = -1;
-int decode_batch_host(rs2_plan* plan, int axis, uint32_t n_blobs, const uint64_t* blob_lens,
-                      const uint32_t* counts, const uint16_t* sliver_idx,
-                      const uint8_t* const* slivers, const uint64_t* sliver_len,
-                      const uint16_t* sliver_symbol_size, const uint8_t* hashes,
-                      const uint8_t* blob_ids, int check, uint8_t* const* blobs_out,
-                      int32_t* verdict_out, int* status_out);
 
 }  // namespace
 
@@ -2472,11 +2538,6 @@ int rs2_plan_create(uint16_t n_shards, uint64_t blob_len, rs2_plan** out) {
   p->blob_len = blob_len;
   HIP_TRY(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
   HIP_TRY(hipStreamCreateWithFlags(&p->side, hipStreamNonBlocking));
-  HIP_TRY(hipEventCreateWithFlags(&p->fork_ev, hipEventDisableTiming));
-  HIP_TRY(hipEventCreateWithFlags(&p->join_ev, hipEventDisableTiming));
-  HIP_TRY(hipEventCreateWithFlags(&p->copy_ev, hipEventDisableTiming));
-  HIP_TRY(hipEventCreateWithFlags(&p->leaf_ev, hipEventDisableTiming));
-  HIP_TRY(hipEventCreateWithFlags(&p->enc_done, hipEventDisableTiming));
   const int64_t n = n_shards;
   HIP_TRY(p->both.ensure(size_t(n - kp) * (n - ks) * s));
   HIP_TRY(p->leaves.ensure(size_t(n) * n * 32));
@@ -2515,9 +2576,9 @@ void rs2_plan_destroy(rs2_plan* plan) {
   // its buffers then go straight back to the device arena for the next plan
   for (hipStream_t st : {plan->stream, plan->side, plan->side_hi, plan->aux, plan->io})
     if (st) (void)hipStreamSynchronize(st);
-  for (hipEvent_t ev : {plan->enc_done, plan->dec[0].done, plan->dec[1].done, plan->leaf_ev,
-                        plan->dbatch[0].done, plan->dbatch[1].done, plan->vb_done})
-    if (ev) (void)hipEventSynchronize(ev);
+  for (const Event* ev : {&plan->enc_done, &plan->dec[0].done, &plan->dec[1].done, &plan->leaf_ev,
+                          &plan->dbatch[0].done, &plan->dbatch[1].done, &plan->vb_done})
+    (void)ev->sync();
   const Quiesced quiesced;
   delete plan;
 }
@@ -2570,11 +2631,7 @@ int rs2_device_memory_stats(int device, uint64_t* stats_out) {
 }
 
 int rs2_upload_stats(uint64_t* stats_out) {
-  if (!stats_out) return fail(RS2_E_INVALID_ARGUMENT, "null argument");
-  stats_out[0] = g_upload_calls.load(std::memory_order_relaxed);
-  stats_out[1] = g_upload_jobs.load(std::memory_order_relaxed);
-  stats_out[2] = g_upload_waits.load(std::memory_order_relaxed);
-  return RS2_OK;
+  return read_stats(stats_out, {&g_upload_calls, &g_upload_jobs, &g_upload_waits});
 }
 
 int rs2_device_memory_trim(int device, uint64_t* released_bytes) {
@@ -2609,13 +2666,9 @@ int rs2_compute_metadata_device_async(rs2_plan* plan, const void* d_blob, void* 
     return fail(RS2_E_INVALID_ARGUMENT, "null argument");
   RS2_TRY(check_encode_ptrs(d_blob, nullptr, nullptr, d_hashes, d_blob_id));
   HIP_TRY(hipSetDevice(plan->ctx->device));
-  const int64_t n = plan->n;
-  HIP_TRY(plan->int_primary.ensure(size_t(n) * primary_len(plan)));
-  HIP_TRY(plan->int_secondary.ensure(size_t(n) * secondary_len(plan)));
-  return encode_device(plan, reinterpret_cast<const uint8_t*>(d_blob),
-                       plan->int_primary.as<uint8_t>(), plan->int_secondary.as<uint8_t>(),
-                       reinterpret_cast<uint8_t*>(d_hashes), reinterpret_cast<uint8_t*>(d_blob_id),
-                       pick_stream(plan, stream), false);
+  return encode_metadata(plan, reinterpret_cast<const uint8_t*>(d_blob),
+                         reinterpret_cast<uint8_t*>(d_hashes), reinterpret_cast<uint8_t*>(d_blob_id),
+                         pick_stream(plan, stream));
 }
 
 int rs2_encode_device_split_async(rs2_plan* plan, const void* d_blob, void* d_primary,
@@ -2640,14 +2693,14 @@ int rs2_decode_device_async(rs2_plan* plan, int axis, uint32_t count, const uint
                             void* d_blob_out, void* stream) {
   if (!plan || !sliver_idx || !sliver_off || !d_slivers_base || !d_blob_out)
     return fail(RS2_E_INVALID_ARGUMENT, "null argument");
-  if (axis != RS2_AXIS_PRIMARY && axis != RS2_AXIS_SECONDARY)
-    return fail(RS2_E_INVALID_ARGUMENT, "bad axis");
+  RS2_TRY(check_axis(axis));
   RS2_TRY(check_decode_ptrs(count, d_slivers_base, sliver_off, d_blob_out));
   HIP_TRY(hipSetDevice(plan->ctx->device));
   std::vector<std::pair<uint16_t, uint32_t>> chosen;
   RS2_TRY(select_slivers(plan, axis, count, sliver_idx, nullptr, nullptr, chosen));
   return decode_device(plan, axis, chosen, reinterpret_cast<const uint8_t*>(d_slivers_base),
-                       sliver_off, reinterpret_cast<uint8_t*>(d_blob_out), pick_stream(plan, stream));
+                       sliver_off, reinterpret_cast<uint8_t*>(d_blob_out), pick_stream(plan, stream),
+                       plan->blob_len);
 }
 
 int rs2_profile_enable(rs2_plan* plan, int enable) {
@@ -2676,35 +2729,6 @@ int rs2_verifier_profile_read(rs2_verifier* v, uint32_t max_stages, char* names,
   return prof_read(v->prof, max_stages, names, total_ms, launches, n_stages);
 }
 
-}  // extern "C"
-
-namespace {
-// Synchronise on the pending marks, hand out the per-stage totals (names: 32-byte NUL-padded
-// slots) and reset them.
-int prof_read(rs2_plan::Prof& pr, uint32_t max_stages, char* names, double* total_ms,
-              uint32_t* launches, uint32_t* n_stages) {
-  prof_collect(pr);
-  uint32_t k = 0;
-  for (const auto& name : pr.order) {
-    if (k >= max_stages) break;
-    const auto& v = pr.acc[name];
-    if (names) {
-      std::memset(names + 32 * size_t(k), 0, 32);
-      std::strncpy(names + 32 * size_t(k), name.c_str(), 31);
-    }
-    if (total_ms) total_ms[k] = v.first;
-    if (launches) launches[k] = v.second;
-    ++k;
-  }
-  *n_stages = k;
-  pr.acc.clear();
-  pr.order.clear();
-  return RS2_OK;
-}
-}  // namespace
-
-extern "C" {
-
 int rs2_sync(rs2_plan* plan, void* stream) {
   if (!plan) return fail(RS2_E_INVALID_ARGUMENT, "null plan");
   HIP_TRY(hipStreamSynchronize(pick_stream(plan, stream)));
@@ -2722,10 +2746,10 @@ struct RingGuard {
   ~RingGuard() {
     // the ring's slot events were recorded on this plan's streams, which may be destroyed before
     // the next lease waits on them: drain them and move them to the context's stream
-    for (hipEvent_t ev : lease.st->ev)
-      if (ev) {
-        (void)hipEventSynchronize(ev);
-        (void)hipEventRecord(ev, p->ctx->util_stream);
+    for (Event& ev : lease.st->ev)
+      if (ev.set()) {
+        (void)ev.sync();
+        (void)ev.record(p->ctx->util_stream);
       }
     p->stage = nullptr;
   }
@@ -2768,7 +2792,7 @@ int rs2_encode_with_metadata(rs2_plan* plan, const uint8_t* blob, uint8_t* const
     if (secondary_out[i]) segs.push_back({secondary_out[i], ds + i * sl, size_t(sl)});
   if (hashes_out) segs.push_back({hashes_out, plan->pairs.as<uint8_t>(), size_t(n) * 64});
   if (blob_id_out) segs.push_back({blob_id_out, plan->blob_id.as<uint8_t>(), 32});
-  HIP_TRY(hipStreamWaitEvent(io, plan->enc_done, 0));
+  HIP_TRY(plan->enc_done.wait_on(io));
   if (!segs.empty()) RS2_TRY(stage_d2h(ctx, *plan->stage, segs, io));
   HIP_TRY(hipStreamSynchronize(io));
   HIP_TRY(hipStreamSynchronize(st));
@@ -2803,8 +2827,9 @@ int rs2_encode_batch_with_metadata(rs2_plan* plan, uint32_t n_blobs, const uint8
                                    uint8_t* const* secondary_out, uint8_t* hashes_out,
                                    uint8_t* blob_ids_out) {
   if (!plan) return fail(RS2_E_INVALID_ARGUMENT, "null plan");
-  if (n_blobs == 0) return RS2_OK;
-  if (n_blobs > 65535) return fail(RS2_E_INVALID_ARGUMENT, "more than 65535 blobs in a batch");
+  bool empty;
+  RS2_TRY(batch_count(n_blobs, "blobs in a batch", true, &empty));
+  if (empty) return RS2_OK;
   HIP_TRY(hipSetDevice(plan->ctx->device));
   RingGuard ring(plan);
   Context* ctx = plan->ctx;
@@ -2856,12 +2881,11 @@ int rs2_decode_batch_device_async(rs2_plan* plan, int axis, uint32_t n_blobs,
                                   const uint64_t* sliver_off, void* d_blobs_out,
                                   uint64_t out_stride, int* status_out, void* stream) {
   if (!plan) return fail(RS2_E_INVALID_ARGUMENT, "null plan");
-  if (axis != RS2_AXIS_PRIMARY && axis != RS2_AXIS_SECONDARY)
-    return fail(RS2_E_INVALID_ARGUMENT, "bad axis");
-  if (n_blobs == 0) return RS2_OK;
-  if (n_blobs > 65535) return fail(RS2_E_INVALID_ARGUMENT, "more than 65535 blobs in a batch");
-  if (!counts || !sliver_idx || !sliver_off || !d_slivers_base || !d_blobs_out)
-    return fail(RS2_E_INVALID_ARGUMENT, "null argument");
+  RS2_TRY(check_axis(axis));
+  bool empty;
+  RS2_TRY(batch_count(n_blobs, "blobs in a batch",
+                      counts && sliver_idx && sliver_off && d_slivers_base && d_blobs_out, &empty));
+  if (empty) return RS2_OK;
   RS2_TRY(check_symbol_ptr(d_slivers_base, "d_slivers_base"));
   RS2_TRY(check_symbol_ptr(d_blobs_out, "d_blobs_out"));
   RS2_TRY(check_symbol_step(out_stride, "out_stride"));
@@ -2874,22 +2898,8 @@ int rs2_decode_batch_device_async(rs2_plan* plan, int axis, uint32_t n_blobs,
                             pick_stream(plan, stream));
 }
 
-int rs2_decode_batch(rs2_plan* plan, int axis, uint32_t n_blobs, const uint64_t* blob_lens,
-                     const uint32_t* counts, const uint16_t* sliver_idx,
-                     const uint8_t* const* slivers, const uint64_t* sliver_len,
-                     const uint16_t* sliver_symbol_size, uint8_t* const* blobs_out,
-                     int* status_out) {
-  return decode_batch_host(plan, axis, n_blobs, blob_lens, counts, sliver_idx, slivers, sliver_len,
-                           sliver_symbol_size, nullptr, nullptr, kNoCheck, blobs_out, nullptr,
-                           status_out);
-}
-
 int rs2_decode_batch_stats(uint64_t* stats_out) {
-  if (!stats_out) return fail(RS2_E_INVALID_ARGUMENT, "null argument");
-  stats_out[0] = g_batch_launches.load(std::memory_order_relaxed);
-  stats_out[1] = g_batch_blobs.load(std::memory_order_relaxed);
-  stats_out[2] = g_batch_single.load(std::memory_order_relaxed);
-  return RS2_OK;
+  return read_stats(stats_out, {&g_batch_launches, &g_batch_blobs, &g_batch_single});
 }
 
 }  // extern "C"
@@ -2904,8 +2914,7 @@ int decode_host(rs2_plan* plan, int axis, uint32_t count, const uint16_t* sliver
                 const uint16_t* sliver_symbol_size, uint32_t* pulled) {
   if (count && (!sliver_idx || !slivers || !sliver_len))
     return fail(RS2_E_INVALID_ARGUMENT, "null argument");
-  if (axis != RS2_AXIS_PRIMARY && axis != RS2_AXIS_SECONDARY)
-    return fail(RS2_E_INVALID_ARGUMENT, "bad axis");
+  RS2_TRY(check_axis(axis));
   HIP_TRY(hipSetDevice(plan->ctx->device));
   std::vector<std::pair<uint16_t, uint32_t>> chosen;
   RS2_TRY(select_slivers(plan, axis, count, sliver_idx, sliver_len, sliver_symbol_size, chosen,
@@ -2931,7 +2940,7 @@ int decode_host(rs2_plan* plan, int axis, uint32_t count, const uint16_t* sliver
     HIP_TRY(hipMemsetAsync(plan->dev_blob.as<uint8_t>() + plan->blob_len, 0,
                            size_t(msg - plan->blob_len), st));
   return decode_device(plan, axis, chosen, stage.as<uint8_t>(), off.data(),
-                       plan->dev_blob.as<uint8_t>(), st);
+                       plan->dev_blob.as<uint8_t>(), st, plan->blob_len);
 }
 
 // Default consistency check (blob_encoding.rs:579-612) on a decoded blob on the device (`blob`,
@@ -2994,17 +3003,28 @@ int default_check(rs2_plan* plan, const std::vector<uint8_t>& verified, const ui
 // Strict consistency check (config.rs:164-172): the metadata of the decoded blob (blob_len bytes
 // on the device), re-derived on the device, must give the same blob id.
 int strict_check(rs2_plan* plan, const uint8_t* blob_id, const uint8_t* blob, hipStream_t st) {
-  const int64_t n = plan->n;
-  HIP_TRY(plan->int_primary.ensure(size_t(n) * primary_len(plan)));
-  HIP_TRY(plan->int_secondary.ensure(size_t(n) * secondary_len(plan)));
-  RS2_TRY(encode_device(plan, blob, plan->int_primary.as<uint8_t>(),
-                        plan->int_secondary.as<uint8_t>(), plan->pairs.as<uint8_t>(),
-                        plan->blob_id.as<uint8_t>(), st, false));
+  RS2_TRY(encode_metadata(plan, blob, plan->pairs.as<uint8_t>(), plan->blob_id.as<uint8_t>(), st));
   uint8_t bid[32];
   HIP_TRY(hipMemcpyAsync(bid, plan->blob_id.p, 32, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   if (std::memcmp(bid, blob_id, 32) != 0) return fail(RS2_E_VERIFICATION, "blob id mismatch");
   return RS2_OK;
+}
+
+// The consistency check of a blob decoded on the device (`blob_valid` bytes of it written).
+// Default, config.rs:621-640: with primary slivers, every systematic index the decoder pulled
+// from the input counts as already verified (the caller verified each sliver on receipt); with
+// secondary slivers none does.
+int check_decoded(rs2_plan* plan, int axis, const uint16_t* sliver_idx, uint32_t pulled,
+                  const uint8_t* hashes, const uint8_t* blob_id, int check, const uint8_t* blob,
+                  int64_t blob_valid, hipStream_t st) {
+  if (check == RS2_CHECK_STRICT) return strict_check(plan, blob_id, blob, st);
+  if (check != RS2_CHECK_DEFAULT) return RS2_OK;
+  std::vector<uint8_t> verified(plan->kp, 0);
+  if (axis == RS2_AXIS_PRIMARY)
+    for (uint32_t i = 0; i < pulled; ++i)
+      if (sliver_idx[i] < plan->kp) verified[sliver_idx[i]] = 1;
+  return default_check(plan, verified, hashes, blob, blob_valid, st);
 }
 
 int blob_to_host(rs2_plan* plan, uint8_t* blob_out) {
@@ -3037,26 +3057,14 @@ int rs2_decode_and_verify(rs2_plan* plan, int axis, uint32_t count, const uint16
                           const uint8_t* blob_id, int consistency_check, uint8_t* blob_out) {
   if (!plan || (!blob_out && plan->blob_len)) return fail(RS2_E_INVALID_ARGUMENT, "null argument");
   if (!hashes || !blob_id) return fail(RS2_E_INVALID_ARGUMENT, "null metadata");
-  if (consistency_check != RS2_CHECK_SKIP && consistency_check != RS2_CHECK_DEFAULT &&
-      consistency_check != RS2_CHECK_STRICT)
-    return fail(RS2_E_INVALID_ARGUMENT, "bad consistency check");
+  RS2_TRY(check_value(consistency_check));
   RingGuard ring(plan);
   uint32_t pulled = 0;
   RS2_TRY(decode_host(plan, axis, count, sliver_idx, slivers, sliver_len, sliver_symbol_size,
                       &pulled));
-  if (consistency_check == RS2_CHECK_DEFAULT) {
-    // config.rs:621-640: with primary slivers, every systematic index the decoder pulled from
-    // the input counts as already verified (the caller verified each sliver on receipt); with
-    // secondary slivers none does
-    std::vector<uint8_t> verified(plan->kp, 0);
-    if (axis == RS2_AXIS_PRIMARY)
-      for (uint32_t i = 0; i < pulled; ++i)
-        if (sliver_idx[i] < plan->kp) verified[sliver_idx[i]] = 1;
-    RS2_TRY(default_check(plan, verified, hashes, plan->dev_blob.as<uint8_t>(),
-                          int64_t(plan->kp) * plan->ks * plan->s, plan->stream));
-  } else if (consistency_check == RS2_CHECK_STRICT) {
-    RS2_TRY(strict_check(plan, blob_id, plan->dev_blob.as<uint8_t>(), plan->stream));
-  }
+  RS2_TRY(check_decoded(plan, axis, sliver_idx, pulled, hashes, blob_id, consistency_check,
+                        plan->dev_blob.as<uint8_t>(), int64_t(plan->kp) * plan->ks * plan->s,
+                        plan->stream));
   return blob_to_host(plan, blob_out);
 }
 
@@ -3068,11 +3076,8 @@ int rs2_decode_and_verify_device(rs2_plan* plan, int axis, uint32_t count,
   if (!plan || !sliver_idx || !sliver_off || !d_slivers_base || !d_blob_out)
     return fail(RS2_E_INVALID_ARGUMENT, "null argument");
   if (!hashes || !blob_id) return fail(RS2_E_INVALID_ARGUMENT, "null metadata");
-  if (axis != RS2_AXIS_PRIMARY && axis != RS2_AXIS_SECONDARY)
-    return fail(RS2_E_INVALID_ARGUMENT, "bad axis");
-  if (consistency_check != RS2_CHECK_SKIP && consistency_check != RS2_CHECK_DEFAULT &&
-      consistency_check != RS2_CHECK_STRICT)
-    return fail(RS2_E_INVALID_ARGUMENT, "bad consistency check");
+  RS2_TRY(check_axis(axis));
+  RS2_TRY(check_value(consistency_check));
   RS2_TRY(check_decode_ptrs(count, d_slivers_base, sliver_off, d_blob_out));
   HIP_TRY(hipSetDevice(plan->ctx->device));
   std::vector<std::pair<uint16_t, uint32_t>> chosen;
@@ -3081,16 +3086,9 @@ int rs2_decode_and_verify_device(rs2_plan* plan, int axis, uint32_t count,
   hipStream_t st = pick_stream(plan, stream);
   uint8_t* out = reinterpret_cast<uint8_t*>(d_blob_out);
   RS2_TRY(decode_device(plan, axis, chosen, reinterpret_cast<const uint8_t*>(d_slivers_base),
-                        sliver_off, out, st));
-  if (consistency_check == RS2_CHECK_DEFAULT) {
-    std::vector<uint8_t> verified(plan->kp, 0);  // as rs2_decode_and_verify
-    if (axis == RS2_AXIS_PRIMARY)
-      for (uint32_t i = 0; i < pulled; ++i)
-        if (sliver_idx[i] < plan->kp) verified[sliver_idx[i]] = 1;
-    RS2_TRY(default_check(plan, verified, hashes, out, int64_t(plan->blob_len), st));
-  } else if (consistency_check == RS2_CHECK_STRICT) {
-    RS2_TRY(strict_check(plan, blob_id, out, st));
-  }
+                        sliver_off, out, st, plan->blob_len));
+  RS2_TRY(check_decoded(plan, axis, sliver_idx, pulled, hashes, blob_id, consistency_check, out,
+                        int64_t(plan->blob_len), st));
   HIP_TRY(hipStreamSynchronize(st));
   return RS2_OK;
 }
@@ -3201,8 +3199,7 @@ int rs2_decode_1d(uint16_t k, uint16_t n_shards, uint16_t symbol_size, uint32_t 
 int rs2_verifier_create(uint16_t n_shards, uint16_t symbol_size, int axis, rs2_verifier** out) {
   if (!out) return fail(RS2_E_INVALID_ARGUMENT, "null verifier pointer");
   *out = nullptr;
-  if (axis != RS2_AXIS_PRIMARY && axis != RS2_AXIS_SECONDARY)
-    return fail(RS2_E_INVALID_ARGUMENT, "bad axis");
+  RS2_TRY(check_axis(axis));
   if (symbol_size == 0 || symbol_size % 2)
     return fail(RS2_E_INCOMPATIBLE_PARAMETERS, "symbol_size must be a multiple of the required alignment");
   uint16_t kp, ks;
@@ -3225,7 +3222,7 @@ void rs2_verifier_destroy(rs2_verifier* v) {
   if (!v) return;
   (void)hipSetDevice(v->ctx->device);
   if (v->stream) (void)hipStreamSynchronize(v->stream);
-  if (v->done) (void)hipEventSynchronize(v->done);  // work queued on a caller's stream
+  (void)v->done.sync();  // work queued on a caller's stream
   const Quiesced quiesced;
   delete v;
 }
@@ -3259,7 +3256,7 @@ struct VerifierLease {
     // drained before it goes back: an error return may leave the h_in -> input copy queued on
     // its stream, and the next holder rewrites h_in / grows it (PinnedBuf::ensure frees it)
     (void)hipStreamSynchronize(v->stream);
-    if (v->done) (void)hipEventSynchronize(v->done);
+    (void)v->done.sync();
     {
       std::lock_guard<std::mutex> lk(ctx->pool_mu);
       auto& free_ = ctx->verifier_pool[std::make_tuple(int(v->n), int(v->s), v->axis)];
@@ -3291,6 +3288,19 @@ uint64_t merkle_n_nodes(uint64_t n) {
   return tot + n;
 }
 
+// The repair symbols of `count` back-to-back slivers at din (n > k), on st: sliver i's n - k
+// symbols at rep + i * (n - k) * s.
+int verifier_expand(rs2_verifier* v, const uint8_t* din, uint8_t* rep, int64_t count,
+                    hipStream_t st) {
+  const int64_t n = v->n, K = v->k, s = v->s;
+  RS2_TRY(plan_encode(uint32_t(K), uint32_t(n - K), int(s), din, K * s,
+                      [&](uint32_t i) { return int64_t(i) * s; }, rep, (n - K) * s,
+                      [&](uint32_t j) { return int64_t(j) * s; }, INT64_MAX, v->job));
+  RS2_TRY(bind_job(v->ctx, v->job, v->mem, st));
+  HIP_TRY(launch_job(v->job, int(count), st));
+  return RS2_OK;
+}
+
 // The n leaf hashes (v->leaves) of `count` back-to-back slivers, on st, without an expanded
 // copy: each sliver's n - k repair symbols on the orthogonal axis go to a compact
 // [count][n - k][s] buffer (v->repair) and the leaf kernel reads its systematic symbols in place
@@ -3300,17 +3310,13 @@ int verifier_leaves(rs2_verifier* v, uint32_t count, const uint8_t* din, hipStre
   const int64_t n = v->n, K = v->k, s = v->s;
   // a previous call on another stream still owns the scratch buffers: order after it, so the
   // done event recorded at the end of this call also covers that one
-  if (v->done) HIP_TRY(hipStreamWaitEvent(st, v->done, 0));
+  HIP_TRY(v->done.wait_on(st));
   HIP_TRY(v->leaves.ensure(size_t(count) * n * 32));
   uint8_t* rep = nullptr;
   if (n > K) {
     HIP_TRY(v->repair.ensure(size_t(count) * (n - K) * s));
     rep = v->repair.as<uint8_t>();
-    RS2_TRY(plan_encode(uint32_t(K), uint32_t(n - K), int(s), din, K * s,
-                        [&](uint32_t i) { return int64_t(i) * s; }, rep, (n - K) * s,
-                        [&](uint32_t j) { return int64_t(j) * s; }, INT64_MAX, v->job));
-    RS2_TRY(bind_job(v->ctx, v->job, v->mem, st));
-    HIP_TRY(launch_job(v->job, int(count), st));
+    RS2_TRY(verifier_expand(v, din, rep, count, st));
   }
   SymbolMap map{din, rep, nullptr, int(n), int(count), int(K), int(s)};
   HIP_TRY(rs2k_launch_leaf_hash(map, 4, int64_t(count) * n, 1, v->leaves.as<uint8_t>(), st));
@@ -3319,8 +3325,15 @@ int verifier_leaves(rs2_verifier* v, uint32_t count, const uint8_t* din, hipStre
 
 // the verifier's last work on st (any caller stream): rs2_verifier_destroy waits for it
 int verifier_mark_done(rs2_verifier* v, hipStream_t st) {
-  if (!v->done) HIP_TRY(hipEventCreateWithFlags(&v->done, hipEventDisableTiming));
-  HIP_TRY(hipEventRecord(v->done, st));
+  HIP_TRY(v->done.record(st));
+  return RS2_OK;
+}
+
+// the hashing scratch for `count` slivers at once, so that no run of a window regrows it in flight
+int verifier_reserve(rs2_verifier* v, size_t count) {
+  HIP_TRY(v->leaves.ensure(count * size_t(v->n) * 32));
+  HIP_TRY(v->repair.ensure(count * size_t(v->n - v->k) * size_t(v->s)));
+  if (const size_t sb = tree_scratch_bytes(int64_t(count), v->n)) HIP_TRY(v->tree_scratch.ensure(sb));
   return RS2_OK;
 }
 
@@ -3363,12 +3376,10 @@ int validate_recovery(const rs2_verifier* v, uint32_t n_slivers, const uint32_t*
     RecoverItem it;
     it.slot = i;
     it.first = first;
-    const int rc = select_recovery_symbols(v->k, v->n, counts[i], symbol_idx + first, it.chosen);
-    if (status_out)
-      status_out[i] = rc;
-    else if (rc != RS2_OK)
-      return rc;
-    if (rc == RS2_OK) items.push_back(std::move(it));
+    bool ok;
+    RS2_TRY(slot_outcome(select_recovery_symbols(v->k, v->n, counts[i], symbol_idx + first, it.chosen),
+                         status_out, i, &ok));
+    if (ok) items.push_back(std::move(it));
   }
   return RS2_OK;
 }
@@ -3384,60 +3395,32 @@ int recover_items(rs2_verifier* v, uint32_t n_slivers, const std::vector<Recover
   const int64_t s = v->s, K = v->k;
   const size_t sliver_len = size_t(K) * size_t(s);
   // a previous call on another stream still owns the scratch buffers (verifier_mark_done)
-  if (v->done) HIP_TRY(hipStreamWaitEvent(st, v->done, 0));
+  HIP_TRY(v->done.wait_on(st));
   const bool want_roots = d_roots || expected_roots;
+  const BatchRun run{ctx, v->rbatch, v->rbatch_slot, 1, &v->prof, "rec_plan_host",
+                     g_recover_launches, g_recover_batched, g_recover_single};
   size_t next_item = 0;
   for (uint32_t w0 = 0; w0 < n_slivers; w0 += uint32_t(kBatchChunkJobs)) {
     const uint32_t w1 = uint32_t(std::min<size_t>(n_slivers, size_t(w0) + kBatchChunkJobs));
     const size_t i0 = next_item;
     while (next_item < items.size() && items[next_item].slot < w1) ++next_item;
     const size_t cnt = next_item - i0;
-    std::vector<BatchBlob> jobs(cnt);
     std::vector<DecodeSpec> specs(cnt);
-    const auto host_t0 = std::chrono::steady_clock::now();
-    if (cnt) {
-      const size_t T = std::min<size_t>(size_t(ctx->pool.threads()), cnt);
-      std::vector<std::function<void()>> tasks;
-      for (size_t t = 0; t < T; ++t)
-        tasks.emplace_back([&, t] {
-          for (size_t i = t; i < cnt; i += T) {
-            const RecoverItem& it = items[i0 + i];
-            DecodeSpec& sp = specs[i];
-            sliver_recover_spec(uint32_t(K), v->n, int(s), it.chosen, d_symbols + it.first * s,
-                                d_out + size_t(it.slot) * sliver_len, decode_may_fuse(), sp);
-            uint32_t originals = 0;
-            for (uint32_t q = 0; q < sp.K; ++q) originals += sp.present[q] >= 0;
-            if (originals < sp.K) plan_batch_spec(sp, originals, jobs[i]);
-          }
-        });
-      ctx->pool.run(tasks);
-    }
-    prof_host(&v->prof, "rec_plan_host", host_t0);
-    std::vector<BatchBlob*> ch;
-    size_t tab_bytes = 0;
-    for (size_t i = 0; i <= cnt; ++i) {
-      BatchBlob* bb = i < cnt && jobs[i].eligible ? &jobs[i] : nullptr;
-      if (bb && !ch.empty() && (bb->C != ch[0]->C || bb->job.pairs_span != ch[0]->job.pairs_span))
-        bb->eligible = false, bb = nullptr;
-      const size_t need = bb ? bb->logs.size() * kTabU16 * 2 : 0;
-      if (!ch.empty() && (i == cnt || (bb && tab_bytes + need > kBatchTableBytes))) {
-        RS2_TRY(launch_batch_chunk(ctx, v->rbatch, v->rbatch_slot, ch, 1, &v->prof, st));
-        g_recover_launches.fetch_add(1, std::memory_order_relaxed);
-        g_recover_batched.fetch_add(ch.size(), std::memory_order_relaxed);
-        ch.clear();
-        tab_bytes = 0;
-      }
-      if (bb) {
-        ch.push_back(bb);
-        tab_bytes += need;
-      }
-    }
-    for (size_t i = 0; i < cnt; ++i) {
-      if (jobs[i].eligible) continue;
-      RS2_TRY(run_decode(ctx, v->rdec, v->rdec_slot, specs[i], {}, decode_may_fuse(), 1,
-                         &v->prof, st));
-      g_recover_single.fetch_add(1, std::memory_order_relaxed);
-    }
+    RS2_TRY(run_batch_window(
+        run, cnt, st,
+        [&](size_t i, BatchBlob& bb) {
+          const RecoverItem& it = items[i0 + i];
+          DecodeSpec& sp = specs[i];
+          sliver_recover_spec(uint32_t(K), v->n, int(s), it.chosen, d_symbols + it.first * s,
+                              d_out + size_t(it.slot) * sliver_len, decode_may_fuse(), sp);
+          uint32_t originals = 0;
+          for (uint32_t q = 0; q < sp.K; ++q) originals += sp.present[q] >= 0;
+          if (originals < sp.K) plan_batch_spec(sp, originals, bb);
+        },
+        [&](size_t i) {
+          return run_decode(ctx, v->rdec, v->rdec_slot, specs[i], {}, decode_may_fuse(), 1,
+                            &v->prof, st);
+        }));
     if (!want_roots) continue;
     mark(&v->prof, "", st);
     // roots of the window's recovered slivers, in runs of neighbouring slots (a refused sliver
@@ -3447,20 +3430,15 @@ int recover_items(rs2_verifier* v, uint32_t n_slivers, const std::vector<Recover
       HIP_TRY(v->window_roots.ensure(kBatchChunkJobs * 32));
       roots = v->window_roots.as<uint8_t>();
     }
-    if (cnt) {  // the hashing scratch once, for the longest run: no run regrows it in flight
-      HIP_TRY(v->leaves.ensure(cnt * size_t(v->n) * 32));
-      HIP_TRY(v->repair.ensure(cnt * size_t(v->n - v->k) * size_t(s)));
-      if (const size_t sb = tree_scratch_bytes(int64_t(cnt), v->n))
-        HIP_TRY(v->tree_scratch.ensure(sb));
-    }
-    for (size_t a = 0; a < cnt;) {
-      size_t b = a + 1;
-      while (b < cnt && items[i0 + b].slot == items[i0 + b - 1].slot + 1) ++b;
-      const uint32_t slot = items[i0 + a].slot;
-      RS2_TRY(verifier_roots(v, uint32_t(b - a), d_out + size_t(slot) * sliver_len,
-                             roots + size_t(slot - w0) * 32, st));
-      a = b;
-    }
+    // the hashing scratch once, for the longest run: no run regrows it in flight
+    if (cnt) RS2_TRY(verifier_reserve(v, cnt));
+    RS2_TRY(for_each_run(
+        i0, next_item, [&](size_t i) { return items[i].slot; },
+        [&](size_t a, size_t b) {
+          const uint32_t slot = items[a].slot;
+          return verifier_roots(v, uint32_t(b - a), d_out + size_t(slot) * sliver_len,
+                                roots + size_t(slot - w0) * 32, st);
+        }));
     mark(&v->prof, "rec_roots", st);
     if (!expected_roots) continue;
     // expected roots and skip mask of the window through one upload slot
@@ -3478,6 +3456,7 @@ int recover_items(rs2_verifier* v, uint32_t n_slivers, const std::vector<Recover
   }
   return RS2_OK;
 }
+
 // ---------------------------------------------------------------------------------------------
 // verified decode batches: many blobs, each decoded from its own slivers and checked against its
 // own metadata, a verdict per blob in device memory
@@ -3485,12 +3464,6 @@ int recover_items(rs2_verifier* v, uint32_t n_slivers, const std::vector<Recover
 constexpr uint64_t kVerifyBatchBudget = uint64_t(256) << 20;
 std::atomic<uint64_t> g_vb_budget{kVerifyBatchBudget};
 std::atomic<uint64_t> g_vb_windows{0}, g_vb_blobs{0}, g_vb_rows{0}, g_vb_encoded{0};
-
-int check_value(int check) {
-  if (check == RS2_CHECK_SKIP || check == RS2_CHECK_DEFAULT || check == RS2_CHECK_STRICT)
-    return RS2_OK;
-  return fail(RS2_E_INVALID_ARGUMENT, "bad consistency check");
-}
 
 // Decode and check validated blobs (slot order; it.blob = the slot) of a call of n_slots slots on
 // st.  Slot b's metadata is at d_hashes + b*64n / d_ids + b*32, its verdict at d_verdict + b;
@@ -3538,7 +3511,7 @@ int verify_batch_items(rs2_plan* p, int axis, uint32_t n_slots, const std::vecto
     }
   }
   // the previous call's work (possibly on another stream) still owns the scratch
-  if (p->vb_done) HIP_TRY(hipStreamWaitEvent(st, p->vb_done, 0));
+  HIP_TRY(p->vb_done.wait_on(st));
   HIP_TRY(p->vb_slot_tab.ensure(kBatchChunkJobs * sizeof(CheckSlot)));
   rs2_verifier* v = nullptr;
   if (dflt && max_rows) {
@@ -3547,10 +3520,7 @@ int verify_batch_items(rs2_plan* p, int axis, uint32_t n_slots, const std::vecto
     HIP_TRY(p->vb_row_tab.ensure(max_rows * sizeof(CheckRow)));
     HIP_TRY(p->vb_rows.ensure(max_rows * size_t(row)));
     HIP_TRY(p->vb_roots.ensure(max_rows * 32));
-    HIP_TRY(v->leaves.ensure(max_rows * size_t(n) * 32));
-    HIP_TRY(v->repair.ensure(max_rows * size_t(n - ks) * size_t(s)));
-    if (const size_t sb = tree_scratch_bytes(int64_t(max_rows), v->n))
-      HIP_TRY(v->tree_scratch.ensure(sb));
+    RS2_TRY(verifier_reserve(v, max_rows));
   }
   if (strict && max_cnt) {
     HIP_TRY(p->vb_primary.ensure(max_cnt * size_t(n * pl)));
@@ -3607,21 +3577,19 @@ int verify_batch_items(rs2_plan* p, int axis, uint32_t n_slots, const std::vecto
       mark(p, "", st);
       const bool prof_on = p->prof.on;
       p->prof.on = false;  // one stage for the window's encodes, not encode_batch_device's own
-      int rc = RS2_OK;
       // runs of neighbouring accepted slots: a refused blob's slot is never read
-      for (size_t a = i0; a < next_item && rc == RS2_OK;) {
-        size_t b = a + 1;
-        while (b < next_item && items[b].blob == items[b - 1].blob + 1) ++b;
-        const uint32_t slot = items[a].blob;
-        std::vector<uint64_t> lens(b - a);
-        for (size_t i = a; i < b; ++i) lens[i - a] = items[i].len;
-        rc = encode_batch_device(p, uint32_t(b - a), items[a].out, int64_t(out_stride), lens.data(),
-                                 p->vb_primary.as<uint8_t>(), n * pl,
-                                 p->vb_secondary.as<uint8_t>(), n * sl, p->vb_hashes.as<uint8_t>(),
-                                 p->vb_ids.as<uint8_t>() + size_t(slot - w0) * 32, st,
-                                 p->vb_lens.as<uint64_t>() + slot);
-        a = b;
-      }
+      const int rc = for_each_run(
+          i0, next_item, [&](size_t i) { return items[i].blob; },
+          [&](size_t a, size_t b) {
+            const uint32_t slot = items[a].blob;
+            std::vector<uint64_t> lens(b - a);
+            for (size_t i = a; i < b; ++i) lens[i - a] = items[i].len;
+            return encode_batch_device(
+                p, uint32_t(b - a), items[a].out, int64_t(out_stride), lens.data(),
+                p->vb_primary.as<uint8_t>(), n * pl, p->vb_secondary.as<uint8_t>(), n * sl,
+                p->vb_hashes.as<uint8_t>(), p->vb_ids.as<uint8_t>() + size_t(slot - w0) * 32, st,
+                p->vb_lens.as<uint64_t>() + slot);
+          });
       p->prof.on = prof_on;
       RS2_TRY(rc);
       mark(p, "ver_batch_encode", st);
@@ -3646,8 +3614,7 @@ int verify_batch_items(rs2_plan* p, int axis, uint32_t n_slots, const std::vecto
     w0 = w1;
   }
   if (v) RS2_TRY(verifier_mark_done(v, st));
-  if (!p->vb_done) HIP_TRY(hipEventCreateWithFlags(&p->vb_done, hipEventDisableTiming));
-  HIP_TRY(hipEventRecord(p->vb_done, st));
+  HIP_TRY(p->vb_done.record(st));
   return RS2_OK;
 }
 
@@ -3661,6 +3628,9 @@ int check_verify_batch_args(int check, const void* hashes, const void* blob_ids,
   return RS2_OK;
 }
 
+// The host-buffer batch decode, plain (check == kNoCheck: rs2_decode_batch) or verified
+// (rs2_decode_and_verify_batch).
+constexpr int kNoCheck = -1;
 int decode_batch_host(rs2_plan* plan, int axis, uint32_t n_blobs, const uint64_t* blob_lens,
                       const uint32_t* counts, const uint16_t* sliver_idx,
                       const uint8_t* const* slivers, const uint64_t* sliver_len,
@@ -3668,16 +3638,13 @@ int decode_batch_host(rs2_plan* plan, int axis, uint32_t n_blobs, const uint64_t
                       const uint8_t* blob_ids, int check, uint8_t* const* blobs_out,
                       int32_t* verdict_out, int* status_out) {
   if (!plan) return fail(RS2_E_INVALID_ARGUMENT, "null plan");
-  if (axis != RS2_AXIS_PRIMARY && axis != RS2_AXIS_SECONDARY)
-    return fail(RS2_E_INVALID_ARGUMENT, "bad axis");
+  RS2_TRY(check_axis(axis));
   const bool verify = check != kNoCheck;
   if (verify) RS2_TRY(check_verify_batch_args(check, hashes, blob_ids, verdict_out));
-  if (n_blobs == 0) return RS2_OK;
-  if (n_blobs > 65535) return fail(RS2_E_INVALID_ARGUMENT, "more than 65535 blobs in a batch");
-  if (!counts || !blobs_out) return fail(RS2_E_INVALID_ARGUMENT, "null argument");
-  size_t total = 0;
-  for (uint32_t b = 0; b < n_blobs; ++b) total += counts[b];
-  if (total && (!sliver_idx || !slivers || !sliver_len))
+  bool empty;
+  RS2_TRY(batch_count(n_blobs, "blobs in a batch", counts && blobs_out, &empty));
+  if (empty) return RS2_OK;
+  if (std::accumulate(counts, counts + n_blobs, size_t(0)) && (!sliver_idx || !slivers || !sliver_len))
     return fail(RS2_E_INVALID_ARGUMENT, "null argument");
   HIP_TRY(hipSetDevice(plan->ctx->device));
   RingGuard ring(plan);
@@ -3705,12 +3672,9 @@ int decode_batch_host(rs2_plan* plan, int axis, uint32_t n_blobs, const uint64_t
         if (!slivers[first + c.second]) return fail(RS2_E_INVALID_ARGUMENT, "null sliver");
       return RS2_OK;
     };
-    const int rc = validate();
-    if (status_out)
-      status_out[b] = rc;
-    else if (rc != RS2_OK)
-      return rc;
-    if (rc != RS2_OK) continue;
+    bool ok;
+    RS2_TRY(slot_outcome(validate(), status_out, b, &ok));
+    if (!ok) continue;
     for (auto& c : it.chosen) c.second = uint32_t(first + c.second);  // position in `slivers`
     items.push_back(std::move(it));
   }
@@ -3802,7 +3766,7 @@ int symbol_request_windows(rs2_verifier* v, const SymbolRequestPlan& plan,
   const int64_t n = v->n, K = v->k, s = v->s, nn = int64_t(plan.n_nodes), L = plan.path_len;
   const bool build = trees == RS2_TREES_BUILD;
   // a previous call on another stream still owns the scratch buffers (verifier_leaves)
-  if (v->done) HIP_TRY(hipStreamWaitEvent(st, v->done, 0));
+  HIP_TRY(v->done.wait_on(st));
   size_t widest = 0;
   bool codec = false, runs = false;
   for (const SymbolWindow& w : plan.windows) {
@@ -3830,11 +3794,7 @@ int symbol_request_windows(rs2_verifier* v, const SymbolRequestPlan& plan,
       uint8_t* rep = nullptr;
       if (n > K) {
         rep = v->repair.as<uint8_t>() + first * (n - K) * s;
-        RS2_TRY(plan_encode(uint32_t(K), uint32_t(n - K), int(s), rin, K * s,
-                            [&](uint32_t i) { return int64_t(i) * s; }, rep, (n - K) * s,
-                            [&](uint32_t j) { return int64_t(j) * s; }, INT64_MAX, v->job));
-        RS2_TRY(bind_job(v->ctx, v->job, v->mem, st));
-        HIP_TRY(launch_job(v->job, int(cnt), st));
+        RS2_TRY(verifier_expand(v, rin, rep, cnt, st));
         expanded += uint64_t(cnt);
       }
       if (!build) continue;
@@ -3868,6 +3828,50 @@ int symbol_request_windows(rs2_verifier* v, const SymbolRequestPlan& plan,
   return RS2_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// host-buffer forms: a pooled verifier, its pinned h_in / h_out and its own stream
+// ---------------------------------------------------------------------------------------------
+// The length rule of the host-buffer forms: `count` slivers of k * s bytes each.
+int check_host_slivers(const rs2_verifier* v, uint32_t count, const uint8_t* const* slivers,
+                       const uint64_t* sliver_len) {
+  const uint64_t len = uint64_t(v->k) * v->s;
+  for (uint32_t i = 0; i < count; ++i)
+    if (!slivers[i] || sliver_len[i] != len)
+      return fail(RS2_E_INCORRECT_DATA_LENGTH, "sliver length does not match the encoder");
+  return RS2_OK;
+}
+
+// The checked slivers gathered into pinned staging and on to v->input: one DMA, not a pageable
+// copy per sliver.  (Apart from the check: a call makes all its checks before it queues work.)
+// h_out is sized for the call's out_bytes here, before any work is queued.
+int upload_host_slivers(rs2_verifier* v, uint32_t count, const uint8_t* const* slivers,
+                        size_t out_bytes) {
+  const size_t len = size_t(v->k) * v->s;
+  HIP_TRY(v->input.ensure(count * len));
+  HIP_TRY(v->h_in.ensure(count * len));
+  HIP_TRY(v->h_out.ensure(out_bytes));
+  for (uint32_t i = 0; i < count; ++i)
+    std::memcpy(static_cast<uint8_t*>(v->h_in.p) + i * len, slivers[i], len);
+  HIP_TRY(hipMemcpyAsync(v->input.p, v->h_in.p, count * len, hipMemcpyHostToDevice, v->stream));
+  return RS2_OK;
+}
+
+// Device ranges back to the host after the work queued on the verifier's stream: one D2H each
+// (none for an empty range) into h_out, which the call sized before it queued work, back to back
+// in the order given, one synchronize.
+using DevRange = std::pair<const void*, size_t>;  // device address, bytes
+int download_ranges(rs2_verifier* v, std::initializer_list<DevRange> ranges, const uint8_t** host) {
+  uint8_t* ho = static_cast<uint8_t*>(v->h_out.p);
+  size_t at = 0;
+  for (const DevRange& r : ranges) {
+    if (r.second) HIP_TRY(hipMemcpyAsync(ho + at, r.first, r.second, hipMemcpyDeviceToHost, v->stream));
+    at += r.second;
+  }
+  HIP_TRY(hipStreamSynchronize(v->stream));
+  *host = ho;
+  return RS2_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -3878,16 +3882,15 @@ int rs2_decode_and_verify_batch_device_async(
     const void* d_hashes, const void* d_blob_ids, int consistency_check, void* d_blobs_out,
     uint64_t out_stride, void* d_verdict, int* status_out, void* stream) {
   if (!plan) return fail(RS2_E_INVALID_ARGUMENT, "null plan");
-  if (axis != RS2_AXIS_PRIMARY && axis != RS2_AXIS_SECONDARY)
-    return fail(RS2_E_INVALID_ARGUMENT, "bad axis");
+  RS2_TRY(check_axis(axis));
   RS2_TRY(check_verify_batch_args(consistency_check, d_hashes, d_blob_ids, d_verdict));
   RS2_TRY(check_digest_ptr(d_hashes, "d_hashes"));
   RS2_TRY(check_digest_ptr(d_blob_ids, "d_blob_ids"));
   RS2_TRY(check_digest_ptr(d_verdict, "d_verdict"));
-  if (n_blobs == 0) return RS2_OK;
-  if (n_blobs > 65535) return fail(RS2_E_INVALID_ARGUMENT, "more than 65535 blobs in a batch");
-  if (!counts || !sliver_idx || !sliver_off || !d_slivers_base || !d_blobs_out)
-    return fail(RS2_E_INVALID_ARGUMENT, "null argument");
+  bool empty;
+  RS2_TRY(batch_count(n_blobs, "blobs in a batch",
+                      counts && sliver_idx && sliver_off && d_slivers_base && d_blobs_out, &empty));
+  if (empty) return RS2_OK;
   RS2_TRY(check_symbol_ptr(d_slivers_base, "d_slivers_base"));
   RS2_TRY(check_symbol_ptr(d_blobs_out, "d_blobs_out"));
   RS2_TRY(check_symbol_step(out_stride, "out_stride"));
@@ -3902,6 +3905,16 @@ int rs2_decode_and_verify_batch_device_async(
                             reinterpret_cast<const uint8_t*>(d_blob_ids), consistency_check,
                             reinterpret_cast<int32_t*>(d_verdict), out_stride,
                             pick_stream(plan, stream));
+}
+
+int rs2_decode_batch(rs2_plan* plan, int axis, uint32_t n_blobs, const uint64_t* blob_lens,
+                     const uint32_t* counts, const uint16_t* sliver_idx,
+                     const uint8_t* const* slivers, const uint64_t* sliver_len,
+                     const uint16_t* sliver_symbol_size, uint8_t* const* blobs_out,
+                     int* status_out) {
+  return decode_batch_host(plan, axis, n_blobs, blob_lens, counts, sliver_idx, slivers, sliver_len,
+                           sliver_symbol_size, nullptr, nullptr, kNoCheck, blobs_out, nullptr,
+                           status_out);
 }
 
 int rs2_decode_and_verify_batch(rs2_plan* plan, int axis, uint32_t n_blobs,
@@ -3923,12 +3936,7 @@ int rs2_set_verify_batch_budget(uint64_t bytes) {
 }
 
 int rs2_verify_batch_stats(uint64_t* stats_out) {
-  if (!stats_out) return fail(RS2_E_INVALID_ARGUMENT, "null argument");
-  stats_out[0] = g_vb_windows.load(std::memory_order_relaxed);
-  stats_out[1] = g_vb_blobs.load(std::memory_order_relaxed);
-  stats_out[2] = g_vb_rows.load(std::memory_order_relaxed);
-  stats_out[3] = g_vb_encoded.load(std::memory_order_relaxed);
-  return RS2_OK;
+  return read_stats(stats_out, {&g_vb_windows, &g_vb_blobs, &g_vb_rows, &g_vb_encoded});
 }
 
 int rs2_verifier_roots_device_async(rs2_verifier* v, uint32_t count, const void* d_slivers,
@@ -3950,12 +3958,11 @@ int rs2_verifier_recover_slivers_device_async(rs2_verifier* v, uint32_t n_sliver
                                               void* d_slivers_out, void* d_roots, void* d_verdict,
                                               int* status_out, void* stream) {
   if (!v) return fail(RS2_E_INVALID_ARGUMENT, "null verifier");
-  if (n_slivers == 0) return RS2_OK;
-  if (n_slivers > 65535) return fail(RS2_E_INVALID_ARGUMENT, "more than 65535 slivers in a call");
-  if (!counts || !d_slivers_out) return fail(RS2_E_INVALID_ARGUMENT, "null argument");
-  size_t total = 0;
-  for (uint32_t i = 0; i < n_slivers; ++i) total += counts[i];
-  if (total && (!symbol_idx || !d_symbols)) return fail(RS2_E_INVALID_ARGUMENT, "null argument");
+  bool empty;
+  RS2_TRY(batch_count(n_slivers, "slivers in a call", counts && d_slivers_out, &empty));
+  if (empty) return RS2_OK;
+  if (std::accumulate(counts, counts + n_slivers, size_t(0)) && (!symbol_idx || !d_symbols))
+    return fail(RS2_E_INVALID_ARGUMENT, "null argument");
   if (expected_roots ? !d_verdict : d_verdict != nullptr)
     return fail(RS2_E_INVALID_ARGUMENT, "expected_roots and d_verdict go together");
   RS2_TRY(check_symbol_ptr(d_symbols, "d_symbols"));
@@ -3980,14 +3987,13 @@ int rs2_recover_slivers(uint16_t n_shards, uint16_t symbol_size, int axis, uint3
                         const uint8_t* const* symbols, const uint8_t* expected_roots,
                         uint8_t* const* slivers_out, uint8_t* roots_out, int32_t* verdict_out,
                         int* status_out) {
-  if (n_slivers == 0) return RS2_OK;
-  if (n_slivers > 65535) return fail(RS2_E_INVALID_ARGUMENT, "more than 65535 slivers in a call");
-  if (!counts || !slivers_out) return fail(RS2_E_INVALID_ARGUMENT, "null argument");
+  bool empty;
+  RS2_TRY(batch_count(n_slivers, "slivers in a call", counts && slivers_out, &empty));
+  if (empty) return RS2_OK;
   if (expected_roots ? !verdict_out : verdict_out != nullptr)
     return fail(RS2_E_INVALID_ARGUMENT, "expected_roots and verdict_out go together");
-  size_t total = 0;
-  for (uint32_t i = 0; i < n_slivers; ++i) total += counts[i];
-  if (total && (!symbol_idx || !symbols)) return fail(RS2_E_INVALID_ARGUMENT, "null argument");
+  if (std::accumulate(counts, counts + n_slivers, size_t(0)) && (!symbol_idx || !symbols))
+    return fail(RS2_E_INVALID_ARGUMENT, "null argument");
   VerifierLease lease;
   RS2_TRY(lease.get(n_shards, symbol_size, axis));
   rs2_verifier* v = lease.v;
@@ -4030,9 +4036,8 @@ int rs2_recover_slivers(uint16_t n_shards, uint16_t symbol_size, int axis, uint3
                         st));
   RS2_TRY(verifier_mark_done(v, st));
   // one D2H of slivers, roots and verdicts; slots of refused slivers are not copied out
-  HIP_TRY(hipMemcpyAsync(v->h_out.p, dout, back_b, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  const uint8_t* ho = static_cast<const uint8_t*>(v->h_out.p);
+  const uint8_t* ho = nullptr;
+  RS2_TRY(download_ranges(v, {{dout, back_b}}, &ho));
   for (const RecoverItem& it : items) {
     std::memcpy(slivers_out[it.slot], ho + size_t(it.slot) * len, len);
     if (roots_out)
@@ -4043,11 +4048,7 @@ int rs2_recover_slivers(uint16_t n_shards, uint16_t symbol_size, int axis, uint3
 }
 
 int rs2_recover_stats(uint64_t* stats_out) {
-  if (!stats_out) return fail(RS2_E_INVALID_ARGUMENT, "null argument");
-  stats_out[0] = g_recover_launches.load(std::memory_order_relaxed);
-  stats_out[1] = g_recover_batched.load(std::memory_order_relaxed);
-  stats_out[2] = g_recover_single.load(std::memory_order_relaxed);
-  return RS2_OK;
+  return read_stats(stats_out, {&g_recover_launches, &g_recover_batched, &g_recover_single});
 }
 
 int rs2_verifier_check_recovery_symbols_device_async(rs2_verifier* v, uint32_t n_slivers,
@@ -4057,9 +4058,9 @@ int rs2_verifier_check_recovery_symbols_device_async(rs2_verifier* v, uint32_t n
                                                      const void* d_expected_roots, void* d_ok,
                                                      void* stream) {
   if (!v) return fail(RS2_E_INVALID_ARGUMENT, "null verifier");
-  if (n_slivers == 0) return RS2_OK;
-  if (n_slivers > 65535) return fail(RS2_E_INVALID_ARGUMENT, "more than 65535 slivers in a call");
-  if (!counts || !target_index) return fail(RS2_E_INVALID_ARGUMENT, "null argument");
+  bool empty;
+  RS2_TRY(batch_count(n_slivers, "slivers in a call", counts && target_index, &empty));
+  if (empty) return RS2_OK;
   const int L = merkle_path_len(v->n);
   uint64_t total = 0;
   uint32_t max_count = 0;
@@ -4082,12 +4083,11 @@ int rs2_verifier_check_recovery_symbols_device_async(rs2_verifier* v, uint32_t n
   RS2_TRY(check_digest_ptr(d_ok, "d_ok"));
   HIP_TRY(hipSetDevice(v->ctx->device));
   hipStream_t st = abi_stream(stream, v->stream);
-  if (v->done) HIP_TRY(hipStreamWaitEvent(st, v->done, 0));
+  HIP_TRY(v->done.wait_on(st));
   HIP_TRY(v->sym_digests.ensure(size_t(total) * 32));
   HIP_TRY(v->per_sliver.ensure(per.size() * 4));
   RS2_TRY(upload_pieces(v->ctx, v->per_sliver.p, per.data(), per.size() * 4, st));
-  SymbolMap map{reinterpret_cast<const uint8_t*>(d_symbols), nullptr, nullptr, 0, 0, 0, int(v->s)};
-  HIP_TRY(rs2k_launch_leaf_hash(map, 1, int64_t(total), 1, v->sym_digests.as<uint8_t>(), st));
+  HIP_TRY(hash_symbols(d_symbols, int64_t(total), int(v->s), v->sym_digests.p, st));
   HIP_TRY(rs2k_launch_recovery_proof_check(
       v->sym_digests.as<uint8_t>(), v->per_sliver.as<uint32_t>(), int(n_slivers), max_count,
       uint32_t(total), reinterpret_cast<const uint8_t*>(d_proofs), L,
@@ -4131,9 +4131,9 @@ int rs2_check_recovery_symbols(uint16_t n_shards, uint16_t symbol_size, int axis
                                                            d + prf_at, d + exp_at, d + ok_at,
                                                            nullptr));
   if (total) {
-    HIP_TRY(hipMemcpyAsync(v->h_out.p, d + ok_at, total, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    std::memcpy(ok_out, v->h_out.p, total);
+    const uint8_t* ho = nullptr;
+    RS2_TRY(download_ranges(v, {{d + ok_at, total}}, &ho));
+    std::memcpy(ok_out, ho, total);
   }
   return RS2_OK;
 }
@@ -4194,10 +4194,7 @@ int rs2_recovery_symbols(uint16_t n_shards, uint16_t symbol_size, int axis, uint
   VerifierLease lease;
   RS2_TRY(lease.get(n_shards, symbol_size, axis));
   rs2_verifier* v = lease.v;
-  const uint64_t len = uint64_t(v->k) * symbol_size;
-  for (uint32_t i = 0; i < count; ++i)
-    if (!slivers[i] || sliver_len[i] != len)
-      return fail(RS2_E_INCORRECT_DATA_LENGTH, "sliver length does not match the encoder");
+  RS2_TRY(check_host_slivers(v, count, slivers, sliver_len));
   // every argument checked before any work is queued (a target is remote input on a node)
   for (uint32_t i = 0; i < count; ++i)
     if (target_sliver_index[i] >= n_shards)  // slivers.rs check_index -> IndexTooLarge
@@ -4206,21 +4203,13 @@ int rs2_recovery_symbols(uint16_t n_shards, uint16_t symbol_size, int axis, uint
   HIP_TRY(hipSetDevice(v->ctx->device));
   const int L = merkle_path_len(n_shards);
   const size_t sym_b = size_t(count) * symbol_size, prf_b = size_t(count) * L * 32;
-  HIP_TRY(v->input.ensure(size_t(count) * len));
   HIP_TRY(v->sym_out.ensure(sym_b));
   HIP_TRY(v->proof_out.ensure(size_t(count) * std::max(L, 1) * 32));
-  HIP_TRY(v->h_in.ensure(size_t(count) * len));
-  HIP_TRY(v->h_out.ensure(sym_b + prf_b));
-  for (uint32_t i = 0; i < count; ++i)
-    std::memcpy(static_cast<uint8_t*>(v->h_in.p) + size_t(i) * len, slivers[i], len);
-  HIP_TRY(hipMemcpyAsync(v->input.p, v->h_in.p, size_t(count) * len, hipMemcpyHostToDevice,
-                         v->stream));
+  RS2_TRY(upload_host_slivers(v, count, slivers, sym_b + prf_b));
   RS2_TRY(rs2_verifier_recovery_symbols_device_async(v, count, v->input.p, target_sliver_index,
                                                      v->sym_out.p, v->proof_out.p, nullptr, nullptr));
-  uint8_t* ho = static_cast<uint8_t*>(v->h_out.p);
-  HIP_TRY(hipMemcpyAsync(ho, v->sym_out.p, sym_b, hipMemcpyDeviceToHost, v->stream));
-  if (L) HIP_TRY(hipMemcpyAsync(ho + sym_b, v->proof_out.p, prf_b, hipMemcpyDeviceToHost, v->stream));
-  HIP_TRY(hipStreamSynchronize(v->stream));
+  const uint8_t* ho = nullptr;
+  RS2_TRY(download_ranges(v, {{v->sym_out.p, sym_b}, {v->proof_out.p, prf_b}}, &ho));
   std::memcpy(symbols_out, ho, sym_b);
   if (L) std::memcpy(proofs_out, ho + sym_b, prf_b);
   return RS2_OK;
@@ -4262,16 +4251,13 @@ int rs2_recovery_symbols_multi(uint16_t n_shards, uint16_t symbol_size, int axis
                                const uint64_t* sliver_len, const uint32_t* target_counts,
                                const uint16_t* target_sliver_index, uint8_t* symbols_out,
                                uint8_t* proofs_out) {
-  if (n_slivers == 0) return RS2_OK;
-  if (n_slivers > 65535) return fail(RS2_E_INVALID_ARGUMENT, "more than 65535 slivers in a call");
-  if (!slivers || !sliver_len || !target_counts) return fail(RS2_E_INVALID_ARGUMENT, "null argument");
+  bool empty;
+  RS2_TRY(batch_count(n_slivers, "slivers in a call", slivers && sliver_len && target_counts, &empty));
+  if (empty) return RS2_OK;
   VerifierLease lease;
   RS2_TRY(lease.get(n_shards, symbol_size, axis));
   rs2_verifier* v = lease.v;
-  const uint64_t len = uint64_t(v->k) * symbol_size;
-  for (uint32_t i = 0; i < n_slivers; ++i)
-    if (!slivers[i] || sliver_len[i] != len)
-      return fail(RS2_E_INCORRECT_DATA_LENGTH, "sliver length does not match the encoder");
+  RS2_TRY(check_host_slivers(v, n_slivers, slivers, sliver_len));
   uint64_t total = 0;
   for (uint32_t i = 0; i < n_slivers; ++i) {
     total += target_counts[i];
@@ -4286,23 +4272,15 @@ int rs2_recovery_symbols_multi(uint16_t n_shards, uint16_t symbol_size, int axis
     return fail(RS2_E_INVALID_ARGUMENT, "null argument");
   if (total == 0) return RS2_OK;  // no trees to hand out: nothing to do
   HIP_TRY(hipSetDevice(v->ctx->device));
-  const size_t in_b = size_t(n_slivers) * len, sym_b = size_t(total) * symbol_size;
-  const size_t prf_b = size_t(total) * L * 32;
-  HIP_TRY(v->input.ensure(in_b));
+  const size_t sym_b = size_t(total) * symbol_size, prf_b = size_t(total) * L * 32;
   HIP_TRY(v->sym_out.ensure(sym_b));
   HIP_TRY(v->proof_out.ensure(std::max<size_t>(prf_b, 32)));
-  HIP_TRY(v->h_in.ensure(in_b));
-  HIP_TRY(v->h_out.ensure(sym_b + prf_b));
-  for (uint32_t i = 0; i < n_slivers; ++i)
-    std::memcpy(static_cast<uint8_t*>(v->h_in.p) + size_t(i) * len, slivers[i], len);
-  HIP_TRY(hipMemcpyAsync(v->input.p, v->h_in.p, in_b, hipMemcpyHostToDevice, v->stream));
+  RS2_TRY(upload_host_slivers(v, n_slivers, slivers, sym_b + prf_b));
   RS2_TRY(rs2_verifier_recovery_symbols_multi_device_async(
       v, n_slivers, v->input.p, target_counts, target_sliver_index, RS2_TREES_BUILD, nullptr,
       v->sym_out.p, v->proof_out.p, nullptr));
-  uint8_t* ho = static_cast<uint8_t*>(v->h_out.p);
-  HIP_TRY(hipMemcpyAsync(ho, v->sym_out.p, sym_b, hipMemcpyDeviceToHost, v->stream));
-  if (L) HIP_TRY(hipMemcpyAsync(ho + sym_b, v->proof_out.p, prf_b, hipMemcpyDeviceToHost, v->stream));
-  HIP_TRY(hipStreamSynchronize(v->stream));
+  const uint8_t* ho = nullptr;
+  RS2_TRY(download_ranges(v, {{v->sym_out.p, sym_b}, {v->proof_out.p, prf_b}}, &ho));
   std::memcpy(symbols_out, ho, sym_b);
   if (L) std::memcpy(proofs_out, ho + sym_b, prf_b);
   return RS2_OK;
@@ -4314,13 +4292,8 @@ int rs2_set_recovery_symbols_budget(uint64_t bytes) {
 }
 
 int rs2_recovery_symbols_stats(uint64_t* stats_out) {
-  if (!stats_out) return fail(RS2_E_INVALID_ARGUMENT, "null argument");
-  stats_out[0] = g_sym_windows.load(std::memory_order_relaxed);
-  stats_out[1] = g_sym_expanded.load(std::memory_order_relaxed);
-  stats_out[2] = g_sym_built.load(std::memory_order_relaxed);
-  stats_out[3] = g_sym_cached.load(std::memory_order_relaxed);
-  stats_out[4] = g_sym_requests.load(std::memory_order_relaxed);
-  return RS2_OK;
+  return read_stats(stats_out, {&g_sym_windows, &g_sym_expanded, &g_sym_built, &g_sym_cached,
+                                &g_sym_requests});
 }
 
 int rs2_merkle_proof_roots(uint32_t count, const uint8_t* leaves, uint32_t leaf_len,
@@ -4344,8 +4317,7 @@ int rs2_merkle_proof_roots(uint32_t count, const uint8_t* leaves, uint32_t leaf_
   HIP_TRY(hipMemcpyAsync(di.p, leaf_index, size_t(count) * 4, hipMemcpyHostToDevice, st));
   if (path_len)
     HIP_TRY(hipMemcpyAsync(dp.p, paths, size_t(count) * path_len * 32, hipMemcpyHostToDevice, st));
-  SymbolMap map{dl.as<uint8_t>(), nullptr, nullptr, 0, 0, 0, int(leaf_len)};
-  HIP_TRY(rs2k_launch_leaf_hash(map, 1, count, 1, dd.as<uint8_t>(), st));
+  HIP_TRY(hash_symbols(dl.p, count, int(leaf_len), dd.p, st));
   HIP_TRY(rs2k_launch_proof_roots(dd.as<uint8_t>(), di.as<uint32_t>(), dp.as<uint8_t>(),
                                   int(path_len), int(count), dr.as<uint8_t>(), st));
   HIP_TRY(hipMemcpyAsync(roots_out, dr.p, size_t(count) * 32, hipMemcpyDeviceToHost, st));
@@ -4361,26 +4333,15 @@ int rs2_sliver_merkle_roots(uint16_t n_shards, uint16_t symbol_size, int axis, u
   VerifierLease lease;
   RS2_TRY(lease.get(n_shards, symbol_size, axis));
   rs2_verifier* v = lease.v;
-  const uint64_t len = uint64_t(v->k) * symbol_size;
-  for (uint32_t i = 0; i < count; ++i)
-    if (!slivers[i] || sliver_len[i] != len)
-      return fail(RS2_E_INCORRECT_DATA_LENGTH, "sliver length does not match the encoder");
+  RS2_TRY(check_host_slivers(v, count, slivers, sliver_len));
   if (count == 0) return RS2_OK;
   HIP_TRY(hipSetDevice(v->ctx->device));
-  HIP_TRY(v->input.ensure(size_t(count) * len));
   HIP_TRY(v->roots.ensure(size_t(count) * 32));
-  // the slivers gathered into pinned staging: one DMA instead of one pageable copy per sliver
-  HIP_TRY(v->h_in.ensure(size_t(count) * len));
-  HIP_TRY(v->h_out.ensure(size_t(count) * 32));
-  for (uint32_t i = 0; i < count; ++i)
-    std::memcpy(static_cast<uint8_t*>(v->h_in.p) + size_t(i) * len, slivers[i], len);
-  HIP_TRY(hipMemcpyAsync(v->input.p, v->h_in.p, size_t(count) * len, hipMemcpyHostToDevice,
-                         v->stream));
+  RS2_TRY(upload_host_slivers(v, count, slivers, size_t(count) * 32));
   RS2_TRY(rs2_verifier_roots_device_async(v, count, v->input.p, v->roots.p, nullptr));
-  HIP_TRY(hipMemcpyAsync(v->h_out.p, v->roots.p, size_t(count) * 32, hipMemcpyDeviceToHost,
-                         v->stream));
-  HIP_TRY(hipStreamSynchronize(v->stream));
-  std::memcpy(roots_out, v->h_out.p, size_t(count) * 32);
+  const uint8_t* ho = nullptr;
+  RS2_TRY(download_ranges(v, {{v->roots.p, size_t(count) * 32}}, &ho));
+  std::memcpy(roots_out, ho, size_t(count) * 32);
   return RS2_OK;
 }
 
@@ -4406,8 +4367,7 @@ int rs2_merkle_root(const uint8_t* leaves, uint32_t n_leaves, uint32_t leaf_len,
   HIP_TRY(root.ensure(32));
   if (leaf_len)
     HIP_TRY(hipMemcpyAsync(din.p, leaves, size_t(n_leaves) * leaf_len, hipMemcpyHostToDevice, st));
-  SymbolMap map{din.as<uint8_t>(), nullptr, nullptr, 0, 0, 0, int(leaf_len)};
-  HIP_TRY(rs2k_launch_leaf_hash(map, 1, n_leaves, 1, digests.as<uint8_t>(), st));
+  HIP_TRY(hash_symbols(din.p, n_leaves, int(leaf_len), digests.p, st));
   RS2_TRY(device_merkle_root(digests.as<uint8_t>(), n_leaves, tmp, root.as<uint8_t>(), st));
   HIP_TRY(hipMemcpyAsync(root_out, root.p, 32, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
@@ -4438,9 +4398,8 @@ int rs2_codec_create(uint16_t k, uint16_t n_shards, uint16_t symbol_size, rs2_co
 void rs2_codec_destroy(rs2_codec* c) {
   if (!c) return;
   (void)hipSetDevice(c->ctx->device);
-  if (c->enc_done) (void)hipEventSynchronize(c->enc_done);
-  for (auto& sl : c->dec)
-    if (sl.done) (void)hipEventSynchronize(sl.done);
+  (void)c->enc_done.sync();
+  for (auto& sl : c->dec) (void)sl.done.sync();
   const Quiesced quiesced;
   delete c;
 }
@@ -4466,7 +4425,7 @@ int rs2_codec_encode_device_async(rs2_codec* c, uint32_t lines, const void* d_sr
   const uint8_t* src = reinterpret_cast<const uint8_t*>(d_src);
   uint8_t* dst = reinterpret_cast<uint8_t*>(d_repair);
   if (!std::equal(key, key + 4, c->enc_key)) {
-    if (c->enc_done) HIP_TRY(hipEventSynchronize(c->enc_done));  // old arrays may be in use
+    HIP_TRY(c->enc_done.sync());  // old arrays may be in use
     const int64_t ss = key[0], rs = key[2];
     RS2_TRY(plan_encode(uint32_t(c->k), uint32_t(c->n - c->k), int(c->s), src, key[1],
                         [&](uint32_t i) { return int64_t(i) * ss; }, dst, key[3],
@@ -4477,8 +4436,7 @@ int rs2_codec_encode_device_async(rs2_codec* c, uint32_t lines, const void* d_sr
   for (int b = 0; b < c->enc.job.n_in; ++b) c->enc.job.in[b].base = src;
   for (int o = 0; o < c->enc.job.n_out; ++o) c->enc.job.out[o].base = dst;
   HIP_TRY(launch_job(c->enc, int(lines), st));
-  if (!c->enc_done) HIP_TRY(hipEventCreateWithFlags(&c->enc_done, hipEventDisableTiming));
-  HIP_TRY(hipEventRecord(c->enc_done, st));
+  HIP_TRY(c->enc_done.record(st));
   return RS2_OK;
 }
 
@@ -4552,9 +4510,8 @@ int rs2_leaf_hashes_device_async(const void* d_symbols, uint64_t count, uint16_t
   if (count == 0) return RS2_OK;
   Context* ctx = nullptr;
   RS2_TRY(get_context(&ctx));
-  SymbolMap map{reinterpret_cast<const uint8_t*>(d_symbols), nullptr, nullptr, 0, 0, 0, int(symbol_size)};
-  HIP_TRY(rs2k_launch_leaf_hash(map, 1, int64_t(count), 1, reinterpret_cast<uint8_t*>(d_leaves),
-                                reinterpret_cast<hipStream_t>(stream)));
+  HIP_TRY(hash_symbols(d_symbols, int64_t(count), int(symbol_size), d_leaves,
+                       reinterpret_cast<hipStream_t>(stream)));
   return RS2_OK;
 }
 

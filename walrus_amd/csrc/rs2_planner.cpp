@@ -595,6 +595,31 @@ void pack_batch_job(const PlannedJob& pj, CodecJobBatch& out, std::vector<uint16
                 mix.begin() + (size_t(o) * MB + i) * row);
 }
 
+void cut_batch_chunks(const std::vector<ChunkJob>& jobs, size_t table_budget, ChunkCut& cut) {
+  cut = ChunkCut{};
+  size_t start = 0, tab_bytes = 0;  // the open chunk: members[start ..), its table bytes
+  for (uint32_t i = 0; i < jobs.size(); ++i) {
+    const ChunkJob& j = jobs[i];
+    if (!j.eligible) continue;
+    const size_t need = j.n_logs * kTabU16 * 2;
+    if (cut.members.size() > start) {
+      const ChunkJob& first = jobs[cut.members[start]];
+      if (j.C != first.C || j.pairs_span != first.pairs_span) {
+        cut.demoted.push_back(i);
+        continue;
+      }
+      if (tab_bytes + need > table_budget) {
+        cut.ends.push_back(uint32_t(cut.members.size()));
+        start = cut.members.size();
+        tab_bytes = 0;
+      }
+    }
+    cut.members.push_back(i);
+    tab_bytes += need;
+  }
+  if (cut.members.size() > start) cut.ends.push_back(uint32_t(cut.members.size()));
+}
+
 int select_recovery_symbols(uint32_t k, uint32_t n, uint32_t count, const uint16_t* idx,
                             std::vector<std::pair<uint16_t, uint32_t>>& chosen) {
   chosen.clear();

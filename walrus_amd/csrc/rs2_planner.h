@@ -285,6 +285,23 @@ bool batch_eligible(const PlannedJob& pj, bool fused);
 // none.  The caller checked batch_eligible.
 void pack_batch_job(const PlannedJob& pj, CodecJobBatch& out, std::vector<uint16_t>& mix);
 
+// What the chunk cut rule reads of a planned job of a window, and its result: chunk c is the jobs
+// members[ends[c - 1] .. ends[c]) (ends[-1] = 0), each an index into the window, in order.
+struct ChunkJob {
+  bool eligible;
+  int C;
+  int64_t pairs_span;
+  size_t n_logs;  // multiplier logs: kTabU16 * 2 table bytes each
+};
+struct ChunkCut {
+  std::vector<uint32_t> members, ends, demoted;
+};
+// Pack a window's eligible jobs into launches, in order.  A chunk's jobs share the C and
+// pairs_span of its first job (the launch geometry): a job that differs from them is demoted to
+// the per-item path and starts no chunk.  A chunk is cut before the job whose tables would take
+// it past table_budget bytes, so a job larger than the budget still forms a chunk of its own.
+void cut_batch_chunks(const std::vector<ChunkJob>& jobs, size_t table_budget, ChunkCut& cut);
+
 // ---------------------------------------------------------------------------------------------
 // sliver recovery (rs2_recover_slivers, rs2_verifier_recover_slivers_device_async): a sliver is
 // one line of a 1D code, K = its symbols, recovered from `count` received symbols
