@@ -572,6 +572,74 @@ int rs2_verifier_profile_enable(rs2_verifier* v, int enable);
 int rs2_verifier_profile_read(rs2_verifier* v, uint32_t max_stages, char* names,
                               double* total_ms, uint32_t* launches, uint32_t* n_stages);
 
+/* ---- sliver verification across blobs: a symbol size per sliver -----------------------------
+ * verify_sliver_against_metadata (walrus-service node.rs:2615-2633, called from put_sliver for
+ * every sliver a node receives) forms SliverData::get_merkle_root (slivers.rs:151-166) of one
+ * sliver and compares it with the hash in its blob's metadata.  A node holds slivers of many
+ * blobs at once, so of about as many symbol sizes, on both axes: this call takes n_slivers
+ * slivers that share only n_shards.  Sliver i is K*symbol_size[i] bytes at d_slivers_base +
+ * sliver_off[i] (K = K_s for axis[i] == RS2_AXIS_PRIMARY, K_p for RS2_AXIS_SECONDARY, as
+ * rs2_verifier_create); nothing outside these extents is read.  d_roots (may be NULL;
+ * n_slivers*32 bytes, 16-byte aligned) receives, in the caller's order, the root
+ * rs2_verifier_roots_device_async gives for that sliver on a verifier of its size and axis.
+ * expected_roots (HOST, n_slivers*32, may be NULL): the hashes from the slivers' metadata;
+ * d_verdict (n_slivers int32, 16-byte aligned, NULL exactly when expected_roots is) then gets
+ * RS2_SLIVER_MATCH / RS2_SLIVER_MISMATCH / RS2_SLIVER_SKIPPED per sliver.  Nothing but d_roots
+ * and d_verdict is written.  The call never waits for the device; the host arrays may be reused
+ * as soon as it returns.
+ * Per sliver, decided on the host before anything is enqueued: an axis that is not one of the two
+ * RS2_E_INVALID_ARGUMENT; symbol_size[i] 0 or odd RS2_E_INCOMPATIBLE_PARAMETERS; an odd
+ * sliver_off[i] RS2_E_INVALID_ARGUMENT; host form only: a NULL sliver or sliver_len[i] != K*s
+ * RS2_E_INCORRECT_DATA_LENGTH.  status_out NULL: the first failing sliver's code is returned and
+ * nothing is enqueued; non-NULL: failing slivers get their code and are skipped (root slot not
+ * written, verdict RS2_SLIVER_SKIPPED), the rest run, RS2_OK.  Whole-call refusals
+ * (RS2_E_INVALID_ARGUMENT): a NULL checker or needed array, a d_slivers_base that is not 2-byte
+ * or a d_roots / d_verdict that is not 16-byte aligned, more than 65535 slivers, d_verdict and
+ * expected_roots not NULL together.  n_slivers 0: RS2_OK, nothing enqueued.
+ *
+ * How it runs.  The slivers are grouped by (axis, symbol size) and taken, in the caller's order,
+ * in windows: a sliver of symbol size s holds n_shards*(s + 32) bytes of scratch (its gathered
+ * copy, its repair symbols, its leaves); a window closes before the sliver that would take it past
+ * the budget (rs2_set_verify_mixed_budget; at least one sliver per window), or past
+ * RS2_VERIFY_MIXED_WINDOW_GROUPS groups (what keeps a window's job table in one upload chunk), so
+ * scratch does not grow with n_slivers.  Per window: one gather puts every group's slivers back to
+ * back; one codec launch per axis present expands all its groups, a job per group found from a
+ * tile prefix array; one leaf-hash launch over a group table; one tree launch; one launch writes
+ * roots and verdicts in the caller's order.  That is at most RS2_VERIFY_MIXED_WINDOW_LAUNCHES
+ * compute launches per window, however many slivers and sizes it holds.  A group runs there iff its
+ * symbol size is >= 4, n_shards <= 4096, and its axis' encode has 1..8 transform blocks on each side
+ * (both axes of n_shards = 10 .. 4096 at the default block limit); other groups (2-byte symbols,
+ * wider trees) run through a per-size verifier on the same stream, inside the same windows.
+ * Measured (tools/verify_mixed_probe.py, MI355X, n_shards = 1000, 128 primary slivers; DESIGN.md
+ * §19): 64 symbol sizes, two slivers each: 0.65 ms against 10.3 ms for 64
+ * rs2_verifier_roots_device_async calls (15.8x); uniform at s = 1206: 0.49 ms against 0.38 ms for
+ * the one rs2_verifier_roots_device_async call (1.28x slower: its leaf kernels are tuned per size
+ * class and its codec runs pipelined), so a batch uniform in axis and size should keep that call.
+ * Stream conventions as the verifier calls; one checker per thread, or serialise its use. */
+#define RS2_VERIFY_MIXED_WINDOW_LAUNCHES 6
+#define RS2_VERIFY_MIXED_WINDOW_GROUPS 256
+typedef struct rs2_sliver_checker rs2_sliver_checker;
+int rs2_sliver_checker_create(uint16_t n_shards, rs2_sliver_checker** out);
+void rs2_sliver_checker_destroy(rs2_sliver_checker* c);
+int rs2_sliver_checker_verify_device_async(
+    rs2_sliver_checker* c, uint32_t n_slivers, const uint8_t* axis, const uint16_t* symbol_size,
+    const void* d_slivers_base, const uint64_t* sliver_off, const uint8_t* expected_roots,
+    void* d_roots, void* d_verdict, int* status_out, void* stream);
+/* Host form (blocking): slivers[i] is sliver i (sliver_len[i] bytes); roots_out (may be NULL)
+ * n_slivers*32 bytes, verdict_out n_slivers values (NULL exactly when expected_roots is).  Root
+ * slots of skipped slivers are not written. */
+int rs2_verify_slivers_mixed(uint16_t n_shards, uint32_t n_slivers, const uint8_t* axis,
+                             const uint16_t* symbol_size, const uint8_t* const* slivers,
+                             const uint64_t* sliver_len, const uint8_t* expected_roots,
+                             uint8_t* roots_out, int32_t* verdict_out, int* status_out);
+/* Window scratch of the mixed calls in bytes (default 256 MiB; 0 restores it).  Process-wide. */
+int rs2_set_verify_mixed_budget(uint64_t bytes);
+/* Process-wide counters, stats_out[5]: windows; slivers verified inside group launches; slivers
+ * that took the per-size path; groups, i.e. distinct (axis, size) pairs inside windows; compute
+ * launches of the group path (gather, codec, leaf hash, trees, roots/verdicts; table uploads and
+ * the per-size path's own launches are not counted).  No reference counterpart. */
+int rs2_verify_mixed_stats(uint64_t* stats_out);
+
 /* RecoverySymbol::verify's proof step (symbols.rs:617-642; merkle.rs:78-99,150-169) for every
  * received symbol of a recovery call, grouped and laid out as above: sliver i's counts[i]
  * symbols all authenticate leaf target_index[i] (HOST; the target sliver's index on the

@@ -26,6 +26,7 @@ from .encoding import (  # noqa: F401
     ReedSolomonDecoder,
     ReedSolomonEncoder,
     ReedSolomonEncodingConfig,
+    SliverChecker,
     SliverData,
     SliverPair,
     SliverVerifier,
@@ -36,10 +37,14 @@ from .encoding import (  # noqa: F401
     recovery_symbols_stats,
     set_recovery_symbols_budget,
     set_verify_batch_budget,
+    set_verify_mixed_budget,
     sliver_merkle_roots,
+    sliver_merkle_roots_mixed,
     source_symbols_for_n_shards,
     verify_batch_stats,
+    verify_mixed_stats,
     verify_slivers,
+    verify_slivers_of_blobs,
 )
 
 from .recovery import (  # noqa: F401

@@ -1833,6 +1833,34 @@ __global__ void __launch_bounds__(Geo<C>::THREADS, 4)
   codec_body<C, 3, false, CodecJobBatch, true>(job, tile - blob * uint32_t(tiles_per_blob));
 }
 
+// Encode over a job table with a tile range per job (mixed sliver verification,
+// rs2_sliver_checker_*): job g is a group of slivers of one symbol size -- n_lines slivers, its
+// own symbol_size, n_pairs, pairs_span, bases and position offsets -- and owns the tiles
+// [tile_first[g], tile_first[g + 1]) of the launch (XCD order over the whole grid); the tile
+// counts differ with the symbol size, so the workgroup finds its job by a search of the prefix
+// array (n_jobs + 1 entries, the last one the grid's tile count).  The search reads nothing a lane
+// owns: the index is wave-uniform, and goes through readfirstlane like codec_body's `w` so the
+// job's fields are scalar loads.  grid.z is the launch's n_out (one code per launch: every job has
+// the same blocks); a workgroup past its job's n_out leaves before any barrier or LDS use.
+template <int C, int MODE>
+__global__ void __launch_bounds__(Geo<C>::THREADS, 4)
+    rs2_encode_groups_kernel(const CodecJobBatch* __restrict__ jobs,
+                             const uint32_t* __restrict__ tile_first, int n_jobs) {
+  const uint32_t tile = xcd_tile(blockIdx.x, gridDim.x);
+  int lo = 0, hi = n_jobs - 1;  // the last g with tile_first[g] <= tile
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (tile_first[mid] <= tile)
+      lo = mid;
+    else
+      hi = mid - 1;
+  }
+  const int g = __builtin_amdgcn_readfirstlane(lo);
+  const CodecJobBatch& job = jobs[g];
+  if (int(blockIdx.z) >= job.n_out) return;
+  codec_body<C, MODE, false, CodecJobBatch, true>(job, tile - tile_first[g]);
+}
+
 }  // namespace rs2
 
 #define RS2_CAT2(a, b) a##b
@@ -1886,6 +1914,26 @@ extern "C" hipError_t RS2_CAT(rs2k_launch_decode_batch_, RS2_C)(const rs2::Codec
   const dim3 block(rs2::Geo<RS2_C>::THREADS);
   hipLaunchKernelGGL(rs2::rs2_decode_batch_kernel<RS2_C>, grid, block, 0, stream, d_jobs,
                      tiles_per_blob);
+  return hipGetLastError();
+}
+
+// Encode groups: n_jobs jobs at d_jobs, job g the tiles [d_tile_first[g], d_tile_first[g + 1]) of
+// n_tiles; mode kModeRows (grid.z = n_z = the code's n_out) or kModeCols (n_z 1)
+extern "C" hipError_t RS2_CAT(rs2k_launch_encode_groups_, RS2_C)(const rs2::CodecJobBatch* d_jobs,
+                                                                 const uint32_t* d_tile_first,
+                                                                 int n_jobs, int n_tiles, int n_z,
+                                                                 int mode, hipStream_t stream) {
+  if (n_jobs < 1 || n_tiles < n_jobs || n_z < 1 || n_z > rs2::kBatchBlocks)
+    return hipErrorInvalidValue;
+  const dim3 grid(uint32_t(n_tiles), 1, n_z), block(rs2::Geo<RS2_C>::THREADS);
+  if (mode == rs2::kModeRows)
+    hipLaunchKernelGGL((rs2::rs2_encode_groups_kernel<RS2_C, rs2::kModeRows>), grid, block, 0,
+                       stream, d_jobs, d_tile_first, n_jobs);
+  else if (mode == rs2::kModeCols && n_z == 1)
+    hipLaunchKernelGGL((rs2::rs2_encode_groups_kernel<RS2_C, rs2::kModeCols>), grid, block, 0,
+                       stream, d_jobs, d_tile_first, n_jobs);
+  else
+    return hipErrorInvalidValue;
   return hipGetLastError();
 }
 

@@ -289,6 +289,51 @@ __global__ void __launch_bounds__(256)
   }
 }
 
+// Sliver gather of a mixed verification window (rs2_sliver_checker_*): slot a's `len` bytes from
+// its own place in the caller's memory to dst + dst_off, so that a group's slivers sit back to
+// back at one stride for the codec and the leaf hash.  The slivers' lengths differ with their
+// symbol size, so a workgroup (one 4 KiB chunk of one sliver) finds its slot by a search of the
+// slots' first chunks; nothing at or past src + len is read.  Both ends are 2-byte aligned and len
+// is even: a lane moves 16 bytes as one, four or eight aligned words, by the alignment the two
+// ends share, and the sliver's last piece element by element.
+__global__ void __launch_bounds__(256)
+    sliver_gather_kernel(const SliverSlot* __restrict__ slots, int n_slots,
+                         uint8_t* __restrict__ dst) {
+  const uint32_t chunk = blockIdx.x;
+  int lo = 0, hi = n_slots - 1;  // the last slot whose chunk0 <= chunk
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (slots[mid].chunk0 <= chunk)
+      lo = mid;
+    else
+      hi = mid - 1;
+  }
+  const SliverSlot sl = slots[lo];
+  const int64_t g = (int64_t(chunk - sl.chunk0) * 256 + threadIdx.x) * 16;
+  const int64_t len = sl.len;
+  if (g >= len) return;
+  const int n = int(len - g < 16 ? len - g : 16);  // even
+  const uint8_t* sp = sl.src + g;
+  uint8_t* dp = dst + sl.dst_off + g;
+  if (n == 16) {
+    const uintptr_t al = reinterpret_cast<uintptr_t>(sp) | reinterpret_cast<uintptr_t>(dp);
+    if ((al & 15) == 0) {
+      *reinterpret_cast<uint4*>(dp) = *reinterpret_cast<const uint4*>(sp);
+    } else if ((al & 3) == 0) {
+      uint32_t v[4];
+      sfor<4>([&](auto j) { v[decltype(j)::value] = reinterpret_cast<const uint32_t*>(sp)[decltype(j)::value]; });
+      sfor<4>([&](auto j) { reinterpret_cast<uint32_t*>(dp)[decltype(j)::value] = v[decltype(j)::value]; });
+    } else {
+      uint16_t v[8];
+      sfor<8>([&](auto j) { v[decltype(j)::value] = reinterpret_cast<const uint16_t*>(sp)[decltype(j)::value]; });
+      sfor<8>([&](auto j) { reinterpret_cast<uint16_t*>(dp)[decltype(j)::value] = v[decltype(j)::value]; });
+    }
+    return;
+  }
+  for (int e = 0; e < n; e += 2)
+    *reinterpret_cast<uint16_t*>(dp + e) = *reinterpret_cast<const uint16_t*>(sp + e);
+}
+
 // Small host -> device uploads (rs2_engine.cpp UploadSlots): the kernel reads the pinned,
 // device-mapped host slot over PCIe and writes the device buffer, in stream order like any
 // launch -- no DMA-engine copy, whose cross-engine dependency on the stream's earlier kernels
@@ -488,6 +533,15 @@ hipError_t rs2k_launch_check_rows_gather(const rs2::CheckRow* d_rows, int64_t n_
     if (e != hipSuccess) return e;
   }
   return hipSuccess;
+}
+
+hipError_t rs2k_launch_sliver_gather(const rs2::SliverSlot* d_slots, int n_slots, int64_t n_chunks,
+                                     uint8_t* d_dst, hipStream_t stream) {
+  if (n_slots <= 0 || n_chunks <= 0) return hipSuccess;
+  if (n_chunks >= (int64_t(1) << 31)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(rs2::sliver_gather_kernel, dim3(unsigned(n_chunks)), dim3(256), 0, stream,
+                     d_slots, n_slots, d_dst);
+  return hipGetLastError();
 }
 
 hipError_t rs2k_launch_host_upload(const void* src, void* dst, int64_t n, uint64_t* done,

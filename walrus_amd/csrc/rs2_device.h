@@ -181,6 +181,30 @@ struct CheckSlot {
 constexpr uint32_t kCheckSkipped = 0xFFFFFFFFu;
 static_assert(sizeof(CheckRow) == 16 && sizeof(CheckSlot) == 8, "check tables are packed");
 
+// Mixed sliver verification (rs2_sliver_checker_*): one window's device tables.
+// A slot of the window (an accepted sliver, slots sorted by group): its bytes in the caller's
+// memory, where its copy goes in the window's gathered buffer (groups back to back, a group's
+// slivers back to back) and its first 4 KiB chunk of the gather launch (sliver_gather_kernel
+// searches these; the entry after the last slot holds the launch's chunk count).
+struct SliverSlot {
+  const uint8_t* src;
+  uint64_t dst_off;
+  uint32_t len;     // K * s, even
+  uint32_t chunk0;
+};
+// A group of the leaf launch (leaf_hash_groups_kernel): `count` slivers of k symbols of s bytes
+// from slot `first_slot` on, their systematic symbols back to back at sys, their n - k repair
+// symbols back to back at rep.  The table is searched by first_slot; the entry after the last
+// group holds the launch's slot count.
+struct SliverLeafGroup {
+  const uint8_t* sys;
+  const uint8_t* rep;
+  uint32_t first_slot, count, k, s;
+};
+static_assert(sizeof(SliverSlot) == 24 && sizeof(SliverLeafGroup) == 32, "sliver tables are packed");
+// caller index -> slot table entry of a sliver refused on the host (sliver_finish_kernel)
+constexpr uint32_t kSliverSkipped = 0xFFFFFFFFu;
+
 // Bulk recovery symbols (symbol_requests_kernel): where each level of a sliver's MerkleTree::nodes
 // array starts, in nodes -- a path has at most kSymbolLevels siblings for n <= 65535 leaves.  By
 // value in the launch arguments (wave-uniform, read once per wave).

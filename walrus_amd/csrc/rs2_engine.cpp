@@ -665,6 +665,7 @@ struct Context {
   std::mutex pool_mu;
   std::map<std::tuple<int, int, int>, std::vector<::rs2_verifier*>> verifier_pool;
   std::map<std::tuple<int, int, int>, std::vector<Dec1D*>> dec1d_pool;
+  std::map<int, std::vector<::rs2_sliver_checker*>> checker_pool;  // rs2_verify_slivers_mixed, by n_shards
   static constexpr size_t kPoolKeep = 8;  // idle objects kept per parameter set
 
   int init(int dev) {
@@ -1460,6 +1461,31 @@ struct rs2_verifier {
   // its buffers go back to the arena as quiesced (they may be handed out again at once)
   Event done;
   ~rs2_verifier() {
+    if (stream) (void)hipStreamDestroy(stream);
+  }
+};
+
+// Mixed sliver verification state (rs2_sliver_checker_*): bound to n_shards only; every sliver of
+// a call has its own axis and symbol size (node.rs:2615-2633 verifies what a node receives, from
+// many blobs at once).
+struct rs2_sliver_checker {
+  Context* ctx = nullptr;
+  hipStream_t stream = nullptr;
+  uint16_t n = 0;
+  // per axis: the code's template (planned once, re-planned only when the block limit changed),
+  // its job with the transform tables attached, and its mixing tables on the device
+  SliverAxisCode codes[2];
+  bool bound[2] = {false, false};
+  DevBuf mix[2];
+  // a window's scratch: gathered slivers, repair symbols, leaves, roots by slot; its tables
+  DevBuf gathered, repair, leaves, slot_roots, tables;
+  // groups the group launch cannot take run through this verifier, re-pointed per group
+  rs2_verifier* single = nullptr;
+  // host-buffer form: slivers in, roots and verdicts out
+  DevBuf input, out;
+  PinnedBuf h_in, h_out;
+  Event done;  // as rs2_verifier::done
+  ~rs2_sliver_checker() {
     if (stream) (void)hipStreamDestroy(stream);
   }
 };
@@ -4349,6 +4375,420 @@ int rs2_sliver_merkle_root(uint16_t n_shards, uint16_t symbol_size, int axis, co
                            uint64_t sliver_len, uint8_t root_out[32]) {
   if (!sliver || !root_out || symbol_size == 0) return fail(RS2_E_INVALID_ARGUMENT, "null argument");
   return rs2_sliver_merkle_roots(n_shards, symbol_size, axis, 1, &sliver, &sliver_len, root_out);
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------
+// mixed sliver verification: slivers that share only n_shards, a symbol size per sliver
+// ---------------------------------------------------------------------------------------------
+namespace {
+constexpr uint64_t kVerifyMixedBudget = uint64_t(256) << 20;
+std::atomic<uint64_t> g_vm_budget{kVerifyMixedBudget};
+std::atomic<uint64_t> g_vm_windows{0}, g_vm_grouped{0}, g_vm_single{0}, g_vm_groups{0},
+    g_vm_launches{0};
+// Groups of one window: what keeps its job table within one upload slot, so the compute launches
+// of a window (RS2_VERIFY_MIXED_WINDOW_LAUNCHES) never depend on how many sizes it holds.
+constexpr uint32_t kMixedWindowGroups = RS2_VERIFY_MIXED_WINDOW_GROUPS;
+static_assert(kMixedWindowGroups <= kBatchChunkJobs, "a window's job table outgrows an upload slot");
+
+hipError_t launch_encode_groups(int C, const CodecJobBatch* d_jobs, const uint32_t* d_tiles,
+                                int n_jobs, int n_tiles, int n_z, int mode, hipStream_t st) {
+  switch (C) {
+#define RS2_GROUPS_CASE(CC) \
+  case CC: return rs2k_launch_encode_groups_##CC(d_jobs, d_tiles, n_jobs, n_tiles, n_z, mode, st);
+    RS2_GROUPS_CASE(1)
+    RS2_GROUPS_CASE(2)
+    RS2_GROUPS_CASE(4)
+    RS2_GROUPS_CASE(8)
+    RS2_GROUPS_CASE(16)
+    RS2_GROUPS_CASE(32)
+    RS2_GROUPS_CASE(64)
+    RS2_GROUPS_CASE(128)
+    RS2_GROUPS_CASE(256)
+    RS2_GROUPS_CASE(512)
+#undef RS2_GROUPS_CASE
+    default: return hipErrorInvalidValue;
+  }
+}
+
+// The codes of both axes, planned once per checker (again only when the block limit changed):
+// host arithmetic only.
+int checker_codes(rs2_sliver_checker* c) {
+  for (int a = 0; a < 2; ++a) {
+    SliverAxisCode& code = c->codes[a];
+    if (code.n == c->n && code.block_max == block_max()) continue;
+    RS2_TRY(plan_sliver_axis(c->n, a, code));
+    c->bound[a] = false;
+  }
+  return RS2_OK;
+}
+
+// A freshly planned code's device side: its blocks get their transform tables, and its mixing
+// tables go up on st (calls on other streams are ordered behind st by the checker's `done`).
+int checker_bind(rs2_sliver_checker* c, hipStream_t st) {
+  for (int a = 0; a < 2; ++a) {
+    SliverAxisCode& code = c->codes[a];
+    if (c->bound[a] || !code.batchable) continue;
+    const PlannedJob& t = code.tmpl;
+    CodecJobBatch& j = code.job;
+    for (int b = 0; b < j.n_in; ++b) {
+      j.in[b].sd_tab = c->ctx->stream(t.C, t.in_sd[size_t(b)], t.ppw);
+      if (!j.in[b].sd_tab) return fail(RS2_E_DEVICE, "table upload failed");
+      j.in[b].zero_first = group0_zero(t.C, t.in_sd[size_t(b)], t.ppw);
+    }
+    for (int o = 0; o < j.n_out; ++o) {
+      j.out[o].sd_tab = c->ctx->stream(t.C, t.out_sd[size_t(o)], t.ppw);
+      if (!j.out[o].sd_tab) return fail(RS2_E_DEVICE, "table upload failed");
+      j.out[o].zero_first = group0_zero(t.C, t.out_sd[size_t(o)], t.ppw);
+    }
+    j.mix_tab = nullptr;
+    if (!code.mix.empty()) {
+      HIP_TRY(c->mix[a].ensure(code.mix.size() * 2));
+      RS2_TRY(upload_pieces(c->ctx, c->mix[a].p, code.mix.data(), code.mix.size() * 2, st));
+      j.mix_tab = c->mix[a].as<uint16_t>();
+    }
+    c->bound[a] = true;
+  }
+  return RS2_OK;
+}
+
+// Where a window's tables lie in the checker's table buffer (every part 16-byte aligned).
+struct MixedTables {
+  size_t slots = 0, groups = 0, jobs = 0, tiles[2] = {0, 0}, offs = 0, slot_of = 0, expected = 0,
+         bytes = 0;
+};
+MixedTables mixed_tables(const rs2_sliver_checker* c, const SliverWindow& w, bool verdicts) {
+  MixedTables t;
+  size_t at = 0;
+  auto take = [&](size_t n) {
+    const size_t here = at;
+    at += (n + 15) / 16 * 16;
+    return here;
+  };
+  const size_t ne = size_t(w.axis_groups[0]) + w.axis_groups[1];
+  t.slots = take((size_t(w.n_slots) + 1) * sizeof(SliverSlot));
+  t.groups = take((ne + 1) * sizeof(SliverLeafGroup));
+  t.jobs = take(ne * sizeof(CodecJobBatch));
+  size_t n_offs = 0;
+  for (int a = 0; a < 2; ++a) {
+    t.tiles[a] = take(w.tiles[a].size() * 4);
+    n_offs += size_t(w.axis_groups[a]) * c->codes[a].tmpl.offs.size();
+  }
+  t.offs = take(n_offs * 8);
+  t.slot_of = take(size_t(w.count) * 4);
+  t.expected = take(verdicts ? size_t(w.count) * 32 : 0);
+  t.bytes = std::max<size_t>(at, 16);
+  return t;
+}
+
+// Run a planned call on st.  src(i): the device address of the caller's sliver i (accepted ones
+// only).  expected / d_roots / d_verdict are indexed by the caller's sliver.  Every buffer is
+// sized for the call's largest window before the first window runs.
+template <class SrcF>
+int checker_run(rs2_sliver_checker* c, const SliverGroupsPlan& plan, SrcF src,
+                const uint8_t* expected, uint8_t* d_roots, int32_t* d_verdict, hipStream_t st) {
+  Context* ctx = c->ctx;
+  const int64_t n = c->n;
+  // a previous call on another stream still owns the scratch buffers and tables
+  HIP_TRY(c->done.wait_on(st));
+  if (plan.accepted) RS2_TRY(checker_bind(c, st));
+  uint64_t max_gather = 0, max_repair = 0;
+  uint32_t max_slots = 0, max_elig = 0;
+  size_t max_tab = 0;
+  for (const SliverWindow& w : plan.windows) {
+    max_gather = std::max(max_gather, w.gather_bytes);
+    max_repair = std::max(max_repair, w.repair_bytes);
+    max_slots = std::max(max_slots, w.n_slots);
+    max_elig = std::max(max_elig, w.n_eligible_slots);
+    max_tab = std::max(max_tab, mixed_tables(c, w, d_verdict != nullptr).bytes);
+  }
+  HIP_TRY(c->gathered.ensure(std::max<uint64_t>(max_gather, 16)));
+  HIP_TRY(c->repair.ensure(std::max<uint64_t>(max_repair, 16)));
+  HIP_TRY(c->leaves.ensure(std::max<size_t>(size_t(max_elig) * size_t(n) * 32, 16)));
+  HIP_TRY(c->slot_roots.ensure(std::max<size_t>(size_t(max_slots) * 32, 16)));
+  HIP_TRY(c->tables.ensure(max_tab));
+  uint8_t* const gath = c->gathered.as<uint8_t>();
+  uint8_t* const rep = c->repair.as<uint8_t>();
+  uint8_t* const d_tab = c->tables.as<uint8_t>();
+  std::vector<uint8_t> h_tab;
+  for (const SliverWindow& w : plan.windows) {
+    const MixedTables t = mixed_tables(c, w, d_verdict != nullptr);
+    h_tab.assign(t.bytes, 0);
+    // slots: where each sliver comes from and goes to, and its chunks of the gather
+    SliverSlot* slots = reinterpret_cast<SliverSlot*>(h_tab.data() + t.slots);
+    uint64_t chunks = 0;
+    for (const SliverGroup& g : w.groups) {
+      const uint64_t len = uint64_t(g.k) * g.s;
+      for (uint32_t q = 0; q < g.count; ++q) {
+        SliverSlot& sl = slots[g.first_slot + q];
+        sl.src = src(w.perm[g.first_slot + q]);
+        sl.dst_off = g.gather_off + q * len;
+        sl.len = uint32_t(len);
+        sl.chunk0 = uint32_t(chunks);
+        chunks += (len + 4095) / 4096;
+        if (chunks > 0x7FFFFFFFu) return fail(RS2_E_UNSUPPORTED, "window exceeds the launch grid");
+      }
+    }
+    slots[w.n_slots].chunk0 = uint32_t(chunks);
+    // eligible groups: leaf table, jobs, tiles, position offsets
+    SliverLeafGroup* lg = reinterpret_cast<SliverLeafGroup*>(h_tab.data() + t.groups);
+    CodecJobBatch* jobs = reinterpret_cast<CodecJobBatch*>(h_tab.data() + t.jobs);
+    int64_t* offs = reinterpret_cast<int64_t*>(h_tab.data() + t.offs);
+    const int64_t* d_offs = reinterpret_cast<const int64_t*>(d_tab + t.offs);
+    const uint32_t ne = w.axis_groups[0] + w.axis_groups[1];
+    size_t off_at = 0;
+    for (uint32_t p = 0; p < ne; ++p) {
+      const SliverGroup& g = w.groups[p];
+      const SliverAxisCode& code = c->codes[g.axis];
+      const PlannedJob& tp = code.tmpl;
+      const int64_t s = g.s, k = g.k;
+      lg[p] = {gath + g.gather_off, rep + g.repair_off, g.first_slot, g.count, g.k, g.s};
+      CodecJobBatch j = code.job;
+      j.symbol_size = int32_t(s);
+      j.n_pairs = int32_t((s + 3) / 4);
+      j.pairs_span = g.pairs_span;
+      j.n_lines = int32_t(g.count);
+      for (int b = 0; b < j.n_in; ++b) {
+        j.in[b].base = gath + g.gather_off;
+        j.in[b].line_stride = k * s;
+        j.in[b].pos_off = d_offs + off_at + tp.in_off(b);
+      }
+      for (int o = 0; o < j.n_out; ++o) {
+        j.out[o].base = rep + g.repair_off;
+        j.out[o].line_stride = (n - k) * s;
+        j.out[o].pos_off = d_offs + off_at + tp.out_off(o);
+      }
+      jobs[p] = j;
+      for (size_t q = 0; q < tp.offs.size(); ++q)
+        offs[off_at + q] = tp.offs[q] < 0 ? int64_t(-1) : tp.offs[q] * s;
+      off_at += tp.offs.size();
+    }
+    lg[ne].first_slot = w.n_eligible_slots;
+    for (int a = 0; a < 2; ++a)
+      std::memcpy(h_tab.data() + t.tiles[a], w.tiles[a].data(), w.tiles[a].size() * 4);
+    uint32_t* slot_of = reinterpret_cast<uint32_t*>(h_tab.data() + t.slot_of);
+    std::fill(slot_of, slot_of + w.count, kSliverSkipped);
+    for (uint32_t sl = 0; sl < w.n_slots; ++sl) slot_of[w.perm[sl] - w.first] = sl;
+    if (d_verdict)
+      std::memcpy(h_tab.data() + t.expected, expected + size_t(w.first) * 32, size_t(w.count) * 32);
+    RS2_TRY(upload_pieces(ctx, d_tab, h_tab.data(), t.bytes, st));
+    uint64_t launches = 0;
+    if (w.n_slots) {
+      HIP_TRY(rs2k_launch_sliver_gather(reinterpret_cast<const SliverSlot*>(d_tab + t.slots),
+                                        int(w.n_slots), int64_t(chunks), gath, st));
+      ++launches;
+    }
+    for (int a = 0; a < 2; ++a) {
+      if (!w.axis_groups[a]) continue;
+      const PlannedJob& tp = c->codes[a].tmpl;
+      HIP_TRY(launch_encode_groups(
+          tp.C, reinterpret_cast<const CodecJobBatch*>(d_tab + t.jobs) + w.axis_first[a],
+          reinterpret_cast<const uint32_t*>(d_tab + t.tiles[a]), int(w.axis_groups[a]),
+          int(w.tiles[a].back()), tp.n_z, tp.mode, st));
+      ++launches;
+    }
+    if (w.n_eligible_slots) {
+      HIP_TRY(rs2k_launch_leaf_hash_groups(reinterpret_cast<const SliverLeafGroup*>(d_tab + t.groups),
+                                           int(ne), int(w.n_eligible_slots), int(n),
+                                           c->leaves.as<uint8_t>(), st));
+      HIP_TRY(rs2k_launch_merkle_trees(c->leaves.as<uint8_t>(), int(n), int(w.n_eligible_slots), 0,
+                                       n * 32, 32, 0, 0, c->slot_roots.as<uint8_t>(), 32, st));
+      launches += 2;
+    }
+    // the other groups: the per-size path on the same stream, from their gathered copies
+    for (size_t p = ne; p < w.groups.size(); ++p) {
+      const SliverGroup& g = w.groups[p];
+      rs2_verifier* v = c->single;
+      v->s = uint16_t(g.s);
+      v->k = uint16_t(g.k);
+      v->axis = g.axis;
+      RS2_TRY(verifier_roots(v, g.count, gath + g.gather_off,
+                             c->slot_roots.as<uint8_t>() + size_t(g.first_slot) * 32, st));
+      RS2_TRY(verifier_mark_done(v, st));
+    }
+    if (d_roots || d_verdict) {
+      HIP_TRY(rs2k_launch_sliver_finish(
+          c->slot_roots.as<uint8_t>(), reinterpret_cast<const uint32_t*>(d_tab + t.slot_of),
+          int(w.count), d_verdict ? d_tab + t.expected : nullptr,
+          d_roots ? d_roots + size_t(w.first) * 32 : nullptr,
+          d_verdict ? d_verdict + w.first : nullptr, st));
+      ++launches;
+    }
+    g_vm_windows.fetch_add(1, std::memory_order_relaxed);
+    g_vm_grouped.fetch_add(w.n_eligible_slots, std::memory_order_relaxed);
+    g_vm_single.fetch_add(w.n_slots - w.n_eligible_slots, std::memory_order_relaxed);
+    g_vm_groups.fetch_add(w.groups.size(), std::memory_order_relaxed);
+    g_vm_launches.fetch_add(launches, std::memory_order_relaxed);
+  }
+  HIP_TRY(c->done.record(st));
+  return RS2_OK;
+}
+
+// The whole-call rules both forms share; *empty: nothing to do (RS2_OK).
+int check_mixed_call(uint32_t n_slivers, bool arrays, const void* expected, const void* verdict,
+                     bool* empty) {
+  RS2_TRY(batch_count(n_slivers, "slivers in a call", arrays, empty));
+  if (*empty) return RS2_OK;
+  if (expected ? !verdict : verdict != nullptr)
+    return fail(RS2_E_INVALID_ARGUMENT, "expected_roots and the verdicts go together");
+  return RS2_OK;
+}
+
+// A pooled checker for one host-buffer call (Context::checker_pool), as VerifierLease.
+struct CheckerLease {
+  Context* ctx = nullptr;
+  rs2_sliver_checker* c = nullptr;
+  CheckerLease() = default;
+  CheckerLease(const CheckerLease&) = delete;
+  CheckerLease& operator=(const CheckerLease&) = delete;
+  int get(uint16_t n_shards) {
+    RS2_TRY(get_context(&ctx));
+    {
+      std::lock_guard<std::mutex> lk(ctx->pool_mu);
+      auto& free_ = ctx->checker_pool[int(n_shards)];
+      if (!free_.empty()) {
+        c = free_.back();
+        free_.pop_back();
+        return RS2_OK;
+      }
+    }
+    return rs2_sliver_checker_create(n_shards, &c);
+  }
+  ~CheckerLease() {
+    if (!c) return;
+    (void)hipStreamSynchronize(c->stream);
+    (void)c->done.sync();
+    {
+      std::lock_guard<std::mutex> lk(ctx->pool_mu);
+      auto& free_ = ctx->checker_pool[int(c->n)];
+      if (free_.size() < Context::kPoolKeep) {
+        free_.push_back(c);
+        return;
+      }
+    }
+    rs2_sliver_checker_destroy(c);
+  }
+};
+}  // namespace
+
+extern "C" {
+
+int rs2_sliver_checker_create(uint16_t n_shards, rs2_sliver_checker** out) {
+  if (!out) return fail(RS2_E_INVALID_ARGUMENT, "null checker pointer");
+  *out = nullptr;
+  uint16_t kp, ks;
+  RS2_TRY(rs2_source_symbols_for_n_shards(n_shards, &kp, &ks));
+  if (n_shards > kMaxShards) return fail(RS2_E_UNSUPPORTED, "n_shards above 65535");
+  Context* ctx = nullptr;
+  RS2_TRY(get_context(&ctx));
+  auto c = std::make_unique<rs2_sliver_checker>();
+  c->ctx = ctx;
+  c->n = n_shards;
+  HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+  // the per-size path's verifier, re-pointed at each group it runs
+  RS2_TRY(rs2_verifier_create(n_shards, 2, RS2_AXIS_PRIMARY, &c->single));
+  *out = c.release();
+  return RS2_OK;
+}
+
+void rs2_sliver_checker_destroy(rs2_sliver_checker* c) {
+  if (!c) return;
+  (void)hipSetDevice(c->ctx->device);
+  if (c->stream) (void)hipStreamSynchronize(c->stream);
+  (void)c->done.sync();  // work queued on a caller's stream
+  if (c->single) rs2_verifier_destroy(c->single);
+  const Quiesced quiesced;
+  delete c;
+}
+
+int rs2_sliver_checker_verify_device_async(rs2_sliver_checker* c, uint32_t n_slivers,
+                                           const uint8_t* axis, const uint16_t* symbol_size,
+                                           const void* d_slivers_base, const uint64_t* sliver_off,
+                                           const uint8_t* expected_roots, void* d_roots,
+                                           void* d_verdict, int* status_out, void* stream) {
+  if (!c) return fail(RS2_E_INVALID_ARGUMENT, "null checker");
+  bool empty;
+  RS2_TRY(check_mixed_call(n_slivers, axis && symbol_size && d_slivers_base && sliver_off,
+                           expected_roots, d_verdict, &empty));
+  if (empty) return RS2_OK;
+  RS2_TRY(check_symbol_ptr(d_slivers_base, "d_slivers_base"));
+  RS2_TRY(check_digest_ptr(d_roots, "d_roots"));
+  RS2_TRY(check_digest_ptr(d_verdict, "d_verdict"));
+  HIP_TRY(hipSetDevice(c->ctx->device));
+  hipStream_t st = abi_stream(stream, c->stream);
+  // every sliver is validated, and the call planned, before anything is enqueued
+  RS2_TRY(checker_codes(c));
+  SliverGroupsPlan plan;
+  RS2_TRY(plan_sliver_groups(c->codes, n_slivers, axis, symbol_size, sliver_off, nullptr, nullptr,
+                             g_vm_budget.load(std::memory_order_relaxed), kMixedWindowGroups,
+                             status_out, plan));
+  const uint8_t* base = reinterpret_cast<const uint8_t*>(d_slivers_base);
+  return checker_run(c, plan, [&](uint32_t i) { return base + sliver_off[i]; }, expected_roots,
+                     reinterpret_cast<uint8_t*>(d_roots), reinterpret_cast<int32_t*>(d_verdict), st);
+}
+
+int rs2_verify_slivers_mixed(uint16_t n_shards, uint32_t n_slivers, const uint8_t* axis,
+                             const uint16_t* symbol_size, const uint8_t* const* slivers,
+                             const uint64_t* sliver_len, const uint8_t* expected_roots,
+                             uint8_t* roots_out, int32_t* verdict_out, int* status_out) {
+  bool empty;
+  RS2_TRY(check_mixed_call(n_slivers, axis && symbol_size && slivers && sliver_len, expected_roots,
+                           verdict_out, &empty));
+  if (empty) return RS2_OK;
+  CheckerLease lease;
+  RS2_TRY(lease.get(n_shards));
+  rs2_sliver_checker* c = lease.c;
+  HIP_TRY(hipSetDevice(c->ctx->device));
+  hipStream_t st = c->stream;
+  RS2_TRY(checker_codes(c));
+  SliverGroupsPlan plan;
+  RS2_TRY(plan_sliver_groups(c->codes, n_slivers, axis, symbol_size, nullptr, slivers, sliver_len,
+                             g_vm_budget.load(std::memory_order_relaxed), kMixedWindowGroups,
+                             status_out, plan));
+  // the accepted slivers back to back through pinned staging: one H2D
+  std::vector<uint64_t> off(n_slivers, 0);
+  std::vector<uint8_t> accepted(n_slivers, 0);
+  uint64_t in_b = 0;
+  for (const SliverWindow& w : plan.windows)
+    for (uint32_t i : w.perm) accepted[i] = 1;
+  for (uint32_t i = 0; i < n_slivers; ++i) {
+    if (!accepted[i]) continue;
+    off[i] = in_b;
+    in_b += sliver_len[i];
+  }
+  const size_t roots_b = size_t(n_slivers) * 32, back_b = roots_b + size_t(n_slivers) * 4;
+  HIP_TRY(c->input.ensure(std::max<uint64_t>(in_b, 16)));
+  HIP_TRY(c->h_in.ensure(std::max<uint64_t>(in_b, 16)));
+  HIP_TRY(c->out.ensure(back_b));
+  HIP_TRY(c->h_out.ensure(back_b));
+  for (uint32_t i = 0; i < n_slivers; ++i)
+    if (accepted[i])
+      std::memcpy(static_cast<uint8_t*>(c->h_in.p) + off[i], slivers[i], sliver_len[i]);
+  if (in_b) HIP_TRY(hipMemcpyAsync(c->input.p, c->h_in.p, in_b, hipMemcpyHostToDevice, st));
+  uint8_t* dout = c->out.as<uint8_t>();
+  const uint8_t* din = c->input.as<uint8_t>();
+  RS2_TRY(checker_run(c, plan, [&](uint32_t i) { return din + off[i]; }, expected_roots, dout,
+                      expected_roots ? reinterpret_cast<int32_t*>(dout + roots_b) : nullptr, st));
+  HIP_TRY(hipMemcpyAsync(c->h_out.p, dout, back_b, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  const uint8_t* ho = static_cast<const uint8_t*>(c->h_out.p);
+  // root slots of refused slivers are not written
+  if (roots_out)
+    for (uint32_t i = 0; i < n_slivers; ++i)
+      if (accepted[i]) std::memcpy(roots_out + size_t(i) * 32, ho + size_t(i) * 32, 32);
+  if (verdict_out) std::memcpy(verdict_out, ho + roots_b, size_t(n_slivers) * 4);
+  return RS2_OK;
+}
+
+int rs2_set_verify_mixed_budget(uint64_t bytes) {
+  g_vm_budget.store(bytes ? bytes : kVerifyMixedBudget, std::memory_order_relaxed);
+  return RS2_OK;
+}
+
+int rs2_verify_mixed_stats(uint64_t* stats_out) {
+  return read_stats(stats_out,
+                    {&g_vm_windows, &g_vm_grouped, &g_vm_single, &g_vm_groups, &g_vm_launches});
 }
 
 int rs2_merkle_root(const uint8_t* leaves, uint32_t n_leaves, uint32_t leaf_len, uint8_t root_out[32]) {

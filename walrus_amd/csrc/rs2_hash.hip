@@ -1120,6 +1120,121 @@ __global__ void __launch_bounds__(64)
   verdict[i] = diff == 0 ? 1 : 0;
 }
 
+// Leaf hashes over a group table (mixed sliver verification, rs2_sliver_checker_*): the slots of
+// a window are slivers of differing symbol sizes, sorted by group.  grid (ceil(n / 256), slots):
+// the workgroup finds its slot's group by a search of the groups' first slots (block-uniform),
+// and lane c hashes leaf (slot, c) = Blake2b-256(0x00 || symbol) with the group's own s -- the
+// symbol read from the group's systematic run for c < k, from its repair run for c >= k -- into
+// out + (slot * n + c) * 32.  The symbol size is a run-time value: the message is walked in
+// 128-byte blocks, each built from the 33 aligned dwords that cover it (one alignbyte per message
+// word, as leaf_hash_small_kernel).  No dword is loaded from below the run's 4-byte-aligned start
+// or, whole, from past the run's end (bytewise there); dwords past the symbol's own end are not
+// loaded at all, and what a covering dword holds of the neighbouring symbol is masked off.
+__global__ void __launch_bounds__(256)
+    leaf_hash_groups_kernel(const SliverLeafGroup* __restrict__ groups, int n_groups, int n,
+                            uint8_t* __restrict__ out) {
+  const uint32_t slot = blockIdx.y;
+  int glo = 0, ghi = n_groups - 1;  // the last group whose first_slot <= slot
+  while (glo < ghi) {
+    const int mid = (glo + ghi + 1) >> 1;
+    if (groups[mid].first_slot <= slot)
+      glo = mid;
+    else
+      ghi = mid - 1;
+  }
+  const SliverLeafGroup gr = groups[glo];
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= n) return;
+  const int64_t s = gr.s, k = gr.k, row = int64_t(slot) - gr.first_slot;
+  const uint8_t* run;
+  int64_t run_len, at;
+  if (c < k) {
+    run = gr.sys;
+    run_len = int64_t(gr.count) * k * s;
+    at = (row * k + c) * s;
+  } else {
+    run = gr.rep;
+    run_len = int64_t(gr.count) * (n - k) * s;
+    at = (row * (n - k) + (c - k)) * s;
+  }
+  const uintptr_t r0 = reinterpret_cast<uintptr_t>(run);
+  const uintptr_t floor_ = r0 & ~uintptr_t(3), end = r0 + uintptr_t(run_len);
+  const uintptr_t a = r0 + uintptr_t(at), sym_end = a + uintptr_t(s);
+  auto dword_at = [&](uintptr_t p) -> uint32_t {
+    if (p < floor_ || p >= sym_end) return 0u;
+    if (p + 4 <= end) return *reinterpret_cast<const uint32_t*>(p);
+    uint32_t v = 0;
+    for (int b = 0; b < 3; ++b)
+      if (p + b < end) v |= uint32_t(*reinterpret_cast<const uint8_t*>(p + b)) << (8 * b);
+    return v;
+  };
+  const int64_t lm = s + 1;
+  uint64_t h[8];
+  b2_init(h);
+#pragma clang loop unroll(disable)
+  for (int64_t b0 = 0; b0 < lm; b0 += 128) {
+    // message bytes [b0, b0 + 128) are the bytes from a + b0 - 1 on (byte 0: the leaf prefix)
+    const uintptr_t p = a + uintptr_t(b0) - 1;
+    const uintptr_t P0 = p & ~uintptr_t(3);
+    const uint32_t sh = uint32_t(p & 3);
+    uint32_t E[33];
+    sfor<33>([&](auto jj) {
+      constexpr int j = decltype(jj)::value;
+      E[j] = dword_at(P0 + 4 * j);
+    });
+    uint64_t m[16];
+    sfor<16>([&](auto ii) {
+      constexpr int i = decltype(ii)::value;
+      uint32_t w[2];
+      sfor<2>([&](auto qq) {
+        constexpr int t = 2 * i + decltype(qq)::value;
+        uint32_t x = __builtin_amdgcn_alignbyte(E[t + 1], E[t], sh);
+        if (t == 0 && b0 == 0) x &= 0xFFFFFF00u;
+        const int64_t keep = lm - b0 - 4 * t;
+        if (keep < 4) x = keep <= 0 ? 0u : (x & ((1u << (8 * int(keep))) - 1u));
+        w[decltype(qq)::value] = x;
+      });
+      m[i] = uint64_t(w[0]) | (uint64_t(w[1]) << 32);
+    });
+    const bool last = b0 + 128 >= lm;
+    b2_compress(h, m, uint64_t(last ? lm : b0 + 128), last);
+  }
+  uint4* o = reinterpret_cast<uint4*>(out + (int64_t(slot) * n + c) * 32);
+  o[0] = make_uint4(uint32_t(h[0]), uint32_t(h[0] >> 32), uint32_t(h[1]), uint32_t(h[1] >> 32));
+  o[1] = make_uint4(uint32_t(h[2]), uint32_t(h[2] >> 32), uint32_t(h[3]), uint32_t(h[3] >> 32));
+}
+
+// Roots and verdicts of a mixed verification window in the caller's order: entry i of the window
+// was refused on the host (slot_of[i] == kSliverSkipped: RS2_SLIVER_SKIPPED, its root slot is
+// not written) or is slot slot_of[i] of the window, whose root (slot_roots + 32 slot) is copied
+// to roots + 32 i (roots may be null) and compared with expected + 32 i (expected and verdict are
+// null together: no verdicts).
+__global__ void __launch_bounds__(64)
+    sliver_finish_kernel(const uint8_t* __restrict__ slot_roots, const uint32_t* __restrict__ slot_of,
+                         int count, const uint8_t* __restrict__ expected,
+                         uint8_t* __restrict__ roots, int32_t* __restrict__ verdict) {
+  const int i = blockIdx.x * 64 + threadIdx.x;
+  if (i >= count) return;
+  const uint32_t slot = slot_of[i];
+  if (slot == kSliverSkipped) {
+    if (verdict) verdict[i] = 2;
+    return;
+  }
+  const uint4* a = reinterpret_cast<const uint4*>(slot_roots + int64_t(slot) * 32);
+  const uint4 r0 = a[0], r1 = a[1];
+  if (roots) {
+    uint4* o = reinterpret_cast<uint4*>(roots + int64_t(i) * 32);
+    o[0] = r0;
+    o[1] = r1;
+  }
+  if (!verdict) return;
+  const uint4* b = reinterpret_cast<const uint4*>(expected + int64_t(i) * 32);
+  const uint4 e0 = b[0], e1 = b[1];
+  const uint32_t diff = (r0.x ^ e0.x) | (r0.y ^ e0.y) | (r0.z ^ e0.z) | (r0.w ^ e0.w) |
+                        (r1.x ^ e1.x) | (r1.y ^ e1.y) | (r1.z ^ e1.z) | (r1.w ^ e1.w);
+  verdict[i] = diff == 0 ? 1 : 0;
+}
+
 // Verdicts of one window of a verified decode batch (rs2_decode_and_verify_batch_*), a wave per
 // slot of the window.  A slot refused on the host (slots[b].rows == kCheckSkipped) is
 // RS2_BLOB_SKIPPED and nothing of it is read.  Default (strict == 0): the slot's rows
@@ -1466,6 +1581,25 @@ hipError_t rs2k_launch_sliver_verdict(const uint8_t* d_roots, const uint8_t* d_e
   if (count <= 0) return hipSuccess;
   hipLaunchKernelGGL(rs2::sliver_verdict_kernel, dim3(unsigned((count + 63) / 64)), dim3(64), 0,
                      stream, d_roots, d_expected, d_skipped, count, d_verdict);
+  return hipGetLastError();
+}
+
+hipError_t rs2k_launch_leaf_hash_groups(const rs2::SliverLeafGroup* d_groups, int n_groups,
+                                        int n_slots, int n, uint8_t* d_leaves, hipStream_t stream) {
+  if (n_slots <= 0) return hipSuccess;
+  if (n_groups < 1 || n_groups > n_slots || n_slots > 65535 || n < 1) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(rs2::leaf_hash_groups_kernel, dim3(unsigned((n + 255) / 256), unsigned(n_slots)),
+                     dim3(256), 0, stream, d_groups, n_groups, n, d_leaves);
+  return hipGetLastError();
+}
+
+hipError_t rs2k_launch_sliver_finish(const uint8_t* d_slot_roots, const uint32_t* d_slot_of,
+                                     int count, const uint8_t* d_expected, uint8_t* d_roots,
+                                     int32_t* d_verdict, hipStream_t stream) {
+  if (count <= 0 || (!d_roots && !d_verdict)) return hipSuccess;
+  if ((d_verdict == nullptr) != (d_expected == nullptr)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(rs2::sliver_finish_kernel, dim3(unsigned((count + 63) / 64)), dim3(64), 0,
+                     stream, d_slot_roots, d_slot_of, count, d_expected, d_roots, d_verdict);
   return hipGetLastError();
 }
 

@@ -39,6 +39,34 @@ RS2_DECL_BATCH(128)
 RS2_DECL_BATCH(256)
 RS2_DECL_BATCH(512)
 #undef RS2_DECL_BATCH
+// encode groups of a mixed sliver verification (rs2_encode_groups_kernel): a tile range per job
+#define RS2_DECL_GROUPS(CC)                                                                    \
+  hipError_t rs2k_launch_encode_groups_##CC(const rs2::CodecJobBatch* d_jobs,                 \
+                                            const uint32_t* d_tile_first, int n_jobs,         \
+                                            int n_tiles, int n_z, int mode, hipStream_t stream);
+RS2_DECL_GROUPS(1)
+RS2_DECL_GROUPS(2)
+RS2_DECL_GROUPS(4)
+RS2_DECL_GROUPS(8)
+RS2_DECL_GROUPS(16)
+RS2_DECL_GROUPS(32)
+RS2_DECL_GROUPS(64)
+RS2_DECL_GROUPS(128)
+RS2_DECL_GROUPS(256)
+RS2_DECL_GROUPS(512)
+#undef RS2_DECL_GROUPS
+// mixed sliver verification, one window: the slots' slivers gathered (d_slots: n_slots + 1
+// SliverSlot, the last one's chunk0 the launch's chunks), the eligible slots' leaves (d_groups:
+// n_groups + 1 SliverLeafGroup, leaf (slot, c) at d_leaves + (slot * n + c) * 32), and the roots
+// and verdicts of the window's `count` caller entries (d_slot_of[i]: slot or kSliverSkipped;
+// d_roots / d_expected / d_verdict at the window's first entry, each may be null)
+hipError_t rs2k_launch_sliver_gather(const rs2::SliverSlot* d_slots, int n_slots, int64_t n_chunks,
+                                     uint8_t* d_dst, hipStream_t stream);
+hipError_t rs2k_launch_leaf_hash_groups(const rs2::SliverLeafGroup* d_groups, int n_groups,
+                                        int n_slots, int n, uint8_t* d_leaves, hipStream_t stream);
+hipError_t rs2k_launch_sliver_finish(const uint8_t* d_slot_roots, const uint32_t* d_slot_of,
+                                     int count, const uint8_t* d_expected, uint8_t* d_roots,
+                                     int32_t* d_verdict, hipStream_t stream);
 hipError_t rs2k_launch_leaf_hash(rs2::SymbolMap map, int mode, int64_t count, int n_blobs,
                                  uint8_t* d_out, hipStream_t stream);
 hipError_t rs2k_launch_merkle_trees(const uint8_t* d_leaves, int n, int n_row_trees,

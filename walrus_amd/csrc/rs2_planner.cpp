@@ -764,4 +764,168 @@ int plan_symbol_requests(uint32_t n, uint32_t k, uint32_t s, uint32_t n_slivers,
   return RS2_OK;
 }
 
+int plan_sliver_axis(uint32_t n_shards, int axis, SliverAxisCode& code) {
+  code = SliverAxisCode{};
+  if (axis != RS2_AXIS_PRIMARY && axis != RS2_AXIS_SECONDARY)
+    return fail(RS2_E_INVALID_ARGUMENT, "bad axis");
+  if (n_shards == 0 || n_shards > 65535) return fail(RS2_E_INVALID_ARGUMENT, "n_shards must be non-zero");
+  const uint32_t f = (n_shards - 1) / 3;
+  code.n = n_shards;
+  code.k = axis == RS2_AXIS_PRIMARY ? n_shards - f : n_shards - 2 * f;
+  code.block_max = block_max();
+  if (code.k >= n_shards || !rate_supported(code.k, n_shards - code.k)) return RS2_OK;
+  auto unit = [](uint32_t i) { return int64_t(i); };
+  if (plan_encode(code.k, n_shards - code.k, 2, nullptr, 0, unit, nullptr, 0, unit, INT64_MAX,
+                  code.tmpl) != RS2_OK)
+    return RS2_OK;
+  code.planned = true;
+  const CodecJobBig& j = code.tmpl.job;
+  code.batchable = j.n_in >= 1 && j.n_out >= 1 && j.n_in <= kBatchBlocks &&
+                   j.n_out <= kBatchBlocks && n_shards <= kGroupMaxLeaves;
+  if (code.batchable) pack_batch_job(code.tmpl, code.job, code.mix);
+  return RS2_OK;
+}
+
+int32_t sliver_pairs_span(int32_t n_pairs, int64_t max_ls) {
+  if (64 * max_ls + 65536 >= (int64_t(1) << 31)) return (n_pairs + 63) & ~63;
+  return (n_pairs + 1) & ~1;
+}
+
+namespace {
+// Close a window of a mixed call: order its groups (eligible primary, eligible secondary, the
+// rest), give the slivers their slots and the groups their tiles and buffer offsets.
+// idx / grp: the window's accepted slivers in the caller's order and their group (as opened).
+void close_sliver_window(const SliverAxisCode (&codes)[2], SliverWindow& w,
+                         const std::vector<uint32_t>& idx, const std::vector<uint32_t>& grp) {
+  std::vector<SliverGroup>& gs = w.groups;
+  const uint32_t ng = uint32_t(gs.size());
+  // tiles: eligibility may still fall to the 2^31 bound of an axis' launch
+  uint64_t tiles_sum[2] = {0, 0};
+  for (SliverGroup& g : gs) {
+    if (!g.eligible) continue;
+    const int64_t k = g.k, r = int64_t(codes[g.axis].n) - k;
+    g.pairs_span = sliver_pairs_span(int32_t((g.s + 3) / 4), std::max(k, r) * int64_t(g.s));
+    const uint64_t t = (uint64_t(g.count) * uint64_t(g.pairs_span) + 63) / 64;
+    if (tiles_sum[g.axis] + t > 0x7FFFFFFFu) {
+      g.eligible = false;
+      continue;
+    }
+    tiles_sum[g.axis] += t;
+  }
+  auto cls = [](const SliverGroup& g) { return g.eligible ? int(g.axis) : 2; };
+  std::vector<uint32_t> order(ng), place(ng);
+  for (uint32_t i = 0; i < ng; ++i) order[i] = i;
+  std::stable_sort(order.begin(), order.end(),
+                   [&](uint32_t a, uint32_t b) { return cls(gs[a]) < cls(gs[b]); });
+  std::vector<SliverGroup> sorted(ng);
+  uint32_t slot = 0;
+  w.tiles[0].assign(1, 0);
+  w.tiles[1].assign(1, 0);
+  w.axis_first[0] = w.axis_first[1] = w.axis_groups[0] = w.axis_groups[1] = 0;
+  w.gather_bytes = w.repair_bytes = 0;
+  w.n_eligible_slots = 0;
+  for (uint32_t p = 0; p < ng; ++p) {
+    SliverGroup g = gs[order[p]];
+    place[order[p]] = p;
+    g.first_slot = slot;
+    slot += g.count;
+    g.gather_off = w.gather_bytes;
+    w.gather_bytes += uint64_t(g.count) * g.k * g.s;
+    if (g.eligible) {
+      const uint32_t a = g.axis;
+      if (w.axis_groups[a]++ == 0) w.axis_first[a] = p;
+      g.first_tile = w.tiles[a].back();
+      w.tiles[a].push_back(g.first_tile +
+                           uint32_t((uint64_t(g.count) * uint64_t(g.pairs_span) + 63) / 64));
+      g.repair_off = w.repair_bytes;
+      w.repair_bytes += uint64_t(g.count) * (codes[a].n - g.k) * g.s;
+      w.n_eligible_slots = slot;
+    }
+    sorted[p] = g;
+  }
+  gs = std::move(sorted);
+  w.n_slots = slot;
+  w.perm.assign(slot, 0);
+  std::vector<uint32_t> next(ng);
+  for (uint32_t p = 0; p < ng; ++p) next[p] = gs[p].first_slot;
+  for (size_t i = 0; i < idx.size(); ++i) w.perm[next[place[grp[i]]]++] = idx[i];
+}
+}  // namespace
+
+int plan_sliver_groups(const SliverAxisCode (&codes)[2], uint32_t n_slivers, const uint8_t* axis,
+                       const uint16_t* symbol_size, const uint64_t* sliver_off,
+                       const uint8_t* const* slivers, const uint64_t* sliver_len, uint64_t budget,
+                       uint32_t max_groups, int* status_out, SliverGroupsPlan& plan) {
+  plan = SliverGroupsPlan{};
+  if (n_slivers > 65535) return fail(RS2_E_INVALID_ARGUMENT, "more than 65535 slivers in a call");
+  if (max_groups == 0 || codes[0].n == 0 || codes[0].n != codes[1].n)
+    return fail(RS2_E_INVALID_ARGUMENT, "not a sliver's code");
+  if (n_slivers == 0) return RS2_OK;
+  if (!axis || !symbol_size || (!sliver_off && !(slivers && sliver_len)))
+    return fail(RS2_E_INVALID_ARGUMENT, "null argument");
+  const uint32_t n = codes[0].n;
+  auto check = [&](uint32_t i) -> int {
+    if (axis[i] != RS2_AXIS_PRIMARY && axis[i] != RS2_AXIS_SECONDARY)
+      return fail(RS2_E_INVALID_ARGUMENT, "bad axis");
+    const uint32_t s = symbol_size[i];
+    if (s == 0 || s % 2)
+      return fail(RS2_E_INCOMPATIBLE_PARAMETERS, "symbol_size must be a multiple of the required alignment");
+    if (sliver_off && sliver_off[i] % 2)
+      return fail(RS2_E_INVALID_ARGUMENT, "sliver_off[i] must be a multiple of 2 bytes");
+    if (!sliver_off && (!slivers[i] || sliver_len[i] != uint64_t(codes[axis[i]].k) * s))
+      return fail(RS2_E_INCORRECT_DATA_LENGTH, "sliver length does not match its axis and symbol size");
+    return RS2_OK;
+  };
+  std::vector<uint8_t> ok(n_slivers, 0);
+  for (uint32_t i = 0; i < n_slivers; ++i) {
+    const int rc = check(i);
+    if (status_out) status_out[i] = rc;
+    else if (rc != RS2_OK) return rc;
+    ok[i] = rc == RS2_OK;
+    plan.accepted += ok[i];
+  }
+  SliverWindow w;
+  std::vector<uint32_t> idx, grp;
+  std::map<uint32_t, uint32_t> open;  // axis << 16 | s -> group of the open window
+  uint64_t used = 0;
+  auto close = [&](uint32_t end) {
+    w.count = end - w.first;
+    close_sliver_window(codes, w, idx, grp);
+    plan.windows.push_back(std::move(w));
+    w = SliverWindow{};
+    w.first = end;
+    idx.clear();
+    grp.clear();
+    open.clear();
+    used = 0;
+  };
+  for (uint32_t i = 0; i < n_slivers; ++i) {
+    if (!ok[i]) continue;  // a refused sliver holds nothing: it stays in the open window
+    const uint32_t s = symbol_size[i], key = uint32_t(axis[i]) << 16 | s;
+    const uint64_t need = sliver_scratch_bytes(n, s);
+    auto it = open.find(key);
+    // (need > budget - used, not used + need > budget: the sum may wrap)
+    if (i > w.first && !idx.empty() &&
+        (used > budget || need > budget - used || (it == open.end() && open.size() == max_groups))) {
+      close(i);
+      it = open.end();
+    }
+    if (it == open.end()) {
+      SliverGroup g;
+      g.k = codes[axis[i]].k;
+      g.s = s;
+      g.axis = axis[i];
+      g.eligible = s >= 4 && codes[axis[i]].batchable;
+      it = open.emplace(key, uint32_t(w.groups.size())).first;
+      w.groups.push_back(g);
+    }
+    ++w.groups[it->second].count;
+    idx.push_back(i);
+    grp.push_back(it->second);
+    used += need;
+  }
+  close(n_slivers);
+  return RS2_OK;
+}
+
 }  // namespace rs2

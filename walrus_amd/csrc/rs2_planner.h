@@ -397,4 +397,92 @@ int plan_symbol_requests(uint32_t n, uint32_t k, uint32_t s, uint32_t n_slivers,
                          const uint32_t* target_counts, const uint16_t* targets, int trees,
                          bool have_nodes, uint64_t budget, SymbolRequestPlan& plan);
 
+// ---------------------------------------------------------------------------------------------
+// mixed sliver verification (rs2_sliver_checker_verify_device_async): slivers that share only
+// n_shards, each with its own axis and symbol size, grouped by (axis, symbol size) and taken in
+// windows of bounded scratch
+// ---------------------------------------------------------------------------------------------
+// The 1D code a sliver of one axis expands with (a primary sliver: K_s -> n, a secondary one:
+// K_p -> n), planned once: everything of plan_encode that depends on (K, R) only -- the blocks,
+// their skew offsets, the mixing kinds and tables.  tmpl.offs holds symbol indices (the offsets
+// of a unit symbol size), so a group's position offsets are those times its s.
+struct SliverAxisCode {
+  uint32_t n = 0, k = 0;
+  uint32_t block_max = 0;         // block_max() the template was planned under
+  bool planned = false;           // plan_encode accepted the code (n > k, rate supported)
+  // the group launch can run it: at least one and at most kBatchBlocks input and output blocks,
+  // and trees of at most kGroupMaxLeaves leaves
+  bool batchable = false;
+  PlannedJob tmpl;
+  CodecJobBatch job{};            // tmpl narrowed (pack_batch_job); pointers and s-fields unset
+  std::vector<uint16_t> mix;      // mixing tables in rows of kBatchBlocks, or empty
+};
+constexpr uint32_t kGroupMaxLeaves = 4096;  // rs2_hash.hip kMerkleMax: trees without scratch
+// RS2_E_INVALID_ARGUMENT for an axis that is not one of the two or an n_shards without a code;
+// a code plan_encode refuses leaves planned = false (its groups take the per-size path, which
+// reports the refusal).
+int plan_sliver_axis(uint32_t n_shards, int axis, SliverAxisCode& code);
+
+// pairs_span of a job of n_pairs pairs per symbol whose largest line stride is max_ls bytes
+// (finish_plan's rule)
+int32_t sliver_pairs_span(int32_t n_pairs, int64_t max_ls);
+
+// Scratch bytes a sliver of symbol size s holds in a window: its gathered copy (K * s), its
+// repair symbols ((n - K) * s) and its leaves (n * 32).
+inline uint64_t sliver_scratch_bytes(uint32_t n, uint32_t s) { return uint64_t(n) * (uint64_t(s) + 32); }
+
+// ELIGIBILITY.  A group (axis, s) runs inside the window's group launches iff
+//   s >= 4 (whole-dword symbol I/O, as the decode batch), and
+//   its axis' code is batchable (1 .. kBatchBlocks input and output blocks at the current block
+//   limit, n_shards <= kGroupMaxLeaves, n_shards > K), and
+//   the codec tiles of its axis' launch stay below 2^31.
+// Every other group (s = 2, n_shards above 4096, K = n_shards) goes through a per-size verifier
+// on the same stream.
+struct SliverGroup {
+  uint32_t first_slot = 0, count = 0;  // its slots of the window
+  uint32_t k = 0, s = 0;
+  uint8_t axis = 0;
+  bool eligible = false;
+  uint32_t first_tile = 0;             // eligible: its first tile of its axis' codec launch
+  int32_t pairs_span = 0;              // eligible: lanes per line of its codec job
+  uint64_t gather_off = 0;             // its first sliver in the window's gathered buffer
+  uint64_t repair_off = 0;             // eligible: its first repair run in the repair buffer
+};
+
+// One window: the caller's slivers first .. first + count.  Accepted slivers get slots
+// 0 .. n_slots, sorted stably by group; the groups are ordered eligible primary, eligible
+// secondary, then ineligible ones, each class in the order of first appearance, so the eligible
+// slots are 0 .. n_eligible_slots and an axis' jobs are neighbours in the group table.
+struct SliverWindow {
+  uint32_t first = 0, count = 0;
+  uint32_t n_slots = 0, n_eligible_slots = 0;
+  std::vector<SliverGroup> groups;
+  uint32_t axis_first[2] = {0, 0};     // eligible groups of an axis: groups[axis_first ..
+  uint32_t axis_groups[2] = {0, 0};    //   + axis_groups)
+  // per axis: first tile of each of its eligible groups, then the launch's tile count (what the
+  // codec kernel searches); tiles[a][g + 1] - tiles[a][g] = ceil(count * pairs_span / 64)
+  std::vector<uint32_t> tiles[2];
+  std::vector<uint32_t> perm;          // slot -> caller index
+  uint64_t gather_bytes = 0, repair_bytes = 0;  // of all slots / of the eligible ones
+};
+
+struct SliverGroupsPlan {
+  std::vector<SliverWindow> windows;
+  uint32_t accepted = 0;
+};
+
+// Validate and plan a mixed call.  Per sliver, in this order: an axis that is not one of the two
+// RS2_E_INVALID_ARGUMENT; a symbol size of 0 or odd RS2_E_INCOMPATIBLE_PARAMETERS; device form
+// (sliver_off given) an odd offset RS2_E_INVALID_ARGUMENT; host form (slivers and sliver_len given)
+// a null sliver or sliver_len[i] != K * s RS2_E_INCORRECT_DATA_LENGTH.  status_out null: the first
+// failing sliver's code is returned; else every sliver's code is stored and refused slivers get no
+// slot.  Windows: slivers are taken in the caller's order; a window closes before the sliver that
+// would take its scratch (sliver_scratch_bytes summed) past `budget`, or its groups past
+// max_groups, and always holds at least one sliver.  More than 65535 slivers, null arrays or
+// max_groups 0: RS2_E_INVALID_ARGUMENT.
+int plan_sliver_groups(const SliverAxisCode (&codes)[2], uint32_t n_slivers, const uint8_t* axis,
+                       const uint16_t* symbol_size, const uint64_t* sliver_off,
+                       const uint8_t* const* slivers, const uint64_t* sliver_len, uint64_t budget,
+                       uint32_t max_groups, int* status_out, SliverGroupsPlan& plan);
+
 }  // namespace rs2

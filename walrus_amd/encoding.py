@@ -820,6 +820,129 @@ def verify_slivers(config: "ReedSolomonEncodingConfig", metadata: BlobMetadata,
     return result
 
 
+def _mixed_call(n_shards: int, slivers: Sequence[SliverData],
+                expected: Optional[bytes]) -> Tuple[List[bytes], Optional[List[int]]]:
+    """rs2_verify_slivers_mixed over host slivers: (roots, verdicts or None)."""
+    m = len(slivers)
+    keep = [np.frombuffer(s.symbols.data, dtype=np.uint8) for s in slivers]
+    axes = np.array([_AXIS[s.axis] for s in slivers], dtype=np.uint8)
+    sizes = np.array([s.symbol_size for s in slivers], dtype=np.uint16)
+    ptrs = (ctypes.c_void_p * m)(*[a.ctypes.data for a in keep])
+    lens = (ctypes.c_uint64 * m)(*[len(a) for a in keep])
+    roots = np.zeros(32 * m, dtype=np.uint8)
+    verdict = np.zeros(m, dtype=np.int32) if expected is not None else None
+    exp = np.frombuffer(bytes(expected), dtype=np.uint8) if expected is not None else None
+    _ok(_lib.lib().rs2_verify_slivers_mixed(
+        n_shards, m, axes.ctypes.data, sizes.ctypes.data_as(ctypes.POINTER(ctypes.c_uint16)), ptrs,
+        lens, exp.ctypes.data if exp is not None else None, roots.ctypes.data,
+        verdict.ctypes.data if verdict is not None else None, None))
+    raw = roots.tobytes()
+    return ([raw[32 * i:32 * i + 32] for i in range(m)],
+            [int(v) for v in verdict] if verdict is not None else None)
+
+
+def sliver_merkle_roots_mixed(config: "ReedSolomonEncodingConfig",
+                              slivers: Sequence[SliverData]) -> List[bytes]:
+    """SliverData::get_merkle_root (slivers.rs:387-392) for slivers that share only n_shards --
+    any mix of axes and symbol sizes -- in one device call (rs2_verify_slivers_mixed)."""
+    slivers = list(slivers)
+    if not slivers:
+        return []
+    return _mixed_call(config.n_shards, slivers, None)[0]
+
+
+def verify_slivers_of_blobs(config: "ReedSolomonEncodingConfig",
+                            blobs: Sequence[Tuple[BlobMetadata, Sequence[SliverData]]]
+                            ) -> List[List[bool]]:
+    """SliverData::verify (slivers.rs:100-121; node.rs:2615-2633 on every received sliver) for
+    slivers of many blobs in one device call: per blob, True where the sliver's Merkle root
+    matches the hash in that blob's metadata.  Raises as `verify_slivers` does."""
+    n = config.n_shards
+    blobs = [(metadata, list(slivers)) for metadata, slivers in blobs]
+    flat: List[SliverData] = []
+    expected = bytearray()
+    for metadata, slivers in blobs:
+        s = config.symbol_size_for_blob(metadata.unencoded_length)
+        for sl in slivers:
+            if sl.index >= len(metadata.hashes):
+                raise ValueError("IndexTooLarge")
+            k = config.n_secondary_source_symbols if sl.axis == PRIMARY else \
+                config.n_primary_source_symbols
+            if len(sl) != k * s:
+                raise ValueError("SliverSizeMismatch")
+            if sl.symbol_size != s:
+                raise ValueError("SymbolSizeMismatch")
+            pair = metadata.hashes[sl.pair_index(n)]
+            expected += bytes(pair[0] if sl.axis == PRIMARY else pair[1])
+            flat.append(sl)
+    verdicts = _mixed_call(n, flat, bytes(expected))[1] if flat else []
+    out: List[List[bool]] = []
+    at = 0
+    for _, slivers in blobs:
+        cnt = len(slivers)
+        out.append([v == _lib.RS2_SLIVER_MATCH for v in verdicts[at:at + cnt]])
+        at += cnt
+    return out
+
+
+def verify_mixed_stats() -> Dict[str, int]:
+    """rs2_verify_mixed_stats: windows of the mixed sliver verification calls, slivers verified
+    inside group launches, slivers that took the per-size path, groups (distinct axis / symbol
+    size pairs inside windows) and compute launches of the group path (process-wide)."""
+    out = (ctypes.c_uint64 * 5)()
+    _ok(_lib.lib().rs2_verify_mixed_stats(out))
+    return dict(zip(("windows", "grouped", "single", "groups", "launches"),
+                    (int(v) for v in out)))
+
+
+def set_verify_mixed_budget(nbytes: int = 0) -> None:
+    """rs2_set_verify_mixed_budget: scratch a window of a mixed sliver verification may hold
+    (0 restores the 256 MiB default)."""
+    _ok(_lib.lib().rs2_set_verify_mixed_budget(int(nbytes)))
+
+
+class SliverChecker:
+    """Device-resident sliver verification across blobs (rs2_sliver_checker_*): bound to n_shards
+    only; every sliver of a call has its own axis, symbol size and place in device memory."""
+
+    def __init__(self, n_shards: int):
+        self.handle = ctypes.c_void_p()
+        _ok(_lib.lib().rs2_sliver_checker_create(n_shards, ctypes.byref(self.handle)))
+
+    def verify_async(self, axes: Sequence[str], symbol_sizes: Sequence[int], d_base: int,
+                     offsets: Sequence[int], expected_roots: Optional[bytes] = None,
+                     d_roots: int = 0, d_verdict: int = 0, stream: Optional[int] = None,
+                     statuses: bool = False):
+        """rs2_sliver_checker_verify_device_async: sliver i (axes[i], symbol_sizes[i]) lies at
+        d_base + offsets[i]; its root goes to d_roots + 32 i and, with expected_roots, its
+        RS2_SLIVER_* verdict to d_verdict + 4 i.  With `statuses` the per-sliver codes are
+        returned and failing slivers skipped; without, the status code of the call is returned
+        (the first failure, nothing enqueued)."""
+        m = len(axes)
+        ax = np.array([_AXIS.get(a, a) for a in axes] + [0], dtype=np.uint8)
+        sz = np.array(list(symbol_sizes) + [0], dtype=np.uint16)
+        off = np.array(list(offsets) + [0], dtype=np.uint64)
+        exp = None
+        if expected_roots is not None:
+            exp = np.frombuffer(bytes(expected_roots) or b"\0", dtype=np.uint8)
+        st = (ctypes.c_int * max(m, 1))() if statuses else None
+        rc = _lib.lib().rs2_sliver_checker_verify_device_async(
+            self.handle, m, ax.ctypes.data, sz.ctypes.data_as(ctypes.POINTER(ctypes.c_uint16)),
+            d_base or None, off.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)),
+            exp.ctypes.data if exp is not None else None, d_roots or None, d_verdict or None, st,
+            _stream(stream))
+        if statuses:
+            _ok(rc)
+            return list(st)[:m]
+        return rc
+
+    def __del__(self):
+        h = getattr(self, "handle", None)
+        if h and h.value and _lib._LIB is not None:
+            _lib.lib().rs2_sliver_checker_destroy(h)
+            self.handle = ctypes.c_void_p()
+
+
 class SliverVerifier:
     """Device-resident batched sliver verification (rs2_verifier_*): Merkle roots of `count`
     back-to-back device slivers of one axis into a device buffer."""
