@@ -640,6 +640,89 @@ int rs2_set_verify_mixed_budget(uint64_t bytes);
  * the per-size path's own launches are not counted).  No reference counterpart. */
 int rs2_verify_mixed_stats(uint64_t* stats_out);
 
+/* ---- sliver recovery across blobs: a symbol size and an axis per sliver ----------------------
+ * rs2_verifier_recover_slivers_device_async for slivers that share only n_shards: a node that
+ * missed blobs, or takes over a shard at an epoch change, recovers one sliver per blob and axis,
+ * so of about as many symbol sizes as blobs.  Sliver i (axis[i], symbol_size[i]; K = K_s / K_p as
+ * above) is recovered from counts[i] received symbols whose DecodingSymbol indices are
+ * consecutive in symbol_idx (HOST) and whose data lie back to back at d_symbols_base +
+ * symbols_off[i]; it is written whole (K*symbol_size[i] bytes) at d_slivers_base + sliver_off[i].
+ * For every accepted sliver these bytes, its root at d_roots + 32 i and its verdict at
+ * d_verdict + i are bit for bit what rs2_verifier_recover_slivers_device_async writes for that
+ * sliver alone on a verifier of (n_shards, symbol_size[i], axis[i]).  Nothing outside the slivers'
+ * extents, d_roots and d_verdict is written; the symbol buffer is not written.  OUTPUT SLIVERS
+ * MUST NOT OVERLAP EACH OTHER OR THE SYMBOLS.  expected_roots / d_roots / d_verdict as the
+ * verifier call's; with d_roots and expected_roots both NULL nothing is hashed.
+ * Per sliver, decided on the host before anything is enqueued, in this order: an axis that is
+ * not one of the two RS2_E_INVALID_ARGUMENT; symbol_size[i] 0 or odd
+ * RS2_E_INCOMPATIBLE_PARAMETERS; an odd symbols_off[i] or sliver_off[i] RS2_E_INVALID_ARGUMENT;
+ * counts[i] < K RS2_E_DECODING_UNSUCCESSFUL; then rs2_decode_1d's rules
+ * (RS2_E_NOT_ENOUGH_SHARDS).  status_out NULL: the first failing sliver's code is returned and
+ * nothing is enqueued; non-NULL: failing slivers get their code and are skipped (output and root
+ * slot not written, verdict RS2_SLIVER_SKIPPED), the rest run, RS2_OK.  Whole-call refusals,
+ * alignment (bases 2-byte; d_roots and d_verdict 16-byte), the 65535 cap, n_slivers 0 and the
+ * stream conventions as rs2_sliver_checker_verify_device_async.  The host arrays may be reused as
+ * soon as the call returns.  The call does not wait for the device, except that a window's third
+ * decode launch waits for the slot of its first (a window has at most two range launches unless
+ * its multiplier tables pass 256 MiB, plus one launch per sliver on the per-sliver path).
+ *
+ * How it runs.  The slivers are taken in the caller's order in the windows of the mixed
+ * verification (same scratch rule and budget, rs2_set_verify_mixed_budget; at most
+ * RS2_VERIFY_MIXED_WINDOW_GROUPS groups and a few hundred slivers).  Per window every sliver's
+ * decode is planned on the host pool; the slivers whose decode fits a batch job leave in range
+ * launches -- a job per sliver with its own symbol size, found from a tile prefix array, one
+ * launch per block size present (at most two: one per axis) -- and the others (every original
+ * received, a 2-byte symbol, more than 8 transform blocks) are decoded on their own on the same
+ * stream.  Then the recovered slivers, in place, are the sources of one window of the mixed
+ * verification above: gather, group codec launches, leaf hashes, trees, roots and verdicts.
+ * That half counts in rs2_verify_mixed_stats exactly as a rs2_sliver_checker_verify_device_async
+ * call over the accepted slivers would; rs2_recover_stats is not touched.
+ * Measured (tools/recover_mixed_probe.py, MI355X, n_shards = 1000, 128 slivers, each from a random
+ * K-subset of its recovery symbols): 64 symbol sizes over 4 .. 300 alternating
+ * between the axes, two slivers each: 4.02 ms (3.90 - 4.16; the call returns after 1.8 ms) against
+ * 18.62 ms (18.60 - 18.69) for 64 rs2_verifier_recover_slivers_device_async calls, 4.6x; uniform,
+ * primary, s = 1206: 4.44 ms (4.38 - 4.51) against 4.31 ms (4.24 - 4.34) for the one verifier
+ * call, 3 % slower, so a batch uniform in axis and size should keep that call. */
+int rs2_sliver_checker_recover_device_async(
+    rs2_sliver_checker* c, uint32_t n_slivers, const uint8_t* axis, const uint16_t* symbol_size,
+    const uint32_t* counts, const uint16_t* symbol_idx, const void* d_symbols_base,
+    const uint64_t* symbols_off, const uint8_t* expected_roots, void* d_slivers_base,
+    const uint64_t* sliver_off, void* d_roots, void* d_verdict, int* status_out, void* stream);
+/* Host form (blocking): symbols[] holds one pointer per received symbol (symbol_size[i] bytes
+ * each for sliver i's), concatenated like symbol_idx; slivers_out[i] receives sliver i; roots_out
+ * and verdict_out as rs2_recover_slivers.  Slots of skipped slivers are not written, except
+ * verdict_out. */
+int rs2_recover_slivers_mixed(uint16_t n_shards, uint32_t n_slivers, const uint8_t* axis,
+                              const uint16_t* symbol_size, const uint32_t* counts,
+                              const uint16_t* symbol_idx, const uint8_t* const* symbols,
+                              const uint8_t* expected_roots, uint8_t* const* slivers_out,
+                              uint8_t* roots_out, int32_t* verdict_out, int* status_out);
+/* Process-wide counters of the mixed recovery calls, stats_out[5]: windows; decode range
+ * launches; slivers decoded inside them; slivers that took the per-sliver decode path; groups,
+ * i.e. distinct (axis, size) pairs inside windows.  No reference counterpart. */
+int rs2_recover_mixed_stats(uint64_t* stats_out);
+
+/* rs2_verifier_check_recovery_symbols_device_async with a symbol size and a byte offset per
+ * sliver: sliver i's counts[i] received symbols of symbol_size[i] bytes lie back to back at
+ * d_symbols_base + symbols_off[i] (2-byte aligned) and all authenticate leaf target_index[i] of
+ * their own source sliver's tree.  Proofs, expected roots and d_ok are indexed by the symbol's
+ * position j in the concatenated list, as there.  No axis is needed: a source sliver's tree has
+ * n_shards leaves on either axis.  Whole-call refusals before anything is enqueued: a target
+ * index >= n_shards, an odd offset or misaligned pointer RS2_E_INVALID_ARGUMENT; a symbol size of
+ * 0 or odd RS2_E_INCOMPATIBLE_PARAMETERS.  Only d_ok is written. */
+int rs2_sliver_checker_check_recovery_symbols_device_async(
+    rs2_sliver_checker* c, uint32_t n_slivers, const uint16_t* symbol_size, const uint32_t* counts,
+    const uint16_t* target_index, const void* d_symbols_base, const uint64_t* symbols_off,
+    const void* d_proofs, const void* d_expected_roots, void* d_ok, void* stream);
+/* Host form (blocking): symbols[] holds one pointer per received symbol; proofs and
+ * expected_roots are contiguous host arrays laid out as the device form's, ok_out one byte per
+ * symbol. */
+int rs2_check_recovery_symbols_mixed(uint16_t n_shards, uint32_t n_slivers,
+                                     const uint16_t* symbol_size, const uint32_t* counts,
+                                     const uint16_t* target_index, const uint8_t* const* symbols,
+                                     const uint8_t* proofs, const uint8_t* expected_roots,
+                                     uint8_t* ok_out);
+
 /* RecoverySymbol::verify's proof step (symbols.rs:617-642; merkle.rs:78-99,150-169) for every
  * received symbol of a recovery call, grouped and laid out as above: sliver i's counts[i]
  * symbols all authenticate leaf target_index[i] (HOST; the target sliver's index on the

@@ -34,6 +34,7 @@ from .encoding import (  # noqa: F401
     VerificationError,
     VerifiedBlobMetadataWithId,
     compute_symbol_size,
+    recover_mixed_stats,
     recovery_symbols_stats,
     set_recovery_symbols_budget,
     set_verify_batch_budget,
@@ -53,12 +54,14 @@ from .recovery import (  # noqa: F401
     MerkleProof,
     RecoverySymbol,
     recover_sliver_or_generate_inconsistency_proof,
+    recover_slivers_of_blobs,
     recover_slivers_or_generate_inconsistency_proofs,
     recovery_symbol_for_sliver,
     recovery_symbols_for_requests,
     recovery_symbols_for_targets,
     try_recover_sliver_from_decoding_symbols,
     verify_recovery_symbols,
+    verify_recovery_symbols_of_blobs,
 )
 
 build_library = _lib.build_library

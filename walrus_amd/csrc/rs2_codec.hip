@@ -1861,6 +1861,31 @@ __global__ void __launch_bounds__(Geo<C>::THREADS, 4)
   codec_body<C, MODE, false, CodecJobBatch, true>(job, tile - tile_first[g]);
 }
 
+// Decode over a job table with a tile range per job (mixed sliver recovery,
+// rs2_sliver_checker_recover_device_async): the decode counterpart of rs2_encode_groups_kernel.
+// Job g is one sliver -- its own symbol_size, n_pairs, pairs_span, erasure pattern, blocks and
+// tables -- and owns the tiles [tile_first[g], tile_first[g + 1]); the same wave-uniform search.
+// grid.z is the launch's largest n_out; a workgroup past its own job's n_out leaves before any
+// barrier or LDS use (blockIdx and the job are workgroup-uniform, so every wave takes the exit).
+template <int C>
+__global__ void __launch_bounds__(Geo<C>::THREADS, 4)
+    rs2_decode_ranges_kernel(const CodecJobBatch* __restrict__ jobs,
+                             const uint32_t* __restrict__ tile_first, int n_jobs) {
+  const uint32_t tile = xcd_tile(blockIdx.x, gridDim.x);
+  int lo = 0, hi = n_jobs - 1;  // the last g with tile_first[g] <= tile
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (tile_first[mid] <= tile)
+      lo = mid;
+    else
+      hi = mid - 1;
+  }
+  const int g = __builtin_amdgcn_readfirstlane(lo);
+  const CodecJobBatch& job = jobs[g];
+  if (int(blockIdx.z) >= job.n_out) return;
+  codec_body<C, 3, false, CodecJobBatch, true>(job, tile - tile_first[g]);
+}
+
 }  // namespace rs2
 
 #define RS2_CAT2(a, b) a##b
@@ -1934,6 +1959,20 @@ extern "C" hipError_t RS2_CAT(rs2k_launch_encode_groups_, RS2_C)(const rs2::Code
                        stream, d_jobs, d_tile_first, n_jobs);
   else
     return hipErrorInvalidValue;
+  return hipGetLastError();
+}
+
+// Decode ranges: n_jobs jobs at d_jobs, job g the tiles [d_tile_first[g], d_tile_first[g + 1]) of
+// n_tiles (every job at least one), n_z = the largest n_out
+extern "C" hipError_t RS2_CAT(rs2k_launch_decode_ranges_, RS2_C)(const rs2::CodecJobBatch* d_jobs,
+                                                                 const uint32_t* d_tile_first,
+                                                                 int n_jobs, int n_tiles, int n_z,
+                                                                 hipStream_t stream) {
+  if (n_jobs < 1 || n_tiles < n_jobs || n_z < 1 || n_z > rs2::kBatchBlocks)
+    return hipErrorInvalidValue;
+  const dim3 grid(uint32_t(n_tiles), 1, n_z), block(rs2::Geo<RS2_C>::THREADS);
+  hipLaunchKernelGGL(rs2::rs2_decode_ranges_kernel<RS2_C>, grid, block, 0, stream, d_jobs,
+                     d_tile_first, n_jobs);
   return hipGetLastError();
 }
 

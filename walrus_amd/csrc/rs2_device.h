@@ -202,6 +202,13 @@ struct SliverLeafGroup {
   uint32_t first_slot, count, k, s;
 };
 static_assert(sizeof(SliverSlot) == 24 && sizeof(SliverLeafGroup) == 32, "sliver tables are packed");
+// The received symbols of one sliver of a mixed proof check (leaf_hash_runs_kernel): `count`
+// symbols of s bytes back to back at sym; symbol w's digest goes to digest first + w of the call.
+struct SymbolRun {
+  const uint8_t* sym;
+  uint32_t first, count, s, pad;
+};
+static_assert(sizeof(SymbolRun) == 24, "symbol runs are packed");
 // caller index -> slot table entry of a sliver refused on the host (sliver_finish_kernel)
 constexpr uint32_t kSliverSkipped = 0xFFFFFFFFu;
 

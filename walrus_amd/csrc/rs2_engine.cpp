@@ -1484,6 +1484,14 @@ struct rs2_sliver_checker {
   // host-buffer form: slivers in, roots and verdicts out
   DevBuf input, out;
   PinnedBuf h_in, h_out;
+  // mixed recovery (rs2_sliver_checker_recover_device_async): the chunk slots of the range
+  // launches and the slots of the per-sliver decodes, as a verifier's; mixed proof check: the
+  // per-sliver tables and the leaf digests
+  BatchDecodeSlot rbatch[2];
+  int rbatch_slot = 0;
+  DecodeSlot rdec[2];
+  int rdec_slot = 0;
+  DevBuf per_sliver, sym_digests;
   Event done;  // as rs2_verifier::done
   ~rs2_sliver_checker() {
     if (stream) (void)hipStreamDestroy(stream);
@@ -2303,9 +2311,32 @@ struct BatchRun {
   std::atomic<uint64_t>&launches, &batched, &single;
 };
 
+hipError_t launch_decode_ranges(int C, const CodecJobBatch* d_jobs, const uint32_t* d_tiles,
+                                int n_jobs, int n_tiles, int n_z, hipStream_t st) {
+  switch (C) {
+#define RS2_RANGES_CASE(CC) \
+  case CC: return rs2k_launch_decode_ranges_##CC(d_jobs, d_tiles, n_jobs, n_tiles, n_z, st);
+    RS2_RANGES_CASE(1)
+    RS2_RANGES_CASE(2)
+    RS2_RANGES_CASE(4)
+    RS2_RANGES_CASE(8)
+    RS2_RANGES_CASE(16)
+    RS2_RANGES_CASE(32)
+    RS2_RANGES_CASE(64)
+    RS2_RANGES_CASE(128)
+    RS2_RANGES_CASE(256)
+    RS2_RANGES_CASE(512)
+#undef RS2_RANGES_CASE
+    default: return hipErrorInvalidValue;
+  }
+}
+
 // One chunk: the blobs' arrays concatenated into the slot's device arrays, every job pointed
-// at its own part, one table build over all the logs, one launch.
-int launch_batch_chunk(const BatchRun& run, std::vector<BatchBlob*>& ch, hipStream_t st) {
+// at its own part, one table build over all the logs, one launch.  tiles null: every job has the
+// tiles of the first one (cut_batch_chunks).  Else the chunk's tile prefix array
+// (cut_range_chunks: a tile range per job); it goes up behind the job table.
+int launch_batch_chunk(const BatchRun& run, std::vector<BatchBlob*>& ch, hipStream_t st,
+                       const std::vector<uint32_t>* tiles = nullptr) {
   Context* ctx = run.ctx;
   BatchDecodeSlot& sl = run.slots[run.cursor];
   run.cursor ^= 1;
@@ -2328,10 +2359,13 @@ int launch_batch_chunk(const BatchRun& run, std::vector<BatchBlob*>& ch, hipStre
   HIP_TRY(sl.logs.ensure(std::max<size_t>(n_logs * 2, 16)));
   HIP_TRY(sl.tabs.ensure(std::max<size_t>(n_logs * kTabU16 * 2, 16)));
   HIP_TRY(sl.mix.ensure(std::max<size_t>(n_mix * 2, 16)));
-  HIP_TRY(sl.jobs.ensure(ch.size() * sizeof(CodecJobBatch)));
+  static_assert(sizeof(CodecJobBatch) % 4 == 0, "the tile prefix array follows the job table");
+  const size_t jobs_b = ch.size() * sizeof(CodecJobBatch);
+  HIP_TRY(sl.jobs.ensure(jobs_b + (tiles ? tiles->size() * 4 : 0)));
   const int C = ch[0]->C;
   const int64_t per_blob = (int64_t(run.lines) * ch[0]->job.pairs_span + 63) / 64;
-  if (per_blob < 1 || per_blob * int64_t(ch.size()) > 0x7FFFFFFF)
+  if (tiles ? tiles->size() != ch.size() + 1
+            : per_blob < 1 || per_blob * int64_t(ch.size()) > 0x7FFFFFFF)
     return fail(RS2_E_UNSUPPORTED, "decode batch chunk exceeds the launch grid");
   int n_z = 1;
   for (BatchBlob* bb : ch) {
@@ -2380,13 +2414,20 @@ int launch_batch_chunk(const BatchRun& run, std::vector<BatchBlob*>& ch, hipStre
   RS2_TRY(upload_pieces(ctx, sl.offs.p, h_offs.data(), h_offs.size() * 8, st));
   RS2_TRY(upload_pieces(ctx, sl.logs.p, h_logs.data(), h_logs.size() * 2, st));
   RS2_TRY(upload_pieces(ctx, sl.mix.p, h_mix.data(), h_mix.size() * 2, st));
-  RS2_TRY(upload_pieces(ctx, sl.jobs.p, h_jobs.data(), h_jobs.size() * sizeof(CodecJobBatch), st));
+  RS2_TRY(upload_pieces(ctx, sl.jobs.p, h_jobs.data(), jobs_b, st));
+  if (tiles)
+    RS2_TRY(upload_pieces(ctx, sl.jobs.as<uint8_t>() + jobs_b, tiles->data(), tiles->size() * 4, st));
   HIP_TRY(rs2k_launch_build_mul_tables(ctx->exp_t.as<uint16_t>(), ctx->log_t.as<uint16_t>(),
                                        sl.logs.as<uint16_t>(), int(h_logs.size()),
                                        sl.tabs.as<uint16_t>(), st));
   if (run.prof) mark(run.prof, "dec_batch_setup", st);
-  HIP_TRY(launch_decode_batch(C, sl.jobs.as<CodecJobBatch>(), int(ch.size()), int(per_blob), n_z,
-                              st));
+  if (tiles)
+    HIP_TRY(launch_decode_ranges(
+        C, sl.jobs.as<CodecJobBatch>(), reinterpret_cast<const uint32_t*>(sl.jobs.as<uint8_t>() + jobs_b),
+        int(ch.size()), int(tiles->back()), n_z, st));
+  else
+    HIP_TRY(launch_decode_batch(C, sl.jobs.as<CodecJobBatch>(), int(ch.size()), int(per_blob), n_z,
+                                st));
   if (run.prof) mark(run.prof, "dec_batch_codec", st);
   HIP_TRY(sl.done.record(st));
   return RS2_OK;
@@ -4484,10 +4525,13 @@ MixedTables mixed_tables(const rs2_sliver_checker* c, const SliverWindow& w, boo
 
 // Run a planned call on st.  src(i): the device address of the caller's sliver i (accepted ones
 // only).  expected / d_roots / d_verdict are indexed by the caller's sliver.  Every buffer is
-// sized for the call's largest window before the first window runs.
-template <class SrcF>
+// sized for the call's largest window before the first window runs.  before(w) runs on st ahead
+// of window w's own work (the mixed recovery decodes the window's slivers there).
+inline int no_window_hook(const SliverWindow&) { return RS2_OK; }
+template <class SrcF, class BeforeF = int (*)(const SliverWindow&)>
 int checker_run(rs2_sliver_checker* c, const SliverGroupsPlan& plan, SrcF src,
-                const uint8_t* expected, uint8_t* d_roots, int32_t* d_verdict, hipStream_t st) {
+                const uint8_t* expected, uint8_t* d_roots, int32_t* d_verdict, hipStream_t st,
+                BeforeF before = no_window_hook) {
   Context* ctx = c->ctx;
   const int64_t n = c->n;
   // a previous call on another stream still owns the scratch buffers and tables
@@ -4513,6 +4557,7 @@ int checker_run(rs2_sliver_checker* c, const SliverGroupsPlan& plan, SrcF src,
   uint8_t* const d_tab = c->tables.as<uint8_t>();
   std::vector<uint8_t> h_tab;
   for (const SliverWindow& w : plan.windows) {
+    RS2_TRY(before(w));
     const MixedTables t = mixed_tables(c, w, d_verdict != nullptr);
     h_tab.assign(t.bytes, 0);
     // slots: where each sliver comes from and goes to, and its chunks of the gather
@@ -4789,6 +4834,346 @@ int rs2_set_verify_mixed_budget(uint64_t bytes) {
 int rs2_verify_mixed_stats(uint64_t* stats_out) {
   return read_stats(stats_out,
                     {&g_vm_windows, &g_vm_grouped, &g_vm_single, &g_vm_groups, &g_vm_launches});
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------
+// mixed sliver recovery: slivers that share only n_shards, each recovered from its own received
+// symbols, with its own axis and symbol size; and the proof check of such received symbols
+// ---------------------------------------------------------------------------------------------
+namespace {
+std::atomic<uint64_t> g_rm_windows{0}, g_rm_launches{0}, g_rm_batched{0}, g_rm_single{0},
+    g_rm_groups{0};
+
+// What a mixed recovery call reads and writes: sliver i's received symbols back to back at
+// d_symbols + symbols_off[i], its output at d_out + sliver_off[i].
+struct MixedRecoverIo {
+  const uint8_t* axis;
+  const uint16_t* symbol_size;
+  const uint8_t* d_symbols;
+  const uint64_t* symbols_off;
+  uint8_t* d_out;
+  const uint64_t* sliver_off;
+};
+
+// Decode window w's accepted slivers (items from next_item on, in the caller's order) on st:
+// every sliver is planned on the host pool; the batch-eligible ones leave in range launches, one
+// per chunk of cut_range_chunks; the others through the per-sliver decode on the same stream.
+int recover_mixed_window(rs2_sliver_checker* c, const SliverWindow& w,
+                         const std::vector<MixedRecoverItem>& items, size_t& next_item,
+                         const MixedRecoverIo& io, hipStream_t st) {
+  Context* ctx = c->ctx;
+  const size_t i0 = next_item;
+  while (next_item < items.size() && items[next_item].slot < w.first + w.count) ++next_item;
+  const size_t cnt = next_item - i0;
+  std::vector<BatchBlob> jobs(cnt);
+  std::vector<DecodeSpec> specs(cnt);
+  pool_for_each(ctx->pool, cnt, [&](size_t i) {
+    const MixedRecoverItem& it = items[i0 + i];
+    DecodeSpec& sp = specs[i];
+    sliver_recover_spec(c->codes[io.axis[it.slot]].k, c->n, int(io.symbol_size[it.slot]), it.chosen,
+                        io.d_symbols + io.symbols_off[it.slot], io.d_out + io.sliver_off[it.slot],
+                        decode_may_fuse(), sp);
+    uint32_t originals = 0;
+    for (uint32_t q = 0; q < sp.K; ++q) originals += sp.present[q] >= 0;
+    if (originals < sp.K) plan_batch_spec(sp, originals, jobs[i]);
+  });
+  std::vector<ChunkJob> geo(cnt);
+  for (size_t i = 0; i < cnt; ++i)
+    geo[i] = {jobs[i].eligible, jobs[i].C, jobs[i].job.pairs_span, jobs[i].logs.size()};
+  std::vector<RangeChunk> chunks;
+  std::vector<uint32_t> demoted;
+  cut_range_chunks(geo, 1, kBatchTableBytes, chunks, demoted);
+  for (uint32_t i : demoted) jobs[i].eligible = false;
+  const BatchRun run{ctx, c->rbatch, c->rbatch_slot, 1, nullptr, "",
+                     g_rm_launches, g_rm_batched, g_rm_single};
+  std::vector<BatchBlob*> ch;
+  for (const RangeChunk& rc : chunks) {
+    ch.clear();
+    for (uint32_t m : rc.members) ch.push_back(&jobs[m]);
+    RS2_TRY(launch_batch_chunk(run, ch, st, &rc.tiles));
+    g_rm_launches.fetch_add(1, std::memory_order_relaxed);
+    g_rm_batched.fetch_add(ch.size(), std::memory_order_relaxed);
+  }
+  for (size_t i = 0; i < cnt; ++i) {
+    if (jobs[i].eligible) continue;
+    RS2_TRY(run_decode(ctx, c->rdec, c->rdec_slot, specs[i], {}, decode_may_fuse(), 1, nullptr, st));
+    g_rm_single.fetch_add(1, std::memory_order_relaxed);
+  }
+  g_rm_windows.fetch_add(1, std::memory_order_relaxed);
+  g_rm_groups.fetch_add(w.groups.size(), std::memory_order_relaxed);
+  return RS2_OK;
+}
+
+// Run a planned mixed recovery on st: per window the decodes, then -- with roots or verdicts
+// asked for -- the window's verification from the recovered slivers in place (checker_run).
+int recover_mixed_run(rs2_sliver_checker* c, const SliverGroupsPlan& plan,
+                      const std::vector<MixedRecoverItem>& items, const MixedRecoverIo& io,
+                      const uint8_t* expected, uint8_t* d_roots, int32_t* d_verdict,
+                      hipStream_t st) {
+  size_t next_item = 0;
+  auto decode = [&](const SliverWindow& w) {
+    return recover_mixed_window(c, w, items, next_item, io, st);
+  };
+  if (d_roots || expected)
+    return checker_run(
+        c, plan, [&](uint32_t i) -> const uint8_t* { return io.d_out + io.sliver_off[i]; }, expected,
+        d_roots, d_verdict, st, decode);
+  // a previous call on another stream still owns the decode slots
+  HIP_TRY(c->done.wait_on(st));
+  for (const SliverWindow& w : plan.windows) RS2_TRY(decode(w));
+  HIP_TRY(c->done.record(st));
+  return RS2_OK;
+}
+
+// The whole-call rules both recovery forms share (`arrays`: the form's own needed arrays).
+int check_recover_mixed_call(uint32_t n_slivers, bool arrays, const uint32_t* counts,
+                             const void* symbol_idx, const void* symbols, const void* expected,
+                             const void* verdict, bool* empty) {
+  RS2_TRY(check_mixed_call(n_slivers, arrays && counts, expected, verdict, empty));
+  if (*empty) return RS2_OK;
+  if (std::accumulate(counts, counts + n_slivers, size_t(0)) && (!symbol_idx || !symbols))
+    return fail(RS2_E_INVALID_ARGUMENT, "null argument");
+  return RS2_OK;
+}
+
+int recover_mixed_plan(rs2_sliver_checker* c, uint32_t n_slivers, const uint8_t* axis,
+                       const uint16_t* symbol_size, const uint32_t* counts,
+                       const uint16_t* symbol_idx, const uint64_t* symbols_off,
+                       const uint64_t* sliver_off, int* status_out,
+                       std::vector<MixedRecoverItem>& items, SliverGroupsPlan& plan) {
+  RS2_TRY(checker_codes(c));
+  return plan_recover_mixed(c->codes, n_slivers, axis, symbol_size, counts, symbol_idx, symbols_off,
+                            sliver_off, g_vm_budget.load(std::memory_order_relaxed),
+                            kMixedWindowGroups, uint32_t(kBatchChunkJobs), status_out, items, plan);
+}
+
+// The whole-call rules of the mixed proof check and its per-sliver tables: per[2i] = sliver i's
+// first symbol of the concatenated list, per[2i + 1] = its target; *total = symbols of the call.
+int check_symbols_mixed_call(uint16_t n, uint32_t n_slivers, const uint16_t* symbol_size,
+                             const uint32_t* counts, const uint16_t* target_index,
+                             std::vector<uint32_t>& per, uint64_t* total, uint32_t* max_count) {
+  per.assign(size_t(n_slivers) * 2, 0);
+  *total = 0;
+  *max_count = 0;
+  for (uint32_t i = 0; i < n_slivers; ++i) {
+    if (target_index[i] >= n)  // merkle.rs verify_proof: the leaf index is below n_leaves
+      return fail(RS2_E_INVALID_ARGUMENT, "target index too large");
+    if (symbol_size[i] == 0 || symbol_size[i] % 2)
+      return fail(RS2_E_INCOMPATIBLE_PARAMETERS, "symbol_size must be a multiple of the required alignment");
+    per[2 * i] = uint32_t(*total);
+    per[2 * i + 1] = target_index[i];
+    *total += counts[i];
+    *max_count = std::max(*max_count, counts[i]);
+    if (*total > 0x7FFFFFFFu) return fail(RS2_E_INVALID_ARGUMENT, "too many symbols in a call");
+  }
+  return RS2_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int rs2_sliver_checker_recover_device_async(
+    rs2_sliver_checker* c, uint32_t n_slivers, const uint8_t* axis, const uint16_t* symbol_size,
+    const uint32_t* counts, const uint16_t* symbol_idx, const void* d_symbols_base,
+    const uint64_t* symbols_off, const uint8_t* expected_roots, void* d_slivers_base,
+    const uint64_t* sliver_off, void* d_roots, void* d_verdict, int* status_out, void* stream) {
+  if (!c) return fail(RS2_E_INVALID_ARGUMENT, "null checker");
+  bool empty;
+  RS2_TRY(check_recover_mixed_call(
+      n_slivers, axis && symbol_size && symbols_off && d_slivers_base && sliver_off, counts,
+      symbol_idx, d_symbols_base, expected_roots, d_verdict, &empty));
+  if (empty) return RS2_OK;
+  RS2_TRY(check_symbol_ptr(d_symbols_base, "d_symbols_base"));
+  RS2_TRY(check_symbol_ptr(d_slivers_base, "d_slivers_base"));
+  RS2_TRY(check_digest_ptr(d_roots, "d_roots"));
+  RS2_TRY(check_digest_ptr(d_verdict, "d_verdict"));
+  HIP_TRY(hipSetDevice(c->ctx->device));
+  hipStream_t st = abi_stream(stream, c->stream);
+  // every sliver is validated, and the call planned, before anything is enqueued
+  std::vector<MixedRecoverItem> items;
+  SliverGroupsPlan plan;
+  RS2_TRY(recover_mixed_plan(c, n_slivers, axis, symbol_size, counts, symbol_idx, symbols_off,
+                             sliver_off, status_out, items, plan));
+  const MixedRecoverIo io{axis, symbol_size, reinterpret_cast<const uint8_t*>(d_symbols_base),
+                          symbols_off, reinterpret_cast<uint8_t*>(d_slivers_base), sliver_off};
+  return recover_mixed_run(c, plan, items, io, expected_roots, reinterpret_cast<uint8_t*>(d_roots),
+                           reinterpret_cast<int32_t*>(d_verdict), st);
+}
+
+int rs2_recover_slivers_mixed(uint16_t n_shards, uint32_t n_slivers, const uint8_t* axis,
+                              const uint16_t* symbol_size, const uint32_t* counts,
+                              const uint16_t* symbol_idx, const uint8_t* const* symbols,
+                              const uint8_t* expected_roots, uint8_t* const* slivers_out,
+                              uint8_t* roots_out, int32_t* verdict_out, int* status_out) {
+  bool empty;
+  RS2_TRY(check_recover_mixed_call(n_slivers, axis && symbol_size && slivers_out, counts,
+                                   symbol_idx, symbols, expected_roots, verdict_out, &empty));
+  if (empty) return RS2_OK;
+  CheckerLease lease;
+  RS2_TRY(lease.get(n_shards));
+  rs2_sliver_checker* c = lease.c;
+  HIP_TRY(hipSetDevice(c->ctx->device));
+  hipStream_t st = c->stream;
+  std::vector<MixedRecoverItem> items;
+  SliverGroupsPlan plan;
+  RS2_TRY(recover_mixed_plan(c, n_slivers, axis, symbol_size, counts, symbol_idx, nullptr, nullptr,
+                             status_out, items, plan));
+  // only the chosen symbols go up, K per accepted sliver, back to back; the slivers come back
+  // the same way, the roots and verdicts of all slots behind them: one H2D, one D2H
+  std::vector<uint64_t> off(n_slivers, 0);
+  uint64_t len_b = 0;
+  for (MixedRecoverItem& it : items) {
+    if (!slivers_out[it.slot]) return fail(RS2_E_INVALID_ARGUMENT, "null output sliver");
+    for (const auto& ch : it.chosen)
+      if (!symbols[it.first + ch.second]) return fail(RS2_E_INVALID_ARGUMENT, "null symbol");
+    off[it.slot] = len_b;
+    len_b += uint64_t(it.chosen.size()) * symbol_size[it.slot];
+  }
+  const size_t roots_at = (size_t(len_b) + 15) / 16 * 16;
+  const size_t verdict_at = roots_at + size_t(n_slivers) * 32;
+  const size_t back_b = verdict_at + size_t(n_slivers) * 4;
+  HIP_TRY(c->input.ensure(std::max<size_t>(size_t(len_b), 16)));
+  HIP_TRY(c->h_in.ensure(std::max<size_t>(size_t(len_b), 16)));
+  HIP_TRY(c->out.ensure(back_b));
+  HIP_TRY(c->h_out.ensure(back_b));
+  for (MixedRecoverItem& it : items) {
+    const size_t s = symbol_size[it.slot];
+    uint8_t* at = static_cast<uint8_t*>(c->h_in.p) + off[it.slot];
+    for (size_t q = 0; q < it.chosen.size(); ++q) {
+      std::memcpy(at + q * s, symbols[it.first + it.chosen[q].second], s);
+      it.chosen[q].second = uint32_t(q);
+    }
+  }
+  if (len_b) HIP_TRY(hipMemcpyAsync(c->input.p, c->h_in.p, len_b, hipMemcpyHostToDevice, st));
+  uint8_t* dout = c->out.as<uint8_t>();
+  const bool roots = roots_out || expected_roots;
+  const MixedRecoverIo io{axis, symbol_size, c->input.as<uint8_t>(), off.data(), dout, off.data()};
+  RS2_TRY(recover_mixed_run(c, plan, items, io, expected_roots, roots ? dout + roots_at : nullptr,
+                            expected_roots ? reinterpret_cast<int32_t*>(dout + verdict_at) : nullptr,
+                            st));
+  HIP_TRY(hipMemcpyAsync(c->h_out.p, dout, back_b, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  const uint8_t* ho = static_cast<const uint8_t*>(c->h_out.p);
+  // slots of refused slivers are not written, except verdict_out
+  for (const MixedRecoverItem& it : items) {
+    std::memcpy(slivers_out[it.slot], ho + off[it.slot],
+                it.chosen.size() * size_t(symbol_size[it.slot]));
+    if (roots_out)
+      std::memcpy(roots_out + size_t(it.slot) * 32, ho + roots_at + size_t(it.slot) * 32, 32);
+  }
+  if (verdict_out) std::memcpy(verdict_out, ho + verdict_at, size_t(n_slivers) * 4);
+  return RS2_OK;
+}
+
+int rs2_recover_mixed_stats(uint64_t* stats_out) {
+  return read_stats(stats_out,
+                    {&g_rm_windows, &g_rm_launches, &g_rm_batched, &g_rm_single, &g_rm_groups});
+}
+
+int rs2_sliver_checker_check_recovery_symbols_device_async(
+    rs2_sliver_checker* c, uint32_t n_slivers, const uint16_t* symbol_size, const uint32_t* counts,
+    const uint16_t* target_index, const void* d_symbols_base, const uint64_t* symbols_off,
+    const void* d_proofs, const void* d_expected_roots, void* d_ok, void* stream) {
+  if (!c) return fail(RS2_E_INVALID_ARGUMENT, "null checker");
+  bool empty;
+  RS2_TRY(batch_count(n_slivers, "slivers in a call",
+                      symbol_size && counts && target_index && symbols_off, &empty));
+  if (empty) return RS2_OK;
+  const int L = merkle_path_len(c->n);
+  std::vector<uint32_t> per;
+  uint64_t total;
+  uint32_t max_count;
+  RS2_TRY(check_symbols_mixed_call(c->n, n_slivers, symbol_size, counts, target_index, per, &total,
+                                   &max_count));
+  for (uint32_t i = 0; i < n_slivers; ++i)
+    RS2_TRY(check_symbol_step(symbols_off[i], "symbols_off[i]"));
+  if (total == 0) return RS2_OK;
+  if (!d_symbols_base || !d_expected_roots || !d_ok || (L && !d_proofs))
+    return fail(RS2_E_INVALID_ARGUMENT, "null argument");
+  RS2_TRY(check_symbol_ptr(d_symbols_base, "d_symbols_base"));
+  RS2_TRY(check_digest_ptr(d_proofs, "d_proofs"));
+  RS2_TRY(check_digest_ptr(d_expected_roots, "d_expected_roots"));
+  RS2_TRY(check_digest_ptr(d_ok, "d_ok"));
+  HIP_TRY(hipSetDevice(c->ctx->device));
+  hipStream_t st = abi_stream(stream, c->stream);
+  HIP_TRY(c->done.wait_on(st));
+  // the proof check's table, then the leaf launch's runs, through one upload
+  const size_t runs_at = (per.size() * 4 + 15) / 16 * 16;
+  std::vector<uint8_t> h_tab(runs_at + size_t(n_slivers) * sizeof(SymbolRun), 0);
+  std::memcpy(h_tab.data(), per.data(), per.size() * 4);
+  SymbolRun* runs = reinterpret_cast<SymbolRun*>(h_tab.data() + runs_at);
+  for (uint32_t i = 0; i < n_slivers; ++i)
+    runs[i] = {reinterpret_cast<const uint8_t*>(d_symbols_base) + symbols_off[i], per[2 * i],
+               counts[i], symbol_size[i], 0};
+  HIP_TRY(c->sym_digests.ensure(size_t(total) * 32));
+  HIP_TRY(c->per_sliver.ensure(h_tab.size()));
+  RS2_TRY(upload_pieces(c->ctx, c->per_sliver.p, h_tab.data(), h_tab.size(), st));
+  HIP_TRY(rs2k_launch_leaf_hash_runs(
+      reinterpret_cast<const SymbolRun*>(c->per_sliver.as<uint8_t>() + runs_at), int(n_slivers),
+      max_count, c->sym_digests.as<uint8_t>(), st));
+  HIP_TRY(rs2k_launch_recovery_proof_check(
+      c->sym_digests.as<uint8_t>(), c->per_sliver.as<uint32_t>(), int(n_slivers), max_count,
+      uint32_t(total), reinterpret_cast<const uint8_t*>(d_proofs), L,
+      reinterpret_cast<const uint8_t*>(d_expected_roots), reinterpret_cast<uint8_t*>(d_ok), st));
+  HIP_TRY(c->done.record(st));
+  return RS2_OK;
+}
+
+int rs2_check_recovery_symbols_mixed(uint16_t n_shards, uint32_t n_slivers,
+                                     const uint16_t* symbol_size, const uint32_t* counts,
+                                     const uint16_t* target_index, const uint8_t* const* symbols,
+                                     const uint8_t* proofs, const uint8_t* expected_roots,
+                                     uint8_t* ok_out) {
+  bool empty;
+  RS2_TRY(batch_count(n_slivers, "slivers in a call", symbol_size && counts && target_index, &empty));
+  if (empty) return RS2_OK;
+  CheckerLease lease;
+  RS2_TRY(lease.get(n_shards));
+  rs2_sliver_checker* c = lease.c;
+  const size_t L = size_t(merkle_path_len(n_shards));
+  std::vector<uint32_t> per;
+  uint64_t total64;
+  uint32_t max_count;
+  RS2_TRY(check_symbols_mixed_call(n_shards, n_slivers, symbol_size, counts, target_index, per,
+                                   &total64, &max_count));
+  const size_t total = size_t(total64);
+  if (total == 0) return RS2_OK;
+  if (!symbols || !expected_roots || !ok_out || (L && !proofs))
+    return fail(RS2_E_INVALID_ARGUMENT, "null argument");
+  for (size_t j = 0; j < total; ++j)
+    if (!symbols[j]) return fail(RS2_E_INVALID_ARGUMENT, "null symbol");
+  HIP_TRY(hipSetDevice(c->ctx->device));
+  hipStream_t st = c->stream;
+  // symbols (a sliver's back to back), proofs and expected roots through one pinned buffer
+  std::vector<uint64_t> off(n_slivers, 0);
+  size_t sym_b = 0;
+  for (uint32_t i = 0; i < n_slivers; ++i) {
+    off[i] = sym_b;
+    sym_b += size_t(counts[i]) * symbol_size[i];
+  }
+  const size_t prf_at = (sym_b + 15) / 16 * 16;
+  const size_t exp_at = prf_at + total * L * 32, ok_at = exp_at + total * 32;
+  const size_t all_b = ok_at + (total + 15) / 16 * 16;
+  HIP_TRY(c->input.ensure(all_b));
+  HIP_TRY(c->h_in.ensure(ok_at));
+  HIP_TRY(c->h_out.ensure(std::max<size_t>(total, 16)));
+  uint8_t* hi = static_cast<uint8_t*>(c->h_in.p);
+  for (uint32_t i = 0; i < n_slivers; ++i)
+    for (uint32_t q = 0; q < counts[i]; ++q)
+      std::memcpy(hi + off[i] + size_t(q) * symbol_size[i], symbols[per[2 * i] + q], symbol_size[i]);
+  if (L) std::memcpy(hi + prf_at, proofs, total * L * 32);
+  std::memcpy(hi + exp_at, expected_roots, total * 32);
+  HIP_TRY(hipMemcpyAsync(c->input.p, hi, ok_at, hipMemcpyHostToDevice, st));
+  uint8_t* d = c->input.as<uint8_t>();
+  RS2_TRY(rs2_sliver_checker_check_recovery_symbols_device_async(
+      c, n_slivers, symbol_size, counts, target_index, d, off.data(), d + prf_at, d + exp_at,
+      d + ok_at, nullptr));
+  HIP_TRY(hipMemcpyAsync(c->h_out.p, d + ok_at, total, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  std::memcpy(ok_out, c->h_out.p, total);
+  return RS2_OK;
 }
 
 int rs2_merkle_root(const uint8_t* leaves, uint32_t n_leaves, uint32_t leaf_len, uint8_t root_out[32]) {

@@ -1204,6 +1204,67 @@ __global__ void __launch_bounds__(256)
   o[1] = make_uint4(uint32_t(h[2]), uint32_t(h[2] >> 32), uint32_t(h[3]), uint32_t(h[3] >> 32));
 }
 
+// Leaf digests of the received symbols of a mixed proof check
+// (rs2_sliver_checker_check_recovery_symbols_device_async): grid (ceil(max count / 256), slivers)
+// as recovery_proof_check_kernel's, so the symbol size is workgroup-uniform and no wave mixes
+// message lengths.  Lane w of sliver y hashes symbol w of its run into digest runs[y].first + w,
+// where the proof check reads it.  The walk is leaf_hash_groups_kernel's, restated here and not
+// shared as a function: that kernel sits at 128 VGPRs, an occupancy edge, and calling a common
+// helper from it moved its allocation to 130.  Every load is bounded by the sliver's run.
+__global__ void __launch_bounds__(256)
+    leaf_hash_runs_kernel(const SymbolRun* __restrict__ runs, uint8_t* __restrict__ out) {
+  const SymbolRun sr = runs[blockIdx.y];
+  const uint32_t w = blockIdx.x * 256 + threadIdx.x;
+  if (w >= sr.count) return;
+  const int64_t s = sr.s, run_len = int64_t(sr.count) * s, at = int64_t(w) * s;
+  const uint8_t* run = sr.sym;
+  const uintptr_t r0 = reinterpret_cast<uintptr_t>(run);
+  const uintptr_t floor_ = r0 & ~uintptr_t(3), end = r0 + uintptr_t(run_len);
+  const uintptr_t a = r0 + uintptr_t(at), sym_end = a + uintptr_t(s);
+  auto dword_at = [&](uintptr_t p) -> uint32_t {
+    if (p < floor_ || p >= sym_end) return 0u;
+    if (p + 4 <= end) return *reinterpret_cast<const uint32_t*>(p);
+    uint32_t v = 0;
+    for (int b = 0; b < 3; ++b)
+      if (p + b < end) v |= uint32_t(*reinterpret_cast<const uint8_t*>(p + b)) << (8 * b);
+    return v;
+  };
+  const int64_t lm = s + 1;
+  uint64_t h[8];
+  b2_init(h);
+#pragma clang loop unroll(disable)
+  for (int64_t b0 = 0; b0 < lm; b0 += 128) {
+    // message bytes [b0, b0 + 128) are the bytes from a + b0 - 1 on (byte 0: the leaf prefix)
+    const uintptr_t p = a + uintptr_t(b0) - 1;
+    const uintptr_t P0 = p & ~uintptr_t(3);
+    const uint32_t sh = uint32_t(p & 3);
+    uint32_t E[33];
+    sfor<33>([&](auto jj) {
+      constexpr int j = decltype(jj)::value;
+      E[j] = dword_at(P0 + 4 * j);
+    });
+    uint64_t m[16];
+    sfor<16>([&](auto ii) {
+      constexpr int i = decltype(ii)::value;
+      uint32_t w[2];
+      sfor<2>([&](auto qq) {
+        constexpr int t = 2 * i + decltype(qq)::value;
+        uint32_t x = __builtin_amdgcn_alignbyte(E[t + 1], E[t], sh);
+        if (t == 0 && b0 == 0) x &= 0xFFFFFF00u;
+        const int64_t keep = lm - b0 - 4 * t;
+        if (keep < 4) x = keep <= 0 ? 0u : (x & ((1u << (8 * int(keep))) - 1u));
+        w[decltype(qq)::value] = x;
+      });
+      m[i] = uint64_t(w[0]) | (uint64_t(w[1]) << 32);
+    });
+    const bool last = b0 + 128 >= lm;
+    b2_compress(h, m, uint64_t(last ? lm : b0 + 128), last);
+  }
+  uint4* o = reinterpret_cast<uint4*>(out + (int64_t(sr.first) + w) * 32);
+  o[0] = make_uint4(uint32_t(h[0]), uint32_t(h[0] >> 32), uint32_t(h[1]), uint32_t(h[1] >> 32));
+  o[1] = make_uint4(uint32_t(h[2]), uint32_t(h[2] >> 32), uint32_t(h[3]), uint32_t(h[3] >> 32));
+}
+
 // Roots and verdicts of a mixed verification window in the caller's order: entry i of the window
 // was refused on the host (slot_of[i] == kSliverSkipped: RS2_SLIVER_SKIPPED, its root slot is
 // not written) or is slot slot_of[i] of the window, whose root (slot_roots + 32 slot) is copied
@@ -1590,6 +1651,15 @@ hipError_t rs2k_launch_leaf_hash_groups(const rs2::SliverLeafGroup* d_groups, in
   if (n_groups < 1 || n_groups > n_slots || n_slots > 65535 || n < 1) return hipErrorInvalidValue;
   hipLaunchKernelGGL(rs2::leaf_hash_groups_kernel, dim3(unsigned((n + 255) / 256), unsigned(n_slots)),
                      dim3(256), 0, stream, d_groups, n_groups, n, d_leaves);
+  return hipGetLastError();
+}
+
+hipError_t rs2k_launch_leaf_hash_runs(const rs2::SymbolRun* d_runs, int n_slivers,
+                                      uint32_t max_count, uint8_t* d_digests, hipStream_t stream) {
+  if (n_slivers <= 0 || max_count == 0) return hipSuccess;
+  if (n_slivers > 65535) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(rs2::leaf_hash_runs_kernel, dim3((max_count + 255) / 256, unsigned(n_slivers)),
+                     dim3(256), 0, stream, d_runs, d_digests);
   return hipGetLastError();
 }
 

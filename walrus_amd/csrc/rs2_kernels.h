@@ -55,6 +55,26 @@ RS2_DECL_GROUPS(128)
 RS2_DECL_GROUPS(256)
 RS2_DECL_GROUPS(512)
 #undef RS2_DECL_GROUPS
+// decode ranges of a mixed sliver recovery (rs2_decode_ranges_kernel): a tile range per job
+#define RS2_DECL_RANGES(CC)                                                                    \
+  hipError_t rs2k_launch_decode_ranges_##CC(const rs2::CodecJobBatch* d_jobs,                 \
+                                            const uint32_t* d_tile_first, int n_jobs,         \
+                                            int n_tiles, int n_z, hipStream_t stream);
+RS2_DECL_RANGES(1)
+RS2_DECL_RANGES(2)
+RS2_DECL_RANGES(4)
+RS2_DECL_RANGES(8)
+RS2_DECL_RANGES(16)
+RS2_DECL_RANGES(32)
+RS2_DECL_RANGES(64)
+RS2_DECL_RANGES(128)
+RS2_DECL_RANGES(256)
+RS2_DECL_RANGES(512)
+#undef RS2_DECL_RANGES
+// leaf digests of the received symbols of a mixed proof check (leaf_hash_runs_kernel): d_runs
+// holds n_slivers SymbolRun; max_count: the largest symbol count of a sliver (grid.x)
+hipError_t rs2k_launch_leaf_hash_runs(const rs2::SymbolRun* d_runs, int n_slivers,
+                                      uint32_t max_count, uint8_t* d_digests, hipStream_t stream);
 // mixed sliver verification, one window: the slots' slivers gathered (d_slots: n_slots + 1
 // SliverSlot, the last one's chunk0 the launch's chunks), the eligible slots' leaves (d_groups:
 // n_groups + 1 SliverLeafGroup, leaf (slot, c) at d_leaves + (slot * n + c) * 32), and the roots

@@ -850,40 +850,14 @@ void close_sliver_window(const SliverAxisCode (&codes)[2], SliverWindow& w,
   for (uint32_t p = 0; p < ng; ++p) next[p] = gs[p].first_slot;
   for (size_t i = 0; i < idx.size(); ++i) w.perm[next[place[grp[i]]]++] = idx[i];
 }
-}  // namespace
 
-int plan_sliver_groups(const SliverAxisCode (&codes)[2], uint32_t n_slivers, const uint8_t* axis,
-                       const uint16_t* symbol_size, const uint64_t* sliver_off,
-                       const uint8_t* const* slivers, const uint64_t* sliver_len, uint64_t budget,
-                       uint32_t max_groups, int* status_out, SliverGroupsPlan& plan) {
-  plan = SliverGroupsPlan{};
-  if (n_slivers > 65535) return fail(RS2_E_INVALID_ARGUMENT, "more than 65535 slivers in a call");
-  if (max_groups == 0 || codes[0].n == 0 || codes[0].n != codes[1].n)
-    return fail(RS2_E_INVALID_ARGUMENT, "not a sliver's code");
-  if (n_slivers == 0) return RS2_OK;
-  if (!axis || !symbol_size || (!sliver_off && !(slivers && sliver_len)))
-    return fail(RS2_E_INVALID_ARGUMENT, "null argument");
+// The windows of a mixed call over the slivers with ok[i] set (the caller validated them): the
+// rule of plan_sliver_groups, and a window also closes before the sliver that would make it hold
+// more than max_slivers accepted slivers.
+void window_slivers(const SliverAxisCode (&codes)[2], uint32_t n_slivers, const uint8_t* axis,
+                    const uint16_t* symbol_size, const std::vector<uint8_t>& ok, uint64_t budget,
+                    uint32_t max_groups, uint32_t max_slivers, SliverGroupsPlan& plan) {
   const uint32_t n = codes[0].n;
-  auto check = [&](uint32_t i) -> int {
-    if (axis[i] != RS2_AXIS_PRIMARY && axis[i] != RS2_AXIS_SECONDARY)
-      return fail(RS2_E_INVALID_ARGUMENT, "bad axis");
-    const uint32_t s = symbol_size[i];
-    if (s == 0 || s % 2)
-      return fail(RS2_E_INCOMPATIBLE_PARAMETERS, "symbol_size must be a multiple of the required alignment");
-    if (sliver_off && sliver_off[i] % 2)
-      return fail(RS2_E_INVALID_ARGUMENT, "sliver_off[i] must be a multiple of 2 bytes");
-    if (!sliver_off && (!slivers[i] || sliver_len[i] != uint64_t(codes[axis[i]].k) * s))
-      return fail(RS2_E_INCORRECT_DATA_LENGTH, "sliver length does not match its axis and symbol size");
-    return RS2_OK;
-  };
-  std::vector<uint8_t> ok(n_slivers, 0);
-  for (uint32_t i = 0; i < n_slivers; ++i) {
-    const int rc = check(i);
-    if (status_out) status_out[i] = rc;
-    else if (rc != RS2_OK) return rc;
-    ok[i] = rc == RS2_OK;
-    plan.accepted += ok[i];
-  }
   SliverWindow w;
   std::vector<uint32_t> idx, grp;
   std::map<uint32_t, uint32_t> open;  // axis << 16 | s -> group of the open window
@@ -906,7 +880,8 @@ int plan_sliver_groups(const SliverAxisCode (&codes)[2], uint32_t n_slivers, con
     auto it = open.find(key);
     // (need > budget - used, not used + need > budget: the sum may wrap)
     if (i > w.first && !idx.empty() &&
-        (used > budget || need > budget - used || (it == open.end() && open.size() == max_groups))) {
+        (used > budget || need > budget - used || idx.size() >= max_slivers ||
+         (it == open.end() && open.size() == max_groups))) {
       close(i);
       it = open.end();
     }
@@ -925,6 +900,132 @@ int plan_sliver_groups(const SliverAxisCode (&codes)[2], uint32_t n_slivers, con
     used += need;
   }
   close(n_slivers);
+}
+}  // namespace
+
+int plan_sliver_groups(const SliverAxisCode (&codes)[2], uint32_t n_slivers, const uint8_t* axis,
+                       const uint16_t* symbol_size, const uint64_t* sliver_off,
+                       const uint8_t* const* slivers, const uint64_t* sliver_len, uint64_t budget,
+                       uint32_t max_groups, int* status_out, SliverGroupsPlan& plan) {
+  plan = SliverGroupsPlan{};
+  if (n_slivers > 65535) return fail(RS2_E_INVALID_ARGUMENT, "more than 65535 slivers in a call");
+  if (max_groups == 0 || codes[0].n == 0 || codes[0].n != codes[1].n)
+    return fail(RS2_E_INVALID_ARGUMENT, "not a sliver's code");
+  if (n_slivers == 0) return RS2_OK;
+  if (!axis || !symbol_size || (!sliver_off && !(slivers && sliver_len)))
+    return fail(RS2_E_INVALID_ARGUMENT, "null argument");
+  auto check = [&](uint32_t i) -> int {
+    if (axis[i] != RS2_AXIS_PRIMARY && axis[i] != RS2_AXIS_SECONDARY)
+      return fail(RS2_E_INVALID_ARGUMENT, "bad axis");
+    const uint32_t s = symbol_size[i];
+    if (s == 0 || s % 2)
+      return fail(RS2_E_INCOMPATIBLE_PARAMETERS, "symbol_size must be a multiple of the required alignment");
+    if (sliver_off && sliver_off[i] % 2)
+      return fail(RS2_E_INVALID_ARGUMENT, "sliver_off[i] must be a multiple of 2 bytes");
+    if (!sliver_off && (!slivers[i] || sliver_len[i] != uint64_t(codes[axis[i]].k) * s))
+      return fail(RS2_E_INCORRECT_DATA_LENGTH, "sliver length does not match its axis and symbol size");
+    return RS2_OK;
+  };
+  std::vector<uint8_t> ok(n_slivers, 0);
+  for (uint32_t i = 0; i < n_slivers; ++i) {
+    const int rc = check(i);
+    if (status_out) status_out[i] = rc;
+    else if (rc != RS2_OK) return rc;
+    ok[i] = rc == RS2_OK;
+    plan.accepted += ok[i];
+  }
+  window_slivers(codes, n_slivers, axis, symbol_size, ok, budget, max_groups, UINT32_MAX, plan);
+  return RS2_OK;
+}
+
+void cut_range_chunks(const std::vector<ChunkJob>& jobs, int64_t lines, size_t table_budget,
+                      std::vector<RangeChunk>& chunks, std::vector<uint32_t>& demoted) {
+  chunks.clear();
+  demoted.clear();
+  constexpr uint64_t kGrid = 0x7FFFFFFFu;
+  std::vector<int> classes;  // C values in the order of first appearance
+  for (const ChunkJob& j : jobs)
+    if (j.eligible && std::find(classes.begin(), classes.end(), j.C) == classes.end())
+      classes.push_back(j.C);
+  for (int C : classes) {
+    RangeChunk ch;
+    size_t tab_bytes = 0;
+    auto flush = [&] {
+      if (!ch.members.empty()) chunks.push_back(std::move(ch));
+      ch = RangeChunk{};
+      tab_bytes = 0;
+    };
+    for (uint32_t i = 0; i < jobs.size(); ++i) {
+      const ChunkJob& j = jobs[i];
+      if (!j.eligible || j.C != C) continue;
+      const uint64_t t = (uint64_t(lines) * uint64_t(j.pairs_span) + 63) / 64;
+      if (t < 1 || t > kGrid) {
+        demoted.push_back(i);
+        continue;
+      }
+      const size_t need = j.n_logs * kTabU16 * 2;
+      if (!ch.members.empty() && (tab_bytes + need > table_budget || ch.tiles.back() + t > kGrid))
+        flush();
+      if (ch.members.empty()) {
+        ch.C = C;
+        ch.tiles.assign(1, 0);
+      }
+      ch.members.push_back(i);
+      ch.tiles.push_back(uint32_t(ch.tiles.back() + t));
+      tab_bytes += need;
+    }
+    flush();
+  }
+  std::sort(demoted.begin(), demoted.end());
+}
+
+int plan_recover_mixed(const SliverAxisCode (&codes)[2], uint32_t n_slivers, const uint8_t* axis,
+                       const uint16_t* symbol_size, const uint32_t* counts,
+                       const uint16_t* symbol_idx, const uint64_t* symbols_off,
+                       const uint64_t* sliver_off, uint64_t budget, uint32_t max_groups,
+                       uint32_t max_slivers, int* status_out, std::vector<MixedRecoverItem>& items,
+                       SliverGroupsPlan& plan) {
+  plan = SliverGroupsPlan{};
+  items.clear();
+  if (n_slivers > 65535) return fail(RS2_E_INVALID_ARGUMENT, "more than 65535 slivers in a call");
+  if (max_groups == 0 || max_slivers == 0 || codes[0].n == 0 || codes[0].n != codes[1].n)
+    return fail(RS2_E_INVALID_ARGUMENT, "not a sliver's code");
+  const uint32_t n = codes[0].n;
+  if (codes[0].k >= n || codes[1].k >= n)
+    return fail(RS2_E_INCOMPATIBLE_PARAMETERS, "no repair symbols");
+  if (n_slivers == 0) return RS2_OK;
+  if (!axis || !symbol_size || !counts) return fail(RS2_E_INVALID_ARGUMENT, "null argument");
+  uint64_t total = 0;
+  for (uint32_t i = 0; i < n_slivers; ++i) total += counts[i];
+  if (total && !symbol_idx) return fail(RS2_E_INVALID_ARGUMENT, "null argument");
+  items.reserve(n_slivers);
+  std::vector<uint8_t> ok(n_slivers, 0);
+  uint64_t first = 0;
+  for (uint32_t i = 0; i < n_slivers; first += counts[i], ++i) {
+    MixedRecoverItem it;
+    it.slot = i;
+    it.first = first;
+    auto check = [&]() -> int {
+      if (axis[i] != RS2_AXIS_PRIMARY && axis[i] != RS2_AXIS_SECONDARY)
+        return fail(RS2_E_INVALID_ARGUMENT, "bad axis");
+      const uint32_t s = symbol_size[i];
+      if (s == 0 || s % 2)
+        return fail(RS2_E_INCOMPATIBLE_PARAMETERS, "symbol_size must be a multiple of the required alignment");
+      if (symbols_off && symbols_off[i] % 2)
+        return fail(RS2_E_INVALID_ARGUMENT, "symbols_off[i] must be a multiple of 2 bytes");
+      if (sliver_off && sliver_off[i] % 2)
+        return fail(RS2_E_INVALID_ARGUMENT, "sliver_off[i] must be a multiple of 2 bytes");
+      return select_recovery_symbols(codes[axis[i]].k, n, counts[i], symbol_idx + first, it.chosen);
+    };
+    const int rc = check();
+    if (status_out) status_out[i] = rc;
+    else if (rc != RS2_OK) return rc;
+    if (rc != RS2_OK) continue;
+    ok[i] = 1;
+    ++plan.accepted;
+    items.push_back(std::move(it));
+  }
+  window_slivers(codes, n_slivers, axis, symbol_size, ok, budget, max_groups, max_slivers, plan);
   return RS2_OK;
 }
 

@@ -485,4 +485,49 @@ int plan_sliver_groups(const SliverAxisCode (&codes)[2], uint32_t n_slivers, con
                        const uint8_t* const* slivers, const uint64_t* sliver_len, uint64_t budget,
                        uint32_t max_groups, int* status_out, SliverGroupsPlan& plan);
 
+// ---------------------------------------------------------------------------------------------
+// mixed sliver recovery (rs2_sliver_checker_recover_device_async): slivers that share only
+// n_shards, each recovered from its own received symbols, with its own axis and symbol size
+// ---------------------------------------------------------------------------------------------
+// One launch of the range cut: its jobs (indices into the window, in order), their C and the tile
+// prefix array rs2_decode_ranges_kernel searches -- job j of the chunk owns the tiles
+// [tiles[j], tiles[j + 1]), ceil(lines * pairs_span_j / 64) of them, and tiles.back() is the
+// launch's tile count.
+struct RangeChunk {
+  int C = 0;
+  std::vector<uint32_t> members, tiles;
+};
+// Pack a window's eligible jobs into range launches.  The jobs are partitioned by C (the block
+// size: a function of the axis' (K, n) and the block limit, so a checker's window has at most two
+// classes), the classes in the order of first appearance; each class is cut, in order, before the
+// job whose tables would take the chunk past table_budget bytes or whose tiles would take the
+// launch past 2^31 - 1 (a job larger than the budget still forms a chunk of its own).  Nothing is
+// demoted for its pairs_span.  `demoted` receives only jobs whose own tiles exceed a launch grid.
+void cut_range_chunks(const std::vector<ChunkJob>& jobs, int64_t lines, size_t table_budget,
+                      std::vector<RangeChunk>& chunks, std::vector<uint32_t>& demoted);
+
+// One validated sliver of a mixed recovery call: its index in the call, its first entry of
+// symbol_idx and the symbols it is recovered from (select_recovery_symbols).
+struct MixedRecoverItem {
+  uint32_t slot = 0;
+  uint64_t first = 0;
+  std::vector<std::pair<uint16_t, uint32_t>> chosen;
+};
+
+// Validate and plan a mixed recovery call.  Per sliver, in this order: an axis that is not one of
+// the two RS2_E_INVALID_ARGUMENT; a symbol size of 0 or odd RS2_E_INCOMPATIBLE_PARAMETERS; an odd
+// symbols_off[i] or sliver_off[i] (either may be null: the host form has none)
+// RS2_E_INVALID_ARGUMENT; counts[i] < K RS2_E_DECODING_UNSUCCESSFUL; then
+// select_recovery_symbols' rules (RS2_E_NOT_ENOUGH_SHARDS).  status_out as plan_sliver_groups.
+// items: the accepted slivers in the caller's order.  plan: the windows of the recovered slivers'
+// verification, plan_sliver_groups' rule (budget, max_groups) and also closed before the sliver
+// that would take a window past max_slivers accepted slivers.  More than 65535 slivers, null
+// arrays, max_groups or max_slivers 0, or a code without repair symbols: whole-call refusals.
+int plan_recover_mixed(const SliverAxisCode (&codes)[2], uint32_t n_slivers, const uint8_t* axis,
+                       const uint16_t* symbol_size, const uint32_t* counts,
+                       const uint16_t* symbol_idx, const uint64_t* symbols_off,
+                       const uint64_t* sliver_off, uint64_t budget, uint32_t max_groups,
+                       uint32_t max_slivers, int* status_out, std::vector<MixedRecoverItem>& items,
+                       SliverGroupsPlan& plan);
+
 }  // namespace rs2

@@ -936,6 +936,51 @@ class SliverChecker:
             return list(st)[:m]
         return rc
 
+    def recover_async(self, axes: Sequence[str], symbol_sizes: Sequence[int],
+                      index_lists: Sequence[Sequence[int]], d_symbols_base: int,
+                      symbols_off: Sequence[int], d_slivers_base: int, sliver_off: Sequence[int],
+                      expected_roots: Optional[bytes] = None, d_roots: int = 0,
+                      d_verdict: int = 0, stream: Optional[int] = None, statuses: bool = False):
+        """rs2_sliver_checker_recover_device_async: sliver i (axes[i], symbol_sizes[i]) is
+        recovered from the received symbols whose source indices are index_lists[i], their data
+        back to back at d_symbols_base + symbols_off[i], and written at d_slivers_base +
+        sliver_off[i].  Roots, verdicts, `statuses` and the return value as verify_async."""
+        m = len(axes)
+        ax = np.array([_AXIS.get(a, a) for a in axes] + [0], dtype=np.uint8)
+        sz = np.array(list(symbol_sizes) + [0], dtype=np.uint16)
+        counts = np.array([len(x) for x in index_lists] + [0], dtype=np.uint32)
+        idx = np.array([i for x in index_lists for i in x] + [0], dtype=np.uint16)
+        s_off = np.array(list(symbols_off) + [0], dtype=np.uint64)
+        o_off = np.array(list(sliver_off) + [0], dtype=np.uint64)
+        exp = None
+        if expected_roots is not None:
+            exp = np.frombuffer(bytes(expected_roots) or b"\0", dtype=np.uint8)
+        st = (ctypes.c_int * max(m, 1))() if statuses else None
+        u16, u32, u64 = (ctypes.POINTER(t) for t in (ctypes.c_uint16, ctypes.c_uint32,
+                                                     ctypes.c_uint64))
+        rc = _lib.lib().rs2_sliver_checker_recover_device_async(
+            self.handle, m, ax.ctypes.data, sz.ctypes.data_as(u16), counts.ctypes.data_as(u32),
+            idx.ctypes.data_as(u16), d_symbols_base or None, s_off.ctypes.data_as(u64),
+            exp.ctypes.data if exp is not None else None, d_slivers_base or None,
+            o_off.ctypes.data_as(u64), d_roots or None, d_verdict or None, st, _stream(stream))
+        if statuses:
+            _ok(rc)
+            return list(st)[:m]
+        return rc
+
+    def check_recovery_symbols_async(self, symbol_sizes: Sequence[int], counts: Sequence[int],
+                                     targets: Sequence[int], d_symbols_base: int,
+                                     symbols_off: Sequence[int], d_proofs: int,
+                                     d_expected_roots: int, d_ok: int,
+                                     stream: Optional[int] = None) -> int:
+        """rs2_sliver_checker_check_recovery_symbols_device_async (returns the status code)."""
+        m = len(counts)
+        return _lib.lib().rs2_sliver_checker_check_recovery_symbols_device_async(
+            self.handle, m, (ctypes.c_uint16 * max(m, 1))(*symbol_sizes),
+            (ctypes.c_uint32 * max(m, 1))(*counts), (ctypes.c_uint16 * max(m, 1))(*targets),
+            d_symbols_base or None, (ctypes.c_uint64 * max(m, 1))(*symbols_off),
+            d_proofs or None, d_expected_roots or None, d_ok or None, _stream(stream))
+
     def __del__(self):
         h = getattr(self, "handle", None)
         if h and h.value and _lib._LIB is not None:
@@ -1090,6 +1135,16 @@ def recover_stats() -> Dict[str, int]:
     out = (ctypes.c_uint64 * 3)()
     _ok(_lib.lib().rs2_recover_stats(out))
     return dict(zip(("launches", "batched", "single"), (int(v) for v in out)))
+
+
+def recover_mixed_stats() -> Dict[str, int]:
+    """rs2_recover_mixed_stats: windows of the mixed sliver-recovery calls, decode range launches,
+    slivers decoded inside them, slivers that took the per-sliver decode path and groups (distinct
+    axis / symbol size pairs inside windows) (process-wide)."""
+    out = (ctypes.c_uint64 * 5)()
+    _ok(_lib.lib().rs2_recover_mixed_stats(out))
+    return dict(zip(("windows", "launches", "batched", "single", "groups"),
+                    (int(v) for v in out)))
 
 
 def recovery_symbols_stats() -> Dict[str, int]:

@@ -458,6 +458,101 @@ def recover_slivers_or_generate_inconsistency_proofs(config, requests, axis: str
     return out
 
 
+def recover_slivers_of_blobs(config, requests):
+    """recover_sliver_or_generate_inconsistency_proof (slivers.rs:341-379) for requests
+    (verified recovery symbols, target index, metadata, axis) across blobs and axes: one
+    rs2_recover_slivers_mixed call decodes every request with its own symbol size and verifies
+    the recovered slivers against their metadata.  Per request what
+    recover_slivers_or_generate_inconsistency_proofs returns."""
+    n = config.n_shards
+    out: list = [None] * len(requests)
+    members = []
+    for i, (symbols, target, meta, axis) in enumerate(requests):
+        if target >= len(meta.hashes):
+            raise ValueError("IndexTooLarge")
+        need = config.n_symbols_for_recovery(axis)
+        taken = []
+        for r in symbols:
+            if len(taken) == need:
+                break
+            taken.append(r)
+        if len(taken) < need:  # slivers.rs:246-289 refuses before decoding
+            out[i] = SliverRecoveryError("DecodingFailure")
+            continue
+        members.append((i, taken, config.symbol_size_for_blob(meta.unencoded_length), need))
+    m = len(members)
+    if m == 0:
+        return out
+    # wrong-size symbols are dropped by the decoder (basic_encoding.rs:400-410)
+    usable = [[r for r in taken if len(r.data) == s] for _, taken, s, _ in members]
+    axes = np.array([_AXIS[requests[i][3]] for i, _, _, _ in members], dtype=np.uint8)
+    sizes = (ctypes.c_uint16 * m)(*[s for _, _, s, _ in members])
+    counts = (ctypes.c_uint32 * m)(*[len(u) for u in usable])
+    flat = [r for u in usable for r in u]
+    idx = (ctypes.c_uint16 * max(len(flat), 1))(*[r.index for r in flat])
+    keep = [np.frombuffer(bytes(r.data), dtype=np.uint8) for r in flat]
+    ptrs = (ctypes.c_void_p * max(len(flat), 1))(*[a.ctypes.data for a in keep])
+    expected = np.frombuffer(
+        b"".join(bytes(_sliver_hash(requests[i][2], n, requests[i][1], requests[i][3]))
+                 for i, _, _, _ in members), dtype=np.uint8)
+    bufs = [np.zeros(need * s, dtype=np.uint8) for _, _, s, need in members]
+    outs = (ctypes.c_void_p * m)(*[b.ctypes.data for b in bufs])
+    verdict = np.zeros(m, dtype=np.int32)
+    status = (ctypes.c_int * m)()
+    _ok(_lib.lib().rs2_recover_slivers_mixed(n, m, axes.ctypes.data, sizes, counts, idx, ptrs,
+                                             expected.ctypes.data, outs, None,
+                                             verdict.ctypes.data, status))
+    for k, (i, taken, s, _) in enumerate(members):
+        axis = requests[i][3]
+        if status[k] != _lib.RS2_OK or verdict[k] == _lib.RS2_SLIVER_SKIPPED:
+            out[i] = SliverRecoveryError("DecodingFailure")
+        elif verdict[k] == _lib.RS2_SLIVER_MATCH:
+            out[i] = SliverData(Symbols(bufs[k].tobytes(), s), requests[i][1], axis)
+        else:
+            out[i] = InconsistencyProof(axis, requests[i][1], taken)
+    return out
+
+
+def verify_recovery_symbols_of_blobs(config, requests) -> List[List[bool]]:
+    """RecoverySymbol::verify (symbols.rs:617-642) for requests (metadata, target index, received
+    symbols, axis) across blobs and axes, as verify_recovery_symbols checks one axis: every
+    remaining symbol's proof root is formed and compared on the device in one
+    rs2_check_recovery_symbols_mixed call.  Returns one flag per symbol."""
+    n = config.n_shards
+    L = path_length(n)
+    out: List[List[bool]] = [[False] * len(req[2]) for req in requests]
+    members = []
+    for i, (meta, tgt, syms, _) in enumerate(requests):
+        if tgt >= n:
+            continue  # LeafIndexOutOfBounds for every symbol of the request
+        s = config.symbol_size_for_blob(meta.unencoded_length)
+        ok = [j for j, r in enumerate(syms)
+              if r.index < n and len(r.data) == s and len(r.proof.path) == L]
+        if ok:
+            members.append((i, ok, s))
+    m = len(members)
+    if m == 0:
+        return out
+    sizes = (ctypes.c_uint16 * m)(*[s for _, _, s in members])
+    counts = (ctypes.c_uint32 * m)(*[len(ok) for _, ok, _ in members])
+    tgts = (ctypes.c_uint16 * m)(*[requests[i][1] for i, _, _ in members])
+    picked = [(i, j, requests[i][2][j]) for i, ok, _ in members for j in ok]
+    keep = [np.frombuffer(bytes(r.data), dtype=np.uint8) for _, _, r in picked]
+    ptrs = (ctypes.c_void_p * len(picked))(*[a.ctypes.data for a in keep])
+    paths = np.frombuffer(b"".join(b"".join(r.proof.path) for _, _, r in picked) or b"\0" * 32,
+                          dtype=np.uint8)
+    roots = np.frombuffer(
+        b"".join(bytes(_sliver_hash(requests[i][0], n, r.index, _ORTHOGONAL[requests[i][3]]))
+                 for i, _, r in picked), dtype=np.uint8)
+    flags = np.zeros(len(picked), dtype=np.uint8)
+    _ok(_lib.lib().rs2_check_recovery_symbols_mixed(n, m, sizes, counts, tgts, ptrs,
+                                                    paths.ctypes.data, roots.ctypes.data,
+                                                    flags.ctypes.data))
+    for (i, j, _), f in zip(picked, flags):
+        out[i][j] = bool(f)
+    return out
+
+
 def try_recover_sliver_from_decoding_symbols(decoding_symbols: Sequence[DecodingSymbol],
                                              target_index: int, metadata: BlobMetadata, config,
                                              axis: str = PRIMARY) -> SliverData:
