@@ -723,6 +723,85 @@ int rs2_check_recovery_symbols_mixed(uint16_t n_shards, uint32_t n_slivers,
                                      const uint8_t* proofs, const uint8_t* expected_roots,
                                      uint8_t* ok_out);
 
+/* ---- recovery symbols across blobs: a symbol size, an axis and a target list per sliver --------
+ * rs2_verifier_recovery_symbols_multi_device_async for source slivers that share only n_shards:
+ * the serving half of a recovery.  A node that is asked for recovery symbols after an epoch
+ * change holds source slivers of about as many symbol sizes as blobs, on both axes.  Source sliver
+ * i (axis[i], symbol_size[i]; K = K_s / K_p as above) is K*symbol_size[i] bytes at d_slivers_base +
+ * sliver_off[i], read only.  Its target_counts[i] targets (orthogonal-axis indices, any order,
+ * repeats allowed, a count of 0 allowed) are consecutive in target_sliver_index; both are HOST
+ * arrays.  Target t of sliver i is request j = (sum of earlier counts, refused slivers' included)
+ * + t: its symbol goes to d_symbols_base + symbols_off[i] + t*symbol_size[i] -- a sliver's symbols
+ * back to back, the layout rs2_sliver_checker_check_recovery_symbols_device_async reads -- and its
+ * proof to d_proofs + j*path_len*32.  Sliver i's tree is at d_nodes + i*n_nodes*32 in
+ * MerkleTree::nodes order (path_len, n_nodes: rs2_merkle_tree_shape(n_shards)).  trees is
+ * RS2_TREES_BUILD or RS2_TREES_CACHED with the meaning given above: BUILD expands and hashes a
+ * sliver with targets and builds its tree once (with d_nodes non-NULL every accepted sliver, so
+ * all-zero counts warm the cache); CACHED requires d_nodes, never writes it, hashes nothing,
+ * expands only slivers with a repair target (>= K) and serves an all-systematic sliver by a copy
+ * out of the caller's sliver.  For every accepted sliver the symbol, proof and node bytes are bit
+ * for bit what rs2_verifier_recovery_symbols_multi_device_async writes for that sliver alone with
+ * the same targets on a verifier of (n_shards, symbol_size[i], axis[i]).  Nothing outside those
+ * extents is written, nothing outside the slivers (CACHED: and the accepted slivers' trees) is
+ * read.  Base pointers and offsets are 2-byte aligned, d_proofs and d_nodes 16-byte aligned.
+ * Per sliver, decided on the host before anything is enqueued, in this order: an axis that is
+ * not one of the two RS2_E_INVALID_ARGUMENT; symbol_size[i] 0 or odd
+ * RS2_E_INCOMPATIBLE_PARAMETERS; an odd sliver_off[i] or symbols_off[i] RS2_E_INVALID_ARGUMENT; a
+ * target >= n_shards RS2_E_INVALID_ARGUMENT (RecoverySymbolError::IndexTooLarge); host form only: a
+ * NULL or wrong-length sliver RS2_E_INCORRECT_DATA_LENGTH.  status_out NULL: the first failing
+ * sliver's code is returned and nothing is enqueued; non-NULL: failing slivers get their code and
+ * are skipped (their symbol extent, proof slots and node slot keep their bytes), the rest run,
+ * RS2_OK.  Whole-call refusals (RS2_E_INVALID_ARGUMENT): a NULL checker or needed array
+ * (target_sliver_index may be NULL when every count is 0), trees not one of the two values, CACHED
+ * with a NULL d_nodes, a misaligned pointer, more than 65535 slivers, more than 2^31-1 requests
+ * (summed in 64 bits).  n_slivers 0: RS2_OK, nothing enqueued.  The call never waits for the
+ * device and reads nothing back; the host arrays may be reused as soon as it returns.  Stream
+ * conventions as rs2_sliver_checker_verify_device_async.
+ *
+ * How it runs.  The slivers are taken in the caller's order in the windows of the mixed
+ * verification (budget: rs2_set_verify_mixed_budget; a sliver holds n*(s+32) bytes and with BUILD
+ * n_nodes*32 for its tree; at most RS2_VERIFY_MIXED_WINDOW_GROUPS groups).  Per window: one table
+ * upload; the slivers to expand are gathered and expanded by at most two group codec launches;
+ * with BUILD their leaves are hashed in one launch and their trees built in one, slot after slot
+ * into scratch, and one scatter launch moves them to the caller's order when d_nodes is given;
+ * one launch per 2^20 requests gathers each request's symbol (a systematic one from the caller's
+ * sliver in place) and sibling path through a per-slot record that names the sliver's own
+ * addresses, symbol size and K.  So a window makes at most RS2_SYMBOLS_MIXED_WINDOW_LAUNCHES
+ * compute launches however many sizes it holds.  Groups the group launch cannot take (s = 2,
+ * n_shards > 4096, more than 8 transform blocks) are expanded and hashed per size on the same
+ * stream; the same tree and request launches serve them.  rs2_verify_mixed_stats and
+ * rs2_recovery_symbols_stats are not touched.
+ * Measured (tools/symbols_mixed_probe.py, MI355X, n_shards = 1000, 128 slivers, 10 targets each,
+ * half of them systematic): 64 symbol sizes over 4 .. 300 alternating between the
+ * axes, two slivers each, BUILD into d_nodes: 0.792 ms (0.765 - 0.946; the call returns after
+ * 0.22 ms) against 11.310 ms (11.233 - 11.348) for 64
+ * rs2_verifier_recovery_symbols_multi_device_async calls, 14.3x (1 window, 128 slivers expanded,
+ * 128 trees built, 1280 requests, 7 launches); CACHED: 0.641 ms (0.620 - 0.653) against 5.100 ms
+ * (5.070 - 5.118), 8.0x (128 expanded, 128 trees from the cache, 4 launches).  Uniform, primary,
+ * s = 1206: 0.527 ms (0.514 - 0.547) against 0.430 ms (0.409 - 0.472) for the one verifier call
+ * with BUILD, 0.241 ms (0.240 - 0.242) against 0.223 ms (0.221 - 0.225) with CACHED: 22 % and 8 %
+ * slower, so a batch uniform in axis and size should keep that call. */
+#define RS2_SYMBOLS_MIXED_WINDOW_LAUNCHES 7
+int rs2_sliver_checker_recovery_symbols_device_async(
+    rs2_sliver_checker* c, uint32_t n_slivers, const uint8_t* axis, const uint16_t* symbol_size,
+    const void* d_slivers_base, const uint64_t* sliver_off, const uint32_t* target_counts,
+    const uint16_t* target_sliver_index, int trees, void* d_nodes, void* d_symbols_base,
+    const uint64_t* symbols_off, void* d_proofs, int* status_out, void* stream);
+/* Host form (blocking, RS2_TREES_BUILD, no trees handed out): slivers[i] / sliver_len[i] as
+ * rs2_verify_slivers_mixed; symbols_out[i] receives sliver i's target_counts[i] symbols back to
+ * back (may be NULL for a count of 0), proofs_out request j's path at j*path_len*32.  Slots of
+ * skipped slivers are not written. */
+int rs2_recovery_symbols_mixed(uint16_t n_shards, uint32_t n_slivers, const uint8_t* axis,
+                               const uint16_t* symbol_size, const uint8_t* const* slivers,
+                               const uint64_t* sliver_len, const uint32_t* target_counts,
+                               const uint16_t* target_sliver_index, uint8_t* const* symbols_out,
+                               uint8_t* proofs_out, int* status_out);
+/* Process-wide counters of the mixed recovery-symbol calls, stats_out[6]: windows; slivers
+ * expanded; trees built; trees served from the caller's cache (CACHED: accepted slivers with a
+ * request); requests served; compute launches of the group path (the per-size path's own launches
+ * are not counted).  No reference counterpart. */
+int rs2_symbols_mixed_stats(uint64_t* stats_out);
+
 /* RecoverySymbol::verify's proof step (symbols.rs:617-642; merkle.rs:78-99,150-169) for every
  * received symbol of a recovery call, grouped and laid out as above: sliver i's counts[i]
  * symbols all authenticate leaf target_index[i] (HOST; the target sliver's index on the

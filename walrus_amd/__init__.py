@@ -42,6 +42,7 @@ from .encoding import (  # noqa: F401
     sliver_merkle_roots,
     sliver_merkle_roots_mixed,
     source_symbols_for_n_shards,
+    symbols_mixed_stats,
     verify_batch_stats,
     verify_mixed_stats,
     verify_slivers,
@@ -59,6 +60,7 @@ from .recovery import (  # noqa: F401
     recovery_symbol_for_sliver,
     recovery_symbols_for_requests,
     recovery_symbols_for_targets,
+    recovery_symbols_of_blobs,
     try_recover_sliver_from_decoding_symbols,
     verify_recovery_symbols,
     verify_recovery_symbols_of_blobs,

@@ -198,6 +198,16 @@ SIGNATURES = {
         ctypes.c_int,
         [ctypes.c_uint16, ctypes.c_uint32, _u16p, ctypes.POINTER(ctypes.c_uint32), _u16p,
          ctypes.POINTER(_vp), _vp, _vp, _vp]),
+    "rs2_sliver_checker_recovery_symbols_device_async": (
+        ctypes.c_int,
+        [_vp, ctypes.c_uint32, _vp, _u16p, _vp, _u64p, ctypes.POINTER(ctypes.c_uint32), _u16p,
+         ctypes.c_int, _vp, _vp, _u64p, _vp, ctypes.POINTER(ctypes.c_int), _vp]),
+    "rs2_recovery_symbols_mixed": (
+        ctypes.c_int,
+        [ctypes.c_uint16, ctypes.c_uint32, _vp, _u16p, ctypes.POINTER(_vp), _u64p,
+         ctypes.POINTER(ctypes.c_uint32), _u16p, ctypes.POINTER(_vp), _vp,
+         ctypes.POINTER(ctypes.c_int)]),
+    "rs2_symbols_mixed_stats": (ctypes.c_int, [ctypes.POINTER(ctypes.c_uint64)]),
     "rs2_verifier_profile_enable": (ctypes.c_int, [_vp, ctypes.c_int]),
     "rs2_verifier_profile_read": (
         ctypes.c_int,

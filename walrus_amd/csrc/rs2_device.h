@@ -220,4 +220,22 @@ struct SymbolLevels {
   uint32_t base[kSymbolLevels];
 };
 
+// Mixed recovery symbols (symbol_requests_slots_kernel): a slot of the window, i.e. a source sliver
+// with its own symbol size and axis.  sys: its K systematic symbols (the caller's sliver, in
+// place); rep: its n - K repair symbols (null when the sliver was not expanded: no request of it
+// asks for one); nodes: its tree in MerkleTree::nodes order (the window's scratch, or the caller's
+// cached slot); sym: where its first request's symbol goes, the others behind it back to back;
+// first_request: that request's index in the call.  Read wave-uniformly, once per request.
+struct SymbolSlot {
+  const uint8_t* sys;
+  const uint8_t* rep;
+  const uint8_t* nodes;
+  uint8_t* sym;
+  uint32_t first_request;
+  uint16_t s, k;
+};
+static_assert(sizeof(SymbolSlot) == 40, "symbol slots are packed");
+// request table entry of a sliver refused on the host: the wave that draws it leaves
+constexpr uint32_t kRequestSkipped = 0xFFFFFFFFu;
+
 }  // namespace rs2

@@ -1492,6 +1492,7 @@ struct rs2_sliver_checker {
   DecodeSlot rdec[2];
   int rdec_slot = 0;
   DevBuf per_sliver, sym_digests;
+  DevBuf nodes;  // mixed recovery symbols: a window's trees, slot after slot
   Event done;  // as rs2_verifier::done
   ~rs2_sliver_checker() {
     if (stream) (void)hipStreamDestroy(stream);
@@ -4523,6 +4524,92 @@ MixedTables mixed_tables(const rs2_sliver_checker* c, const SliverWindow& w, boo
   return t;
 }
 
+// Window w's slot, leaf-group, job, tile and position-offset tables into h_tab (laid out by t;
+// d_tab: where they will lie on the device).  src(i): the device address of the caller's sliver i.
+// *chunks_out: the 4 KiB chunks of the window's gather launch.
+template <class SrcF>
+int pack_group_tables(const rs2_sliver_checker* c, const SliverWindow& w, SrcF src,
+                      const MixedTables& t, uint8_t* h_tab, const uint8_t* d_tab, uint8_t* gath,
+                      uint8_t* rep, uint64_t* chunks_out) {
+  const int64_t n = c->n;
+  // slots: where each sliver comes from and goes to, and its chunks of the gather
+  SliverSlot* slots = reinterpret_cast<SliverSlot*>(h_tab + t.slots);
+  uint64_t chunks = 0;
+  for (const SliverGroup& g : w.groups) {
+    const uint64_t len = uint64_t(g.k) * g.s;
+    for (uint32_t q = 0; q < g.count; ++q) {
+      SliverSlot& sl = slots[g.first_slot + q];
+      sl.src = src(w.perm[g.first_slot + q]);
+      sl.dst_off = g.gather_off + q * len;
+      sl.len = uint32_t(len);
+      sl.chunk0 = uint32_t(chunks);
+      chunks += (len + 4095) / 4096;
+      if (chunks > 0x7FFFFFFFu) return fail(RS2_E_UNSUPPORTED, "window exceeds the launch grid");
+    }
+  }
+  slots[w.n_slots].chunk0 = uint32_t(chunks);
+  *chunks_out = chunks;
+  // eligible groups: leaf table, jobs, tiles, position offsets
+  SliverLeafGroup* lg = reinterpret_cast<SliverLeafGroup*>(h_tab + t.groups);
+  CodecJobBatch* jobs = reinterpret_cast<CodecJobBatch*>(h_tab + t.jobs);
+  int64_t* offs = reinterpret_cast<int64_t*>(h_tab + t.offs);
+  const int64_t* d_offs = reinterpret_cast<const int64_t*>(d_tab + t.offs);
+  const uint32_t ne = w.axis_groups[0] + w.axis_groups[1];
+  size_t off_at = 0;
+  for (uint32_t p = 0; p < ne; ++p) {
+    const SliverGroup& g = w.groups[p];
+    const SliverAxisCode& code = c->codes[g.axis];
+    const PlannedJob& tp = code.tmpl;
+    const int64_t s = g.s, k = g.k;
+    lg[p] = {gath + g.gather_off, rep + g.repair_off, g.first_slot, g.count, g.k, g.s};
+    CodecJobBatch j = code.job;
+    j.symbol_size = int32_t(s);
+    j.n_pairs = int32_t((s + 3) / 4);
+    j.pairs_span = g.pairs_span;
+    j.n_lines = int32_t(g.count);
+    for (int b = 0; b < j.n_in; ++b) {
+      j.in[b].base = gath + g.gather_off;
+      j.in[b].line_stride = k * s;
+      j.in[b].pos_off = d_offs + off_at + tp.in_off(b);
+    }
+    for (int o = 0; o < j.n_out; ++o) {
+      j.out[o].base = rep + g.repair_off;
+      j.out[o].line_stride = (n - k) * s;
+      j.out[o].pos_off = d_offs + off_at + tp.out_off(o);
+    }
+    jobs[p] = j;
+    for (size_t q = 0; q < tp.offs.size(); ++q)
+      offs[off_at + q] = tp.offs[q] < 0 ? int64_t(-1) : tp.offs[q] * s;
+    off_at += tp.offs.size();
+  }
+  lg[ne].first_slot = w.n_eligible_slots;
+  for (int a = 0; a < 2; ++a)
+    std::memcpy(h_tab + t.tiles[a], w.tiles[a].data(), w.tiles[a].size() * 4);
+  return RS2_OK;
+}
+
+// The expansion of window w from its uploaded tables, on st: the gather of its slots and the
+// encode launch of each axis with eligible groups.  *launches counts them.
+int launch_group_expand(const rs2_sliver_checker* c, const SliverWindow& w, const MixedTables& t,
+                        const uint8_t* d_tab, uint8_t* gath, uint64_t chunks, hipStream_t st,
+                        uint64_t* launches) {
+  if (w.n_slots) {
+    HIP_TRY(rs2k_launch_sliver_gather(reinterpret_cast<const SliverSlot*>(d_tab + t.slots),
+                                      int(w.n_slots), int64_t(chunks), gath, st));
+    ++*launches;
+  }
+  for (int a = 0; a < 2; ++a) {
+    if (!w.axis_groups[a]) continue;
+    const PlannedJob& tp = c->codes[a].tmpl;
+    HIP_TRY(launch_encode_groups(
+        tp.C, reinterpret_cast<const CodecJobBatch*>(d_tab + t.jobs) + w.axis_first[a],
+        reinterpret_cast<const uint32_t*>(d_tab + t.tiles[a]), int(w.axis_groups[a]),
+        int(w.tiles[a].back()), tp.n_z, tp.mode, st));
+    ++*launches;
+  }
+  return RS2_OK;
+}
+
 // Run a planned call on st.  src(i): the device address of the caller's sliver i (accepted ones
 // only).  expected / d_roots / d_verdict are indexed by the caller's sliver.  Every buffer is
 // sized for the call's largest window before the first window runs.  before(w) runs on st ahead
@@ -4560,58 +4647,9 @@ int checker_run(rs2_sliver_checker* c, const SliverGroupsPlan& plan, SrcF src,
     RS2_TRY(before(w));
     const MixedTables t = mixed_tables(c, w, d_verdict != nullptr);
     h_tab.assign(t.bytes, 0);
-    // slots: where each sliver comes from and goes to, and its chunks of the gather
-    SliverSlot* slots = reinterpret_cast<SliverSlot*>(h_tab.data() + t.slots);
     uint64_t chunks = 0;
-    for (const SliverGroup& g : w.groups) {
-      const uint64_t len = uint64_t(g.k) * g.s;
-      for (uint32_t q = 0; q < g.count; ++q) {
-        SliverSlot& sl = slots[g.first_slot + q];
-        sl.src = src(w.perm[g.first_slot + q]);
-        sl.dst_off = g.gather_off + q * len;
-        sl.len = uint32_t(len);
-        sl.chunk0 = uint32_t(chunks);
-        chunks += (len + 4095) / 4096;
-        if (chunks > 0x7FFFFFFFu) return fail(RS2_E_UNSUPPORTED, "window exceeds the launch grid");
-      }
-    }
-    slots[w.n_slots].chunk0 = uint32_t(chunks);
-    // eligible groups: leaf table, jobs, tiles, position offsets
-    SliverLeafGroup* lg = reinterpret_cast<SliverLeafGroup*>(h_tab.data() + t.groups);
-    CodecJobBatch* jobs = reinterpret_cast<CodecJobBatch*>(h_tab.data() + t.jobs);
-    int64_t* offs = reinterpret_cast<int64_t*>(h_tab.data() + t.offs);
-    const int64_t* d_offs = reinterpret_cast<const int64_t*>(d_tab + t.offs);
+    RS2_TRY(pack_group_tables(c, w, src, t, h_tab.data(), d_tab, gath, rep, &chunks));
     const uint32_t ne = w.axis_groups[0] + w.axis_groups[1];
-    size_t off_at = 0;
-    for (uint32_t p = 0; p < ne; ++p) {
-      const SliverGroup& g = w.groups[p];
-      const SliverAxisCode& code = c->codes[g.axis];
-      const PlannedJob& tp = code.tmpl;
-      const int64_t s = g.s, k = g.k;
-      lg[p] = {gath + g.gather_off, rep + g.repair_off, g.first_slot, g.count, g.k, g.s};
-      CodecJobBatch j = code.job;
-      j.symbol_size = int32_t(s);
-      j.n_pairs = int32_t((s + 3) / 4);
-      j.pairs_span = g.pairs_span;
-      j.n_lines = int32_t(g.count);
-      for (int b = 0; b < j.n_in; ++b) {
-        j.in[b].base = gath + g.gather_off;
-        j.in[b].line_stride = k * s;
-        j.in[b].pos_off = d_offs + off_at + tp.in_off(b);
-      }
-      for (int o = 0; o < j.n_out; ++o) {
-        j.out[o].base = rep + g.repair_off;
-        j.out[o].line_stride = (n - k) * s;
-        j.out[o].pos_off = d_offs + off_at + tp.out_off(o);
-      }
-      jobs[p] = j;
-      for (size_t q = 0; q < tp.offs.size(); ++q)
-        offs[off_at + q] = tp.offs[q] < 0 ? int64_t(-1) : tp.offs[q] * s;
-      off_at += tp.offs.size();
-    }
-    lg[ne].first_slot = w.n_eligible_slots;
-    for (int a = 0; a < 2; ++a)
-      std::memcpy(h_tab.data() + t.tiles[a], w.tiles[a].data(), w.tiles[a].size() * 4);
     uint32_t* slot_of = reinterpret_cast<uint32_t*>(h_tab.data() + t.slot_of);
     std::fill(slot_of, slot_of + w.count, kSliverSkipped);
     for (uint32_t sl = 0; sl < w.n_slots; ++sl) slot_of[w.perm[sl] - w.first] = sl;
@@ -4619,20 +4657,7 @@ int checker_run(rs2_sliver_checker* c, const SliverGroupsPlan& plan, SrcF src,
       std::memcpy(h_tab.data() + t.expected, expected + size_t(w.first) * 32, size_t(w.count) * 32);
     RS2_TRY(upload_pieces(ctx, d_tab, h_tab.data(), t.bytes, st));
     uint64_t launches = 0;
-    if (w.n_slots) {
-      HIP_TRY(rs2k_launch_sliver_gather(reinterpret_cast<const SliverSlot*>(d_tab + t.slots),
-                                        int(w.n_slots), int64_t(chunks), gath, st));
-      ++launches;
-    }
-    for (int a = 0; a < 2; ++a) {
-      if (!w.axis_groups[a]) continue;
-      const PlannedJob& tp = c->codes[a].tmpl;
-      HIP_TRY(launch_encode_groups(
-          tp.C, reinterpret_cast<const CodecJobBatch*>(d_tab + t.jobs) + w.axis_first[a],
-          reinterpret_cast<const uint32_t*>(d_tab + t.tiles[a]), int(w.axis_groups[a]),
-          int(w.tiles[a].back()), tp.n_z, tp.mode, st));
-      ++launches;
-    }
+    RS2_TRY(launch_group_expand(c, w, t, d_tab, gath, chunks, st, &launches));
     if (w.n_eligible_slots) {
       HIP_TRY(rs2k_launch_leaf_hash_groups(reinterpret_cast<const SliverLeafGroup*>(d_tab + t.groups),
                                            int(ne), int(w.n_eligible_slots), int(n),
@@ -5174,6 +5199,298 @@ int rs2_check_recovery_symbols_mixed(uint16_t n_shards, uint32_t n_slivers,
   HIP_TRY(hipStreamSynchronize(st));
   std::memcpy(ok_out, c->h_out.p, total);
   return RS2_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------
+// mixed recovery symbols: source slivers that share only n_shards, each with its own axis, symbol
+// size and list of targets
+// ---------------------------------------------------------------------------------------------
+namespace {
+std::atomic<uint64_t> g_sm_windows{0}, g_sm_expanded{0}, g_sm_built{0}, g_sm_cached{0},
+    g_sm_requests{0}, g_sm_launches{0};
+
+// Run a planned mixed recovery-symbol call on st.  src(i): the device address of the caller's
+// sliver i; sym(i): where its first symbol goes.  Per window: one table upload (the group tables
+// of the slivers to expand, the slot records, the scatter's index and the first chunk of the
+// request table), the expansion (gather, encode groups; the other groups through the per-size
+// verifier into the same repair buffer), with BUILD the leaves and the trees in slot order, the
+// scatter to the caller's order when d_nodes is given, and the requests in chunks.
+template <class SrcF, class SymF>
+int symbols_mixed_run(rs2_sliver_checker* c, const SymbolsMixedPlan& plan, const uint8_t* axis,
+                      const uint16_t* symbol_size, int trees, SrcF src, SymF sym, uint8_t* d_nodes,
+                      uint8_t* d_proofs, hipStream_t st) {
+  Context* ctx = c->ctx;
+  const int64_t n = c->n, nn = int64_t(plan.n_nodes);
+  const bool build = trees == RS2_TREES_BUILD;
+  if (plan.accepted == 0) return RS2_OK;  // every sliver refused: nothing is enqueued
+  // a previous call on another stream still owns the scratch buffers and tables
+  HIP_TRY(c->done.wait_on(st));
+  RS2_TRY(checker_bind(c, st));
+  // a window's tables: mixed_tables' layout for its expanded slivers, then its own parts
+  struct Parts {
+    MixedTables t;
+    size_t sym_slots = 0, scatter = 0, requests = 0, bytes = 0;
+    uint64_t other_repair = 0;  // repair bytes of the groups outside the group launches
+  };
+  auto parts_of = [&](const SymbolsMixedWindow& w) {
+    Parts p;
+    p.t = mixed_tables(c, w.ex, false);
+    size_t at = p.t.bytes;
+    auto take = [&](size_t b) {
+      const size_t here = at;
+      at += (b + 15) / 16 * 16;
+      return here;
+    };
+    p.sym_slots = take(size_t(w.n_slots) * sizeof(SymbolSlot));
+    p.scatter = take(size_t(w.ex.n_slots) * 4);
+    p.requests = take(size_t(std::min(w.n_requests, kRequestChunk)) * 4);
+    p.bytes = std::max<size_t>(at, 16);
+    for (size_t g = size_t(w.ex.axis_groups[0]) + w.ex.axis_groups[1]; g < w.ex.groups.size(); ++g)
+      p.other_repair += uint64_t(w.ex.groups[g].count) * uint64_t(n - w.ex.groups[g].k) * w.ex.groups[g].s;
+    return p;
+  };
+  uint64_t max_gather = 0, max_repair = 0;
+  uint32_t max_ex = 0;
+  size_t max_tab = 0;
+  for (const SymbolsMixedWindow& w : plan.windows) {
+    const Parts p = parts_of(w);
+    max_gather = std::max(max_gather, w.ex.gather_bytes);
+    max_repair = std::max(max_repair, w.ex.repair_bytes + p.other_repair);
+    max_ex = std::max(max_ex, w.ex.n_slots);
+    max_tab = std::max(max_tab, p.bytes);
+  }
+  HIP_TRY(c->gathered.ensure(std::max<uint64_t>(max_gather, 16)));
+  HIP_TRY(c->repair.ensure(std::max<uint64_t>(max_repair, 16)));
+  if (build) {
+    HIP_TRY(c->leaves.ensure(std::max<size_t>(size_t(max_ex) * size_t(n) * 32, 16)));
+    HIP_TRY(c->slot_roots.ensure(std::max<size_t>(size_t(max_ex) * 32, 16)));
+    HIP_TRY(c->nodes.ensure(std::max<size_t>(size_t(max_ex) * size_t(nn) * 32, 16)));
+  }
+  HIP_TRY(c->tables.ensure(max_tab));
+  uint8_t* const gath = c->gathered.as<uint8_t>();
+  uint8_t* const rep = c->repair.as<uint8_t>();
+  uint8_t* const d_tab = c->tables.as<uint8_t>();
+  uint8_t* const tree_nodes = c->nodes.as<uint8_t>();
+  SymbolLevels lv;
+  std::copy(plan.level_base, plan.level_base + kSymbolLevels, lv.base);
+  std::vector<uint8_t> h_tab;
+  for (const SymbolsMixedWindow& w : plan.windows) {
+    if (w.n_slots == 0) continue;  // refused slivers only: no work, not counted
+    const SliverWindow& ex = w.ex;
+    const Parts p = parts_of(w);
+    h_tab.assign(p.bytes, 0);
+    uint64_t chunks = 0;
+    RS2_TRY(pack_group_tables(c, ex, src, p.t, h_tab.data(), d_tab, gath, rep, &chunks));
+    const uint32_t ne = ex.axis_groups[0] + ex.axis_groups[1];
+    // slot records: expanded slots find their repair symbols in the window's repair buffer
+    SymbolSlot* ss = reinterpret_cast<SymbolSlot*>(h_tab.data() + p.sym_slots);
+    for (uint32_t sl = 0; sl < w.n_slots; ++sl) {
+      const uint32_t i = w.perm[sl];
+      ss[sl].sys = src(i);
+      ss[sl].rep = nullptr;
+      // (BUILD: a slot that is not expanded has no request, hence no tree)
+      ss[sl].nodes = !build               ? d_nodes + int64_t(i) * nn * 32
+                     : sl < ex.n_slots    ? tree_nodes + int64_t(sl) * nn * 32
+                                          : nullptr;
+      ss[sl].sym = sym(i);
+      ss[sl].first_request = w.slot_request[sl];
+      ss[sl].s = symbol_size[i];
+      ss[sl].k = uint16_t(c->codes[axis[i]].k);
+    }
+    uint64_t other_at = ex.repair_bytes;
+    std::vector<uint8_t*> other_rep(ex.groups.size(), nullptr);
+    for (size_t g = 0; g < ex.groups.size(); ++g) {
+      const SliverGroup& gr = ex.groups[g];
+      const uint64_t rl = uint64_t(n - gr.k) * gr.s;
+      uint8_t* grep = rep + gr.repair_off;
+      if (g >= ne) {
+        grep = other_rep[g] = rep + other_at;
+        other_at += gr.count * rl;
+      }
+      for (uint32_t q = 0; q < gr.count; ++q) ss[gr.first_slot + q].rep = grep + q * rl;
+    }
+    const bool scatter = build && d_nodes && ex.n_slots;
+    uint32_t* dst_index = reinterpret_cast<uint32_t*>(h_tab.data() + p.scatter);
+    for (uint32_t sl = 0; sl < ex.n_slots; ++sl) dst_index[sl] = w.perm[sl];
+    const uint32_t chunk0 = std::min(w.n_requests, kRequestChunk);
+    std::memcpy(h_tab.data() + p.requests, plan.table.data() + w.first_request, size_t(chunk0) * 4);
+    RS2_TRY(upload_pieces(ctx, d_tab, h_tab.data(), p.bytes, st));
+    uint64_t launches = 0;
+    RS2_TRY(launch_group_expand(c, ex, p.t, d_tab, gath, chunks, st, &launches));
+    // the other groups: the per-size verifier on the same stream, from their gathered copies
+    rs2_verifier* v = c->single;
+    for (size_t g = ne; g < ex.groups.size(); ++g) {
+      const SliverGroup& gr = ex.groups[g];
+      v->s = uint16_t(gr.s);
+      v->k = uint16_t(gr.k);
+      v->axis = gr.axis;
+      if (n > int64_t(gr.k))
+        RS2_TRY(verifier_expand(v, gath + gr.gather_off, other_rep[g], gr.count, st));
+      if (build) {
+        SymbolMap map{gath + gr.gather_off, other_rep[g], nullptr, int(n), int(gr.count),
+                      int(gr.k), int(gr.s)};
+        HIP_TRY(rs2k_launch_leaf_hash(map, 4, int64_t(gr.count) * n, 1,
+                                      c->leaves.as<uint8_t>() + int64_t(gr.first_slot) * n * 32, st));
+      }
+    }
+    if (ne < ex.groups.size()) RS2_TRY(verifier_mark_done(v, st));
+    if (build && ex.n_slots) {
+      if (ex.n_eligible_slots) {
+        HIP_TRY(rs2k_launch_leaf_hash_groups(
+            reinterpret_cast<const SliverLeafGroup*>(d_tab + p.t.groups), int(ne),
+            int(ex.n_eligible_slots), int(n), c->leaves.as<uint8_t>(), st));
+        ++launches;
+      }
+      // every expanded slot's tree at once: leaves and trees are uniform over the window
+      HIP_TRY(rs2k_launch_merkle_trees(c->leaves.as<uint8_t>(), int(n), int(ex.n_slots), 0, n * 32,
+                                       32, 0, 0, c->slot_roots.as<uint8_t>(), 32, st, tree_nodes,
+                                       nn * 32));
+      if (n <= int64_t(kGroupMaxLeaves)) ++launches;
+    }
+    if (scatter) {
+      HIP_TRY(rs2k_launch_tree_nodes_scatter(tree_nodes,
+                                             reinterpret_cast<const uint32_t*>(d_tab + p.scatter),
+                                             int(ex.n_slots), nn, d_nodes, st));
+      ++launches;
+    }
+    // (a window whose requests all belong to refused slivers launches nothing)
+    for (uint32_t c0 = 0; w.served && c0 < w.n_requests; c0 += kRequestChunk) {
+      const uint32_t cn = std::min(kRequestChunk, w.n_requests - c0);
+      const int64_t r0 = int64_t(w.first_request) + c0;
+      if (c0)  // the later chunks take the first one's place, in stream order
+        RS2_TRY(upload_pieces(ctx, d_tab + p.requests, plan.table.data() + r0, size_t(cn) * 4, st));
+      HIP_TRY(rs2k_launch_symbol_requests_slots(
+          reinterpret_cast<const SymbolSlot*>(d_tab + p.sym_slots), int(w.n_slots),
+          reinterpret_cast<const uint32_t*>(d_tab + p.requests), cn, r0, plan.path_len, lv,
+          d_proofs, st));
+      ++launches;
+    }
+    g_sm_windows.fetch_add(1, std::memory_order_relaxed);
+    g_sm_expanded.fetch_add(ex.n_slots, std::memory_order_relaxed);
+    g_sm_built.fetch_add(build ? ex.n_slots : 0, std::memory_order_relaxed);
+    g_sm_cached.fetch_add(build ? 0 : w.with_requests, std::memory_order_relaxed);
+    g_sm_requests.fetch_add(w.served, std::memory_order_relaxed);
+    g_sm_launches.fetch_add(launches, std::memory_order_relaxed);
+  }
+  HIP_TRY(c->done.record(st));
+  return RS2_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int rs2_sliver_checker_recovery_symbols_device_async(
+    rs2_sliver_checker* c, uint32_t n_slivers, const uint8_t* axis, const uint16_t* symbol_size,
+    const void* d_slivers_base, const uint64_t* sliver_off, const uint32_t* target_counts,
+    const uint16_t* target_sliver_index, int trees, void* d_nodes, void* d_symbols_base,
+    const uint64_t* symbols_off, void* d_proofs, int* status_out, void* stream) {
+  if (!c) return fail(RS2_E_INVALID_ARGUMENT, "null checker");
+  if (trees != RS2_TREES_BUILD && trees != RS2_TREES_CACHED)
+    return fail(RS2_E_INVALID_ARGUMENT, "trees must be RS2_TREES_BUILD or RS2_TREES_CACHED");
+  bool empty;
+  RS2_TRY(batch_count(n_slivers, "slivers in a call",
+                      axis && symbol_size && d_slivers_base && sliver_off && target_counts &&
+                          symbols_off,
+                      &empty));
+  if (empty) return RS2_OK;
+  RS2_TRY(check_symbol_ptr(d_slivers_base, "d_slivers_base"));
+  RS2_TRY(check_symbol_ptr(d_symbols_base, "d_symbols_base"));
+  RS2_TRY(check_digest_ptr(d_proofs, "d_proofs"));
+  RS2_TRY(check_digest_ptr(d_nodes, "d_nodes"));
+  HIP_TRY(hipSetDevice(c->ctx->device));
+  hipStream_t st = abi_stream(stream, c->stream);
+  // every sliver is validated, and the call planned, before anything is enqueued (a target is
+  // remote input on a node)
+  RS2_TRY(checker_codes(c));
+  SymbolsMixedPlan plan;
+  RS2_TRY(plan_symbols_mixed(c->codes, n_slivers, axis, symbol_size, sliver_off, symbols_off,
+                             nullptr, nullptr, target_counts, target_sliver_index, trees,
+                             d_nodes != nullptr, g_vm_budget.load(std::memory_order_relaxed),
+                             kMixedWindowGroups, status_out, plan));
+  if (plan.total && (!d_symbols_base || (plan.path_len && !d_proofs)))
+    return fail(RS2_E_INVALID_ARGUMENT, "null argument");
+  const uint8_t* base = reinterpret_cast<const uint8_t*>(d_slivers_base);
+  uint8_t* out = reinterpret_cast<uint8_t*>(d_symbols_base);
+  return symbols_mixed_run(
+      c, plan, axis, symbol_size, trees, [&](uint32_t i) { return base + sliver_off[i]; },
+      [&](uint32_t i) { return out + symbols_off[i]; }, reinterpret_cast<uint8_t*>(d_nodes),
+      reinterpret_cast<uint8_t*>(d_proofs), st);
+}
+
+int rs2_recovery_symbols_mixed(uint16_t n_shards, uint32_t n_slivers, const uint8_t* axis,
+                               const uint16_t* symbol_size, const uint8_t* const* slivers,
+                               const uint64_t* sliver_len, const uint32_t* target_counts,
+                               const uint16_t* target_sliver_index, uint8_t* const* symbols_out,
+                               uint8_t* proofs_out, int* status_out) {
+  bool empty;
+  RS2_TRY(batch_count(n_slivers, "slivers in a call",
+                      axis && symbol_size && slivers && sliver_len && target_counts, &empty));
+  if (empty) return RS2_OK;
+  CheckerLease lease;
+  RS2_TRY(lease.get(n_shards));
+  rs2_sliver_checker* c = lease.c;
+  HIP_TRY(hipSetDevice(c->ctx->device));
+  hipStream_t st = c->stream;
+  RS2_TRY(checker_codes(c));
+  SymbolsMixedPlan plan;
+  RS2_TRY(plan_symbols_mixed(c->codes, n_slivers, axis, symbol_size, nullptr, nullptr, slivers,
+                             sliver_len, target_counts, target_sliver_index, RS2_TREES_BUILD, false,
+                             g_vm_budget.load(std::memory_order_relaxed), kMixedWindowGroups,
+                             status_out, plan));
+  // no trees to hand out, or every sliver refused: nothing to do
+  if (plan.total == 0 || plan.accepted == 0) return RS2_OK;
+  const size_t L = size_t(plan.path_len);
+  if (!symbols_out || (L && !proofs_out)) return fail(RS2_E_INVALID_ARGUMENT, "null argument");
+  // the accepted slivers back to back through pinned staging (one H2D); their symbols come back
+  // the same way, the proofs of all requests behind them (one D2H per output range)
+  std::vector<uint64_t> in_off(n_slivers, 0), out_off(n_slivers, 0);
+  std::vector<uint8_t> accepted(n_slivers, 0);
+  for (const SymbolsMixedWindow& w : plan.windows)
+    for (uint32_t i : w.perm) accepted[i] = 1;
+  uint64_t in_b = 0, sym_b = 0;
+  for (uint32_t i = 0; i < n_slivers; ++i) {
+    if (!accepted[i]) continue;
+    if (target_counts[i] && !symbols_out[i])
+      return fail(RS2_E_INVALID_ARGUMENT, "null symbol output");
+    in_off[i] = in_b;
+    in_b += sliver_len[i];
+    out_off[i] = sym_b;
+    sym_b += uint64_t(target_counts[i]) * symbol_size[i];
+  }
+  const size_t prf_at = (size_t(sym_b) + 15) / 16 * 16;
+  const size_t prf_b = size_t(plan.total) * L * 32, back_b = prf_at + prf_b;
+  HIP_TRY(c->input.ensure(std::max<uint64_t>(in_b, 16)));
+  HIP_TRY(c->h_in.ensure(std::max<uint64_t>(in_b, 16)));
+  HIP_TRY(c->out.ensure(std::max<size_t>(back_b, 16)));
+  HIP_TRY(c->h_out.ensure(std::max<size_t>(back_b, 16)));
+  for (uint32_t i = 0; i < n_slivers; ++i)
+    if (accepted[i])
+      std::memcpy(static_cast<uint8_t*>(c->h_in.p) + in_off[i], slivers[i], sliver_len[i]);
+  if (in_b) HIP_TRY(hipMemcpyAsync(c->input.p, c->h_in.p, in_b, hipMemcpyHostToDevice, st));
+  const uint8_t* din = c->input.as<uint8_t>();
+  uint8_t* dout = c->out.as<uint8_t>();
+  RS2_TRY(symbols_mixed_run(
+      c, plan, axis, symbol_size, RS2_TREES_BUILD, [&](uint32_t i) { return din + in_off[i]; },
+      [&](uint32_t i) { return dout + out_off[i]; }, nullptr, dout + prf_at, st));
+  uint8_t* ho = static_cast<uint8_t*>(c->h_out.p);
+  if (sym_b) HIP_TRY(hipMemcpyAsync(ho, dout, sym_b, hipMemcpyDeviceToHost, st));
+  if (prf_b) HIP_TRY(hipMemcpyAsync(ho + prf_at, dout + prf_at, prf_b, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  // symbol and proof slots of refused slivers are not written
+  uint64_t j = 0;
+  for (uint32_t i = 0; i < n_slivers; j += target_counts[i], ++i) {
+    if (!accepted[i] || !target_counts[i]) continue;
+    std::memcpy(symbols_out[i], ho + out_off[i], size_t(target_counts[i]) * symbol_size[i]);
+    if (L) std::memcpy(proofs_out + j * L * 32, ho + prf_at + j * L * 32, size_t(target_counts[i]) * L * 32);
+  }
+  return RS2_OK;
+}
+
+int rs2_symbols_mixed_stats(uint64_t* stats_out) {
+  return read_stats(stats_out, {&g_sm_windows, &g_sm_expanded, &g_sm_built, &g_sm_cached,
+                                &g_sm_requests, &g_sm_launches});
 }
 
 int rs2_merkle_root(const uint8_t* leaves, uint32_t n_leaves, uint32_t leaf_len, uint8_t root_out[32]) {

@@ -1030,6 +1030,88 @@ __global__ void __launch_bounds__(64 * kRequestWaves)
   }
 }
 
+// Mixed form of the above (rs2_sliver_checker_recovery_symbols_device_async), one window at a
+// time: the slivers share only n -- hence the tree shape, lv and path_len -- and entry i of the
+// launch, request r = r0 + i of the call, is requests[i] = slot << 16 | target (kRequestSkipped:
+// the request of a sliver refused on the host, nothing to do).  The slot's record (SymbolSlot)
+// names everything that is the sliver's own: its systematic symbols (the caller's sliver in
+// place), its repair symbols, its tree, its symbol size and K, and where its symbols go -- request
+// r's to sym + (r - first_request) * s, a sliver's symbols back to back.  One wave per request,
+// kRequestWaves requests per workgroup; the wave index is made uniform for the compiler, so the
+// entry and the record are scalar loads.
+//   symbol: copied as wide as the common alignment of source and destination allows, the rule of
+//     symbol_requests_kernel (restated, not shared: that kernel's resource metadata stays as it
+//     is): 16-byte or 4-byte pieces between 2-byte edges, or 2-byte pieces throughout.  No byte
+//     outside the symbol is read or written.
+//   proof: to proof_out + (r * path_len + l) * 32, lanes 2l and 2l + 1 the halves of sibling l.
+// Every byte offset is 64-bit.  No limit on s or on n (16 levels).
+__global__ void __launch_bounds__(64 * kRequestWaves)
+    symbol_requests_slots_kernel(const SymbolSlot* __restrict__ slots,
+                                 const uint32_t* __restrict__ requests, int64_t count, int64_t r0,
+                                 int path_len, SymbolLevels lv, uint8_t* __restrict__ proof_out) {
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(int(threadIdx.x >> 6));
+  const int64_t i = int64_t(blockIdx.x) * kRequestWaves + wave;
+  if (i >= count) return;
+  const uint32_t e = requests[i];
+  if (e == kRequestSkipped) return;
+  const SymbolSlot sl = slots[e >> 16];
+  const int t = int(e & 0xFFFFu);
+  const int64_t r = r0 + i;
+  const int s = sl.s, k = sl.k;
+  const uint8_t* src = t < k ? sl.sys + int64_t(t) * s : sl.rep + int64_t(t - k) * s;
+  uint8_t* dst = sl.sym + (r - int64_t(sl.first_request)) * s;
+  const uintptr_t apart = reinterpret_cast<uintptr_t>(src) ^ reinterpret_cast<uintptr_t>(dst);
+  const int W = (apart & 15) == 0 ? 16 : (apart & 3) == 0 ? 4 : 2;
+  // [0, head) and [mid_end, s) in 2-byte pieces, [head, mid_end) in W-byte pieces aligned on both
+  // sides
+  const int to_aligned = int((W - (reinterpret_cast<uintptr_t>(dst) & uintptr_t(W - 1))) & (W - 1));
+  const int head = to_aligned < s ? to_aligned : s;
+  const int mid = (s - head) / W;
+  const int mid_end = head + mid * W;
+  const int edge = (head + (s - mid_end)) / 2;
+  for (int q = lane; q < edge; q += 64) {
+    const int o = 2 * q < head ? 2 * q : 2 * q - head + mid_end;
+    *reinterpret_cast<uint16_t*>(dst + o) = *reinterpret_cast<const uint16_t*>(src + o);
+  }
+  if (W == 16) {
+    for (int q = lane; q < mid; q += 64)
+      reinterpret_cast<uint4*>(dst + head)[q] = reinterpret_cast<const uint4*>(src + head)[q];
+  } else if (W == 4) {
+    for (int q = lane; q < mid; q += 64)
+      reinterpret_cast<uint32_t*>(dst + head)[q] = reinterpret_cast<const uint32_t*>(src + head)[q];
+  } else {
+    for (int q = lane; q < mid; q += 64)
+      reinterpret_cast<uint16_t*>(dst + head)[q] = reinterpret_cast<const uint16_t*>(src + head)[q];
+  }
+  if (lane < 2 * path_len) {
+    const int l = lane >> 1;
+    uint32_t base = 0;
+    sfor<kSymbolLevels>([&](auto jj) {
+      constexpr int j = decltype(jj)::value;
+      base = l == j ? lv.base[j] : base;
+    });
+    const int64_t sib = int64_t(base) + ((t >> l) ^ 1);
+    const uint4* tn = reinterpret_cast<const uint4*>(sl.nodes + sib * 32);
+    reinterpret_cast<uint4*>(proof_out + (r * path_len + l) * 32)[lane & 1] = tn[lane & 1];
+  }
+}
+
+// The trees a mixed recovery-symbol window built, from slot order (merkle_trees_kernel writes
+// slot after slot into scratch) to the caller's order: slot y's n_nodes * 32 bytes go to
+// dst + dst_index[y] * n_nodes * 32, in 16-byte pieces (both sides are 16-byte aligned), a piece
+// per lane, bounded by the tree.
+__global__ void __launch_bounds__(256)
+    tree_nodes_scatter_kernel(const uint8_t* __restrict__ src, const uint32_t* __restrict__ dst_index,
+                              int64_t n_nodes, uint8_t* __restrict__ dst) {
+  const int64_t piece = int64_t(blockIdx.x) * 256 + threadIdx.x;
+  if (piece >= 2 * n_nodes) return;
+  const int64_t slot = blockIdx.y;
+  const uint4* from = reinterpret_cast<const uint4*>(src + slot * n_nodes * 32);
+  uint4* to = reinterpret_cast<uint4*>(dst + int64_t(dst_index[slot]) * n_nodes * 32);
+  to[piece] = from[piece];
+}
+
 // MerkleProof::compute_root (merkle.rs:150-169) for `count` proofs: start from leaf digest r,
 // climb path r (path_len nodes) by leaf_index[r]'s bits: inner(cur, sib) when the level index
 // is even, inner(sib, cur) when odd.  One lane per proof.
@@ -1609,6 +1691,32 @@ hipError_t rs2k_launch_symbol_requests(const uint8_t* d_sys, const uint8_t* d_re
   hipLaunchKernelGGL(rs2::symbol_requests_kernel, dim3(unsigned(wgs)),
                      dim3(64 * rs2::kRequestWaves), 0, stream, d_sys, d_rep, n, k, s, d_nodes,
                      nodes_stride, d_requests, count, path_len, levels, d_sym, d_proof);
+  return hipGetLastError();
+}
+
+hipError_t rs2k_launch_symbol_requests_slots(const rs2::SymbolSlot* d_slots, int n_slots,
+                                             const uint32_t* d_requests, int64_t count, int64_t r0,
+                                             int path_len, rs2::SymbolLevels levels,
+                                             uint8_t* d_proof, hipStream_t stream) {
+  if (count <= 0) return hipSuccess;
+  if (count > 0x7FFFFFFF || r0 < 0 || r0 + count > 0x7FFFFFFF || n_slots < 1 || n_slots > 65535 ||
+      path_len < 0 || path_len > rs2::kSymbolLevels)
+    return hipErrorInvalidValue;
+  const int64_t wgs = (count + rs2::kRequestWaves - 1) / rs2::kRequestWaves;
+  hipLaunchKernelGGL(rs2::symbol_requests_slots_kernel, dim3(unsigned(wgs)),
+                     dim3(64 * rs2::kRequestWaves), 0, stream, d_slots, d_requests, count, r0,
+                     path_len, levels, d_proof);
+  return hipGetLastError();
+}
+
+hipError_t rs2k_launch_tree_nodes_scatter(const uint8_t* d_src, const uint32_t* d_dst_index,
+                                          int n_slots, int64_t n_nodes, uint8_t* d_dst,
+                                          hipStream_t stream) {
+  if (n_slots <= 0) return hipSuccess;
+  if (n_slots > 65535 || n_nodes < 1 || n_nodes > (int64_t(1) << 30)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(rs2::tree_nodes_scatter_kernel,
+                     dim3(unsigned((2 * n_nodes + 255) / 256), unsigned(n_slots)), dim3(256), 0,
+                     stream, d_src, d_dst_index, n_nodes, d_dst);
   return hipGetLastError();
 }
 

@@ -110,6 +110,17 @@ hipError_t rs2k_launch_symbol_requests(const uint8_t* d_sys, const uint8_t* d_re
                                        const uint32_t* d_requests, int64_t count, int path_len,
                                        rs2::SymbolLevels levels, uint8_t* d_sym, uint8_t* d_proof,
                                        hipStream_t stream);
+// one window of a mixed recovery-symbol call: d_slots its n_slots SymbolSlot, d_requests `count`
+// entries (slot << 16 | target, or kRequestSkipped), the first of them request r0 of the call;
+// d_proof at the call's first request.  The scatter moves the window's trees from slot order
+// (d_src) to d_dst + d_dst_index[slot] * n_nodes * 32.
+hipError_t rs2k_launch_symbol_requests_slots(const rs2::SymbolSlot* d_slots, int n_slots,
+                                             const uint32_t* d_requests, int64_t count, int64_t r0,
+                                             int path_len, rs2::SymbolLevels levels,
+                                             uint8_t* d_proof, hipStream_t stream);
+hipError_t rs2k_launch_tree_nodes_scatter(const uint8_t* d_src, const uint32_t* d_dst_index,
+                                          int n_slots, int64_t n_nodes, uint8_t* d_dst,
+                                          hipStream_t stream);
 hipError_t rs2k_launch_proof_roots(const uint8_t* d_leaf_digests, const uint32_t* d_leaf_index,
                                    const uint8_t* d_paths, int path_len, int count,
                                    uint8_t* d_roots, hipStream_t stream);

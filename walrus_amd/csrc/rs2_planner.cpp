@@ -853,10 +853,12 @@ void close_sliver_window(const SliverAxisCode (&codes)[2], SliverWindow& w,
 
 // The windows of a mixed call over the slivers with ok[i] set (the caller validated them): the
 // rule of plan_sliver_groups, and a window also closes before the sliver that would make it hold
-// more than max_slivers accepted slivers.
+// more than max_slivers accepted slivers.  `extra`: scratch a sliver holds beyond
+// sliver_scratch_bytes (the mixed recovery symbols' slot-ordered trees).
 void window_slivers(const SliverAxisCode (&codes)[2], uint32_t n_slivers, const uint8_t* axis,
                     const uint16_t* symbol_size, const std::vector<uint8_t>& ok, uint64_t budget,
-                    uint32_t max_groups, uint32_t max_slivers, SliverGroupsPlan& plan) {
+                    uint32_t max_groups, uint32_t max_slivers, SliverGroupsPlan& plan,
+                    uint64_t extra = 0) {
   const uint32_t n = codes[0].n;
   SliverWindow w;
   std::vector<uint32_t> idx, grp;
@@ -876,7 +878,7 @@ void window_slivers(const SliverAxisCode (&codes)[2], uint32_t n_slivers, const 
   for (uint32_t i = 0; i < n_slivers; ++i) {
     if (!ok[i]) continue;  // a refused sliver holds nothing: it stays in the open window
     const uint32_t s = symbol_size[i], key = uint32_t(axis[i]) << 16 | s;
-    const uint64_t need = sliver_scratch_bytes(n, s);
+    const uint64_t need = sliver_scratch_bytes(n, s) + extra;
     auto it = open.find(key);
     // (need > budget - used, not used + need > budget: the sum may wrap)
     if (i > w.first && !idx.empty() &&
@@ -1026,6 +1028,108 @@ int plan_recover_mixed(const SliverAxisCode (&codes)[2], uint32_t n_slivers, con
     items.push_back(std::move(it));
   }
   window_slivers(codes, n_slivers, axis, symbol_size, ok, budget, max_groups, max_slivers, plan);
+  return RS2_OK;
+}
+
+int plan_symbols_mixed(const SliverAxisCode (&codes)[2], uint32_t n_slivers, const uint8_t* axis,
+                       const uint16_t* symbol_size, const uint64_t* sliver_off,
+                       const uint64_t* symbols_off, const uint8_t* const* slivers,
+                       const uint64_t* sliver_len, const uint32_t* target_counts,
+                       const uint16_t* targets, int trees, bool have_nodes, uint64_t budget,
+                       uint32_t max_groups, int* status_out, SymbolsMixedPlan& plan) {
+  plan = SymbolsMixedPlan{};
+  if (trees != RS2_TREES_BUILD && trees != RS2_TREES_CACHED)
+    return fail(RS2_E_INVALID_ARGUMENT, "trees must be RS2_TREES_BUILD or RS2_TREES_CACHED");
+  const bool build = trees == RS2_TREES_BUILD;
+  if (!build && !have_nodes)
+    return fail(RS2_E_INVALID_ARGUMENT, "RS2_TREES_CACHED needs the trees in d_nodes");
+  if (n_slivers > 65535) return fail(RS2_E_INVALID_ARGUMENT, "more than 65535 slivers in a call");
+  if (max_groups == 0 || codes[0].n == 0 || codes[0].n != codes[1].n)
+    return fail(RS2_E_INVALID_ARGUMENT, "not a sliver's code");
+  const uint32_t n = codes[0].n;
+  plan.path_len = merkle_level_bases(n, plan.level_base, &plan.n_nodes);
+  if (n_slivers == 0) return RS2_OK;
+  if (!axis || !symbol_size || !target_counts || (slivers != nullptr) != (sliver_len != nullptr))
+    return fail(RS2_E_INVALID_ARGUMENT, "null argument");
+  uint64_t total = 0;
+  for (uint32_t i = 0; i < n_slivers; ++i) {
+    total += target_counts[i];
+    if (total > 0x7FFFFFFFu) return fail(RS2_E_INVALID_ARGUMENT, "too many requests in a call");
+  }
+  if (total && !targets) return fail(RS2_E_INVALID_ARGUMENT, "null argument");
+  plan.total = total;
+  std::vector<uint8_t> ok(n_slivers, 0);
+  std::vector<uint32_t> first_req(n_slivers + 1, 0);
+  for (uint32_t i = 0; i < n_slivers; ++i) {
+    first_req[i + 1] = first_req[i] + target_counts[i];
+    auto check = [&]() -> int {
+      if (axis[i] != RS2_AXIS_PRIMARY && axis[i] != RS2_AXIS_SECONDARY)
+        return fail(RS2_E_INVALID_ARGUMENT, "bad axis");
+      const uint32_t s = symbol_size[i];
+      if (s == 0 || s % 2)
+        return fail(RS2_E_INCOMPATIBLE_PARAMETERS, "symbol_size must be a multiple of the required alignment");
+      if (sliver_off && sliver_off[i] % 2)
+        return fail(RS2_E_INVALID_ARGUMENT, "sliver_off[i] must be a multiple of 2 bytes");
+      if (symbols_off && symbols_off[i] % 2)
+        return fail(RS2_E_INVALID_ARGUMENT, "symbols_off[i] must be a multiple of 2 bytes");
+      for (uint32_t j = first_req[i]; j < first_req[i + 1]; ++j)
+        if (targets[j] >= n)  // slivers.rs check_index -> RecoverySymbolError::IndexTooLarge
+          return fail(RS2_E_INVALID_ARGUMENT, "target index too large");
+      if (slivers && (!slivers[i] || sliver_len[i] != uint64_t(codes[axis[i]].k) * s))
+        return fail(RS2_E_INCORRECT_DATA_LENGTH, "sliver length does not match its axis and symbol size");
+      return RS2_OK;
+    };
+    const int rc = check();
+    if (status_out) status_out[i] = rc;
+    else if (rc != RS2_OK) return rc;
+    ok[i] = rc == RS2_OK;
+    plan.accepted += ok[i];
+  }
+  // the windows: over every accepted sliver, whether or not it is expanded
+  SliverGroupsPlan cut;
+  window_slivers(codes, n_slivers, axis, symbol_size, ok, budget, max_groups, UINT32_MAX, cut,
+                 build ? plan.n_nodes * 32 : 0);
+  plan.table.assign(size_t(total), kRequestSkipped);
+  std::vector<uint8_t> expand;
+  for (const SliverWindow& cw : cut.windows) {
+    SymbolsMixedWindow w;
+    w.first = cw.first;
+    w.count = cw.count;
+    w.first_request = first_req[cw.first];
+    w.n_requests = first_req[cw.first + cw.count] - first_req[cw.first];
+    // the slivers to expand, laid out as a window of their own
+    expand.assign(cw.count, 0);
+    for (uint32_t q = 0; q < cw.count; ++q) {
+      const uint32_t i = cw.first + q;
+      if (!ok[i]) continue;
+      bool e = build && (have_nodes || target_counts[i] > 0);
+      const uint32_t k = codes[axis[i]].k;
+      for (uint32_t j = first_req[i]; j < first_req[i + 1] && !e; ++j) e = targets[j] >= k;
+      expand[q] = e;
+    }
+    SliverGroupsPlan ex;
+    window_slivers(codes, cw.count, axis + cw.first, symbol_size + cw.first, expand, UINT64_MAX,
+                   UINT32_MAX, UINT32_MAX, ex);
+    w.ex = std::move(ex.windows.front());
+    for (uint32_t& i : w.ex.perm) i += cw.first;
+    w.ex.first = cw.first;
+    w.perm = w.ex.perm;
+    for (uint32_t q = 0; q < cw.count; ++q)
+      if (ok[cw.first + q] && !expand[q]) w.perm.push_back(cw.first + q);
+    w.n_slots = uint32_t(w.perm.size());
+    w.slot_request.resize(w.n_slots);
+    w.slot_requests.resize(w.n_slots);
+    for (uint32_t slot = 0; slot < w.n_slots; ++slot) {
+      const uint32_t i = w.perm[slot];
+      w.slot_request[slot] = first_req[i];
+      w.slot_requests[slot] = target_counts[i];
+      w.served += target_counts[i];
+      w.with_requests += target_counts[i] > 0;
+      for (uint32_t j = first_req[i]; j < first_req[i + 1]; ++j)
+        plan.table[j] = slot << 16 | targets[j];
+    }
+    plan.windows.push_back(std::move(w));
+  }
   return RS2_OK;
 }
 

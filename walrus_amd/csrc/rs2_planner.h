@@ -530,4 +530,58 @@ int plan_recover_mixed(const SliverAxisCode (&codes)[2], uint32_t n_slivers, con
                        uint32_t max_slivers, int* status_out, std::vector<MixedRecoverItem>& items,
                        SliverGroupsPlan& plan);
 
+// ---------------------------------------------------------------------------------------------
+// mixed recovery symbols (rs2_sliver_checker_recovery_symbols_device_async): source slivers that
+// share only n_shards, each with its own axis, symbol size and list of targets
+// ---------------------------------------------------------------------------------------------
+// One window: the caller's slivers first .. first + count and their requests first_request ..
+// + n_requests of the concatenated list (those of refused slivers included).  Accepted slivers
+// get slots 0 .. n_slots: first the slivers that are expanded, laid out as a SliverWindow of
+// their own (`ex`: slots sorted by group, tiles, gather and repair offsets; ex.perm holds caller
+// indices), then the others in the caller's order.
+//   BUILD expands every accepted sliver with a target, and every accepted sliver when the trees
+//   go to the caller; CACHED the accepted slivers with a repair target (>= K).
+struct SymbolsMixedWindow {
+  uint32_t first = 0, count = 0;
+  uint32_t n_slots = 0;
+  SliverWindow ex;
+  std::vector<uint32_t> perm;           // slot -> caller index
+  std::vector<uint32_t> slot_request;   // slot -> its first request of the call
+  std::vector<uint32_t> slot_requests;  // slot -> its requests
+  uint64_t first_request = 0;
+  uint32_t n_requests = 0;
+  uint32_t served = 0;                  // requests of accepted slivers
+  uint32_t with_requests = 0;           // accepted slivers with a request
+};
+
+struct SymbolsMixedPlan {
+  std::vector<SymbolsMixedWindow> windows;
+  // per request of the call: slot of its window << 16 | target, or kRequestSkipped for a request
+  // of a refused sliver (no real entry equals it: a slot is at most 65534)
+  std::vector<uint32_t> table;
+  uint32_t level_base[kSymbolLevels] = {};
+  int path_len = 0;
+  uint64_t n_nodes = 0;
+  uint64_t total = 0;           // requests of the call, refused slivers' included
+  uint32_t accepted = 0;
+};
+
+// Validate and plan a mixed recovery-symbol call.  Whole-call refusals (RS2_E_INVALID_ARGUMENT):
+// trees not one of the two modes, CACHED without nodes, more than 65535 slivers, null arrays
+// (targets may be null when every count is zero), more than 2^31-1 requests summed in 64 bits --
+// all before a target is read.  Per sliver, in this order: an axis that is not one of the two
+// RS2_E_INVALID_ARGUMENT; a symbol size of 0 or odd RS2_E_INCOMPATIBLE_PARAMETERS; an odd
+// sliver_off[i] or symbols_off[i] (either array may be null: the host form has none)
+// RS2_E_INVALID_ARGUMENT; a target >= n_shards RS2_E_INVALID_ARGUMENT; host form (slivers and
+// sliver_len given) a null sliver or sliver_len[i] != K * s RS2_E_INCORRECT_DATA_LENGTH.
+// status_out as plan_sliver_groups.  Windows: plan_sliver_groups' rule over the accepted slivers
+// (budget, max_groups), a sliver's scratch being sliver_scratch_bytes plus, with BUILD,
+// n_nodes * 32 for its slot-ordered tree.
+int plan_symbols_mixed(const SliverAxisCode (&codes)[2], uint32_t n_slivers, const uint8_t* axis,
+                       const uint16_t* symbol_size, const uint64_t* sliver_off,
+                       const uint64_t* symbols_off, const uint8_t* const* slivers,
+                       const uint64_t* sliver_len, const uint32_t* target_counts,
+                       const uint16_t* targets, int trees, bool have_nodes, uint64_t budget,
+                       uint32_t max_groups, int* status_out, SymbolsMixedPlan& plan);
+
 }  // namespace rs2

@@ -895,6 +895,16 @@ def verify_mixed_stats() -> Dict[str, int]:
                     (int(v) for v in out)))
 
 
+def symbols_mixed_stats() -> Dict[str, int]:
+    """rs2_symbols_mixed_stats: windows of the mixed recovery-symbol calls, slivers expanded,
+    trees built, trees served from the caller's cache, requests served and compute launches of
+    the group path (process-wide)."""
+    out = (ctypes.c_uint64 * 6)()
+    _ok(_lib.lib().rs2_symbols_mixed_stats(out))
+    return dict(zip(("windows", "expanded", "built", "cached", "requests", "launches"),
+                    (int(v) for v in out)))
+
+
 def set_verify_mixed_budget(nbytes: int = 0) -> None:
     """rs2_set_verify_mixed_budget: scratch a window of a mixed sliver verification may hold
     (0 restores the 256 MiB default)."""
@@ -963,6 +973,40 @@ class SliverChecker:
             idx.ctypes.data_as(u16), d_symbols_base or None, s_off.ctypes.data_as(u64),
             exp.ctypes.data if exp is not None else None, d_slivers_base or None,
             o_off.ctypes.data_as(u64), d_roots or None, d_verdict or None, st, _stream(stream))
+        if statuses:
+            _ok(rc)
+            return list(st)[:m]
+        return rc
+
+    def recovery_symbols_async(self, axes: Sequence[str], symbol_sizes: Sequence[int],
+                               d_slivers_base: int, sliver_off: Sequence[int],
+                               targets_per_sliver: Sequence[Sequence[int]], d_symbols_base: int,
+                               symbols_off: Sequence[int], d_proofs: int, d_nodes: int = 0,
+                               trees: str = "build", stream: Optional[int] = None,
+                               statuses: bool = False):
+        """rs2_sliver_checker_recovery_symbols_device_async: source sliver i (axes[i],
+        symbol_sizes[i]) lies at d_slivers_base + sliver_off[i] and serves targets_per_sliver[i]
+        (orthogonal-axis indices); its symbols go back to back to d_symbols_base +
+        symbols_off[i], request j of the concatenated lists gets its Merkle path at d_proofs +
+        j*path_len*32, and sliver i's tree is d_nodes + i*n_nodes*32.  trees "build" / "cached"
+        as SliverVerifier.recovery_symbols_multi_async; `statuses` and the return value as
+        verify_async."""
+        m = len(axes)
+        ax = np.array([_AXIS.get(a, a) for a in axes] + [0], dtype=np.uint8)
+        sz = np.array(list(symbol_sizes) + [0], dtype=np.uint16)
+        counts = np.array([len(x) for x in targets_per_sliver] + [0], dtype=np.uint32)
+        tg = np.array([t for x in targets_per_sliver for t in x] + [0], dtype=np.uint16)
+        i_off = np.array(list(sliver_off) + [0], dtype=np.uint64)
+        o_off = np.array(list(symbols_off) + [0], dtype=np.uint64)
+        mode = {"build": _lib.RS2_TREES_BUILD, "cached": _lib.RS2_TREES_CACHED}.get(trees, trees)
+        st = (ctypes.c_int * max(m, 1))() if statuses else None
+        u16, u32, u64 = (ctypes.POINTER(t) for t in (ctypes.c_uint16, ctypes.c_uint32,
+                                                     ctypes.c_uint64))
+        rc = _lib.lib().rs2_sliver_checker_recovery_symbols_device_async(
+            self.handle, m, ax.ctypes.data, sz.ctypes.data_as(u16), d_slivers_base or None,
+            i_off.ctypes.data_as(u64), counts.ctypes.data_as(u32), tg.ctypes.data_as(u16), mode,
+            d_nodes or None, d_symbols_base or None, o_off.ctypes.data_as(u64), d_proofs or None,
+            st, _stream(stream))
         if statuses:
             _ok(rc)
             return list(st)[:m]

@@ -278,6 +278,51 @@ def recovery_symbols_for_targets(config, slivers: Sequence[SliverData],
     return out
 
 
+def recovery_symbols_of_blobs(config, slivers: Sequence[SliverData],
+                              targets_per_sliver: Sequence[Sequence[int]]
+                              ) -> List[List[RecoverySymbol]]:
+    """recovery_symbols_for_targets for source slivers of many blobs -- any mix of axes and symbol
+    sizes -- in ONE device call (rs2_recovery_symbols_mixed): every sliver is expanded and hashed
+    once with its own symbol size and its tree built once, whatever the number of sizes.  Returns
+    what recovery_symbols_for_targets returns."""
+    n = config.n_shards
+    L = path_length(n)
+    m = len(slivers)
+    out: List[List[RecoverySymbol]] = [[] for _ in slivers]
+    for tps in targets_per_sliver:
+        if any(tp >= n for tp in tps):
+            raise RecoverySymbolError("IndexTooLarge")
+    if m == 0:
+        return out
+    keep = [np.frombuffer(sl.symbols.data, dtype=np.uint8) for sl in slivers]
+    axes = np.array([_AXIS[sl.axis] for sl in slivers], dtype=np.uint8)
+    sizes = (ctypes.c_uint16 * m)(*[sl.symbol_size for sl in slivers])
+    ptrs = (ctypes.c_void_p * m)(*[a.ctypes.data for a in keep])
+    lens = (ctypes.c_uint64 * m)(*[len(a) for a in keep])
+    counts = (ctypes.c_uint32 * m)(*[len(tps) for tps in targets_per_sliver])
+    tgt = [tp if _ORTHOGONAL[sl.axis] == PRIMARY else n - 1 - tp
+           for sl, tps in zip(slivers, targets_per_sliver) for tp in tps]
+    total = len(tgt)
+    ta = (ctypes.c_uint16 * max(total, 1))(*tgt)
+    bufs = [np.zeros(max(len(tps) * sl.symbol_size, 1), dtype=np.uint8)
+            for sl, tps in zip(slivers, targets_per_sliver)]
+    outs = (ctypes.c_void_p * m)(*[b.ctypes.data for b in bufs])
+    proofs = np.zeros(max(total * L * 32, 1), dtype=np.uint8)
+    _ok(_lib.lib().rs2_recovery_symbols_mixed(n, m, axes.ctypes.data, sizes, ptrs, lens, counts,
+                                              ta, outs, proofs.ctypes.data, None))
+    pb = proofs.tobytes()
+    j = 0
+    for i, (sl, tps) in enumerate(zip(slivers, targets_per_sliver)):
+        s = sl.symbol_size
+        sb = bufs[i].tobytes()
+        for q in range(len(tps)):
+            path = [pb[(j * L + l) * 32:(j * L + l + 1) * 32] for l in range(L)]
+            out[i].append(RecoverySymbol(_ORTHOGONAL[sl.axis], sl.index, sb[q * s:(q + 1) * s],
+                                         MerkleProof(path)))
+            j += 1
+    return out
+
+
 def recovery_symbol_for_sliver(sliver: SliverData, target_pair_index: int,
                                config) -> RecoverySymbol:
     """SliverData::recovery_symbol_for_sliver (slivers.rs:180-213)."""
