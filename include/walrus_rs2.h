@@ -849,7 +849,10 @@ int rs2_merkle_proof_roots(uint32_t count, const uint8_t* leaves, uint32_t leaf_
  * only the symbols themselves are read and written, never the gaps a larger symbol or line
  * stride leaves between them, so a buffer's extent ends with its last line's last symbol:
  * (lines-1)*line_stride + (symbols-1)*sym_stride + symbol_size.  d_src, d_repair and the
- * four strides are 2-byte aligned. */
+ * four strides are 2-byte aligned.  Supported range (encode and decode calls alike): every
+ * stride and every sym_off[i] is below 2^47 bytes; a larger one is RS2_E_INVALID_ARGUMENT,
+ * checked with the alignment before anything is enqueued (also when lines == 0).  Line strides
+ * from (2^31 - 65536) / 64 = 33,553,408 bytes on put every 64-pair tile inside one line. */
 typedef struct rs2_codec rs2_codec;
 int rs2_codec_create(uint16_t k, uint16_t n_shards, uint16_t symbol_size, rs2_codec** out);
 void rs2_codec_destroy(rs2_codec* codec);

@@ -180,6 +180,53 @@ def sliver_root(p: O.Rs2Params, axis: str, sliver: bytes) -> bytes:
     return root.tobytes()
 
 
+def expand_sliver(p: O.Rs2Params, axis: str, sliver: bytes) -> np.ndarray:
+    """The sliver's n expanded symbols [n][s] from the C restatement (rs2cpu_encode_1d)."""
+    lib = _cpu_lib()
+    lib.rs2cpu_encode_1d.argtypes = [ctypes.c_uint32] * 4 + [ctypes.c_void_p] * 2
+    k = p.n_secondary if axis == PRIMARY else p.n_primary
+    src = np.frombuffer(bytes(sliver), np.uint8)
+    out = np.zeros((p.n_shards, p.symbol_size), np.uint8)
+    assert src.size == k * p.symbol_size
+    assert lib.rs2cpu_encode_1d(k, p.n_shards, p.symbol_size, 1, src.ctypes.data,
+                                out.ctypes.data) == 0
+    return out
+
+
+def recovery_symbol(p: O.Rs2Params, axis: str, sliver: bytes, target: int):
+    """(symbol, proof) of recovery_symbol_for_sliver from the C restatement
+    (rs2cpu_recovery_symbol: the expanded symbol and MerkleTree::get_proof of its leaf)."""
+    lib = _cpu_lib()
+    lib.rs2cpu_recovery_symbol.argtypes = [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int,
+                                           ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p,
+                                           ctypes.c_void_p]
+    src = np.frombuffer(bytes(sliver), np.uint8)
+    sym = np.zeros(p.symbol_size, np.uint8)
+    proof = np.zeros(32 * 32, np.uint8)
+    L = lib.rs2cpu_recovery_symbol(p.n_shards, p.symbol_size, int(axis == SECONDARY),
+                                   src.ctypes.data, target, sym.ctypes.data, proof.ctypes.data)
+    assert 0 <= L <= 32
+    return sym.tobytes(), proof[:32 * L].tobytes()
+
+
+def recover_sliver(p: O.Rs2Params, axis: str, idx, symbols: np.ndarray):
+    """(sliver, root) of recover_sliver from the C restatement (rs2cpu_recover_sliver): symbol i
+    of `symbols` ([count][s]) has index idx[i] on the orthogonal axis."""
+    lib = _cpu_lib()
+    lib.rs2cpu_recover_sliver.argtypes = [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int,
+                                          ctypes.c_uint32] + [ctypes.c_void_p] * 4
+    k = p.n_secondary if axis == PRIMARY else p.n_primary
+    ids = np.array(list(idx), np.uint16)
+    sym = np.ascontiguousarray(symbols, dtype=np.uint8)
+    assert sym.size == ids.size * p.symbol_size
+    out = np.zeros(k * p.symbol_size, np.uint8)
+    root = np.zeros(32, np.uint8)
+    assert lib.rs2cpu_recover_sliver(p.n_shards, p.symbol_size, int(axis == SECONDARY), ids.size,
+                                     ids.ctypes.data, sym.ctypes.data, out.ctypes.data,
+                                     root.ctypes.data) == 0
+    return out.tobytes(), root.tobytes()
+
+
 def sliver_positions(p: O.Rs2Params, axis: str):
     """(byte of the sliver, mask) at the first, a middle and the last symbol x symbol_offsets,
     the two masks alternating."""

@@ -2186,6 +2186,13 @@ int check_symbol_step(uint64_t v, const char* what) {
   if (v % 2 == 0) return RS2_OK;
   return fail(RS2_E_INVALID_ARGUMENT, std::string(what) + " must be a multiple of 2 bytes");
 }
+// Strides and offsets of the strided 1D codec: 2-byte aligned like every symbol step and below
+// 2^47 (include/walrus_rs2.h), so that the int64 offsets planned from them cannot overflow.
+int check_codec_step(uint64_t v, const char* what) {
+  RS2_TRY(check_symbol_step(v, what));
+  if (v < (uint64_t(1) << 47)) return RS2_OK;
+  return fail(RS2_E_INVALID_ARGUMENT, std::string(what) + " must be below 2^47 bytes");
+}
 int check_digest_ptr(const void* p, const char* what) {
   if (aligned_to(p, 16)) return RS2_OK;
   return fail(RS2_E_INVALID_ARGUMENT, std::string(what) + " must be 16-byte aligned");
@@ -5553,10 +5560,10 @@ int rs2_codec_encode_device_async(rs2_codec* c, uint32_t lines, const void* d_sr
   if (!c || (lines && (!d_src || !d_repair))) return fail(RS2_E_INVALID_ARGUMENT, "null argument");
   RS2_TRY(check_symbol_ptr(d_src, "d_src"));
   RS2_TRY(check_symbol_ptr(d_repair, "d_repair"));
-  RS2_TRY(check_symbol_step(src_sym_stride, "src_sym_stride"));
-  RS2_TRY(check_symbol_step(src_line_stride, "src_line_stride"));
-  RS2_TRY(check_symbol_step(repair_sym_stride, "repair_sym_stride"));
-  RS2_TRY(check_symbol_step(repair_line_stride, "repair_line_stride"));
+  RS2_TRY(check_codec_step(src_sym_stride, "src_sym_stride"));
+  RS2_TRY(check_codec_step(src_line_stride, "src_line_stride"));
+  RS2_TRY(check_codec_step(repair_sym_stride, "repair_sym_stride"));
+  RS2_TRY(check_codec_step(repair_line_stride, "repair_line_stride"));
   if (lines == 0) return RS2_OK;
   if (src_sym_stride < c->s || repair_sym_stride < c->s)
     return fail(RS2_E_INVALID_ARGUMENT, "symbol stride smaller than the symbol");
@@ -5591,10 +5598,10 @@ int rs2_codec_decode_device_async(rs2_codec* c, uint32_t lines, uint32_t count,
   if (out_sym_stride < c->s) return fail(RS2_E_INVALID_ARGUMENT, "symbol stride smaller than the symbol");
   RS2_TRY(check_symbol_ptr(d_base, "d_base"));
   RS2_TRY(check_symbol_ptr(d_out, "d_out"));
-  RS2_TRY(check_symbol_step(line_stride, "line_stride"));
-  RS2_TRY(check_symbol_step(out_sym_stride, "out_sym_stride"));
-  RS2_TRY(check_symbol_step(out_line_stride, "out_line_stride"));
-  for (uint32_t i = 0; i < count; ++i) RS2_TRY(check_symbol_step(sym_off[i], "sym_off[i]"));
+  RS2_TRY(check_codec_step(line_stride, "line_stride"));
+  RS2_TRY(check_codec_step(out_sym_stride, "out_sym_stride"));
+  RS2_TRY(check_codec_step(out_line_stride, "out_line_stride"));
+  for (uint32_t i = 0; i < count; ++i) RS2_TRY(check_codec_step(sym_off[i], "sym_off[i]"));
   const int64_t K = c->k, N = c->n, s = c->s;
   // the first K distinct valid indices (the crate ignores duplicates and invalid indices)
   std::vector<int64_t> present(N, -1);
