@@ -223,6 +223,98 @@ int rs2_encode_batch_with_metadata(rs2_plan* plan, uint32_t n_blobs, const uint8
                                    uint8_t* const* secondary_out, uint8_t* hashes_out,
                                    uint8_t* blob_ids_out);
 
+/* ---- blob encode across sizes: a symbol size per blob ---------------------------------------
+ * The symbol size is a function of a blob's length, so an upload relay (walrus-upload-relay/src/
+ * controller.rs:177) or a client encoding a queue of blobs (encode_blobs_as, node_client.rs:
+ * 3156-3221) has about as many sizes as blobs, and rs2_encode_batch_* -- bound to one plan, one
+ * size -- would take a call per size.  An encoder is bound to n_shards only; one call takes
+ * n_blobs blobs, each with its own length.  Blob b is blob_lens[b] bytes at d_blobs_base +
+ * blob_off[b]; its symbol size is s_b = rs2_symbol_size_for_blob(n_shards, blob_lens[b]); its
+ * primary slivers lie in the single-blob layout (n*K_s*s_b bytes) at d_primary_base +
+ * primary_off[b], its secondary slivers (n*K_p*s_b bytes) at d_secondary_base + secondary_off[b],
+ * its n pair hashes at d_hashes + b*64*n and its BlobId at d_blob_ids + b*32 -- for every blob bit
+ * for bit what rs2_encode_device_async writes for that blob alone.  Nothing outside these extents
+ * is read or written; in particular no byte at or past blob_off[b] + blob_lens[b] is read.
+ * d_blobs_base, d_primary_base, d_secondary_base and every offset are 2-byte aligned, d_hashes
+ * and d_blob_ids 16-byte aligned.  THE OUTPUT EXTENTS OF DIFFERENT BLOBS MUST NOT OVERLAP EACH
+ * OTHER OR THE BLOBS: that is the caller's duty, nothing checks it.
+ * Metadata only (BlobEncoder::compute_metadata, blob_encoding.rs:406-486): d_primary_base and
+ * d_secondary_base NULL together; the two offset arrays are then ignored, the slivers go to the
+ * window's scratch and count toward its budget.  One of them NULL without the other:
+ * RS2_E_INVALID_ARGUMENT for the whole call.
+ * Per blob, decided on the host before anything is enqueued: the codes rs2_plan_create and
+ * rs2_encode_device_async give for that length (RS2_E_DATA_TOO_LARGE, RS2_E_INCOMPATIBLE_PARAMETERS
+ * for an n_shards without a recovery code); an odd blob_off[b], primary_off[b] or
+ * secondary_off[b] RS2_E_INVALID_ARGUMENT; host form only: a NULL blob of non-zero length
+ * RS2_E_INVALID_ARGUMENT.  status_out NULL: the first failing blob's code is returned and nothing
+ * is enqueued; non-NULL: failing blobs get their code and are skipped (none of their output slots
+ * is touched), the rest run, RS2_OK.  Whole-call refusals (RS2_E_INVALID_ARGUMENT): a NULL
+ * encoder or needed array, a base that is not 2-byte or a d_hashes / d_blob_ids that is not
+ * 16-byte aligned, more than 65535 blobs.  n_blobs 0: RS2_OK, nothing enqueued.
+ *
+ * How it runs.  Blobs are taken, in the caller's order, in windows: a blob of symbol size s holds
+ * (n-K_p)*(n-K_s)*s + 32*n*n bytes of scratch (its repair-repair quadrant and its n*n leaf
+ * digests; metadata only: n*(K_p+K_s)*s more for its slivers; the zero-padded message is staged
+ * in the blob's own systematic primary slivers and takes nothing more).  A window closes before the
+ * blob that would take it past the budget (rs2_set_encode_mixed_budget; at least one blob per
+ * window) or past RS2_ENCODE_MIXED_WINDOW_BLOBS blobs (what keeps a window's job and offset tables
+ * within a third of the pinned upload ring), so scratch does not grow with n_blobs.  The default
+ * budget is 4 GiB: at n_shards = 1000 a blob's leaves alone are 32 MB, so 256 MiB -- the other
+ * mixed calls' default -- would cut windows at 8 small blobs and pay the window's launches for
+ * each; 4 GiB holds about a hundred of them, and a blob of the largest symbol size (s = 65534: a
+ * 14.5 GB quadrant) still runs as a window of its own.  Per window: one staging launch copies every
+ * message into its primary slivers and zero-fills its padding; three codec launches, one per
+ * stage (systematic columns with the systematic secondary slivers written from the same loads,
+ * rows, repair columns), each a job per blob found from a tile prefix array; one leaf-hash launch
+ * over a blob table; one tree launch and one root launch over all blobs of the window; and, when
+ * the window's blobs are not consecutive in the caller's arrays from its first blob on (a refused
+ * or per-blob one lies between), one launch that moves hashes and ids to the caller's slots.  That
+ * is at most RS2_ENCODE_MIXED_WINDOW_LAUNCHES compute launches per window, however many blobs and
+ * sizes it holds.  (Where the column code is not a single shared-input block -- n_shards = 13,
+ * or above 1534 at the default block limit -- its codec has no fused copy-out and the staging
+ * launch writes the systematic secondary slivers instead.)  A blob runs there iff its symbol
+ * size is >= 4, n_shards <= 4096, all three stages have 1..8 transform blocks on each side
+ * (n_shards = 10 .. 4096 have at most 3 at the default block limit) and the tiles of each stage launch stay below
+ * 2^31.  Every other blob (a 2-byte symbol,
+ * wider n_shards) runs inside the same call and window through the single-blob encode, a blob at a
+ * time on an internally cached plan per size, on the same stream; only that path may wait for the
+ * device (a plan re-bound to other buffers waits for its previous encode).  All blobs of at most
+ * 2*K_p*K_s bytes share s = 2: a batch of those should keep rs2_encode_batch_*.
+ * Measured (tools/encode_mixed_probe.py, MI355X, n_shards = 1000, device-resident; DESIGN.md
+ * §22): 32 symbol sizes 4 .. 66, two blobs each: 15.1 ms against 21.5 ms for 32
+ * rs2_encode_batch_device_async calls (1.43x); 64 blobs uniform at s = 20: 12.9 ms against 12.0 ms
+ * for the one rs2_encode_batch_device_async call (1.08x slower: its leaf kernel is specialised per
+ * message length), so a batch uniform in size should keep that call.
+ * The call is enqueued on `stream` and never waits for the device on the group path; the host
+ * arrays may be reused as soon as it returns (the tables go through the pinned upload ring).
+ * Stream conventions and the `done` event as the checker's; one encoder per thread, or serialise
+ * its use; destroy waits for pending work. */
+#define RS2_ENCODE_MIXED_WINDOW_LAUNCHES 8
+#define RS2_ENCODE_MIXED_WINDOW_BLOBS 256
+typedef struct rs2_blob_encoder rs2_blob_encoder;
+int rs2_blob_encoder_create(uint16_t n_shards, rs2_blob_encoder** out);
+void rs2_blob_encoder_destroy(rs2_blob_encoder* e);
+int rs2_blob_encoder_encode_device_async(
+    rs2_blob_encoder* e, uint32_t n_blobs, const uint64_t* blob_lens, const void* d_blobs_base,
+    const uint64_t* blob_off, void* d_primary_base, const uint64_t* primary_off,
+    void* d_secondary_base, const uint64_t* secondary_off, void* d_hashes, void* d_blob_ids,
+    int* status_out, void* stream);
+/* Host form (blocking): blobs[b] is blob b (blob_lens[b] bytes); primary_out / secondary_out hold
+ * n_blobs*n sliver pointers, blob-major (either array, or any entry, may be NULL: not returned);
+ * hashes_out n_blobs*n*64 bytes and blob_ids_out n_blobs*32 bytes (either may be NULL).  Output
+ * slots of skipped blobs are not written. */
+int rs2_encode_blobs_with_metadata(uint16_t n_shards, uint32_t n_blobs, const uint8_t* const* blobs,
+                                   const uint64_t* blob_lens, uint8_t* const* primary_out,
+                                   uint8_t* const* secondary_out, uint8_t* hashes_out,
+                                   uint8_t* blob_ids_out, int* status_out);
+/* Window scratch of the mixed encode in bytes (default 4 GiB; 0 restores it).  Process-wide. */
+int rs2_set_encode_mixed_budget(uint64_t bytes);
+/* Process-wide counters, stats_out[5]: windows; blobs encoded inside group launches; blobs that
+ * took the per-blob path; distinct symbol sizes inside windows; compute launches of the group
+ * path (staging, codecs, leaf hash, trees, roots, scatter; table uploads and the per-blob path's
+ * own launches are not counted).  No reference counterpart. */
+int rs2_encode_mixed_stats(uint64_t* stats_out);
+
 /* BlobDecoder::decode (blob_encoding.rs:888-993) / EncodingFactory::decode (config.rs:605-611).
  * `count` slivers of axis `axis`, sliver i at slivers[i] with index sliver_idx[i], length
  * sliver_len[i] bytes and symbol size sliver_symbol_size[i] (NULL: all equal to the plan's).

@@ -12,6 +12,7 @@ from . import recovery  # noqa: F401  (recovery symbols, Merkle proofs, inconsis
 from .encoding import (  # noqa: F401
     PRIMARY,
     SECONDARY,
+    BlobEncoder,
     BlobId,
     BlobMetadata,
     DataTooLargeError,
@@ -34,8 +35,10 @@ from .encoding import (  # noqa: F401
     VerificationError,
     VerifiedBlobMetadataWithId,
     compute_symbol_size,
+    encode_mixed_stats,
     recover_mixed_stats,
     recovery_symbols_stats,
+    set_encode_mixed_budget,
     set_recovery_symbols_budget,
     set_verify_batch_budget,
     set_verify_mixed_budget,

@@ -35,6 +35,8 @@ CHECK_SKIP, CHECK_DEFAULT, CHECK_STRICT = 0, 1, 2
 RS2_SLIVER_MISMATCH, RS2_SLIVER_MATCH, RS2_SLIVER_SKIPPED = 0, 1, 2
 RS2_BLOB_MISMATCH, RS2_BLOB_MATCH, RS2_BLOB_SKIPPED = 0, 1, 2
 RS2_TREES_BUILD, RS2_TREES_CACHED = 0, 1
+RS2_ENCODE_MIXED_WINDOW_LAUNCHES = 8
+RS2_ENCODE_MIXED_WINDOW_BLOBS = 256
 
 # (name, restype, argtypes) for every function declared in include/walrus_rs2.h
 _u8p = ctypes.POINTER(ctypes.c_uint8)
@@ -91,6 +93,18 @@ SIGNATURES = {
     "rs2_encode_batch_with_metadata": (
         ctypes.c_int, [_vp, ctypes.c_uint32, ctypes.POINTER(_vp), _u64p, ctypes.POINTER(_vp),
                        ctypes.POINTER(_vp), _vp, _vp]),
+    "rs2_blob_encoder_create": (ctypes.c_int, [ctypes.c_uint16, ctypes.POINTER(_vp)]),
+    "rs2_blob_encoder_destroy": (None, [_vp]),
+    "rs2_blob_encoder_encode_device_async": (
+        ctypes.c_int,
+        [_vp, ctypes.c_uint32, _u64p, _vp, _u64p, _vp, _u64p, _vp, _u64p, _vp, _vp,
+         ctypes.POINTER(ctypes.c_int), _vp]),
+    "rs2_encode_blobs_with_metadata": (
+        ctypes.c_int,
+        [ctypes.c_uint16, ctypes.c_uint32, ctypes.POINTER(_vp), _u64p, ctypes.POINTER(_vp),
+         ctypes.POINTER(_vp), _vp, _vp, ctypes.POINTER(ctypes.c_int)]),
+    "rs2_set_encode_mixed_budget": (ctypes.c_int, [ctypes.c_uint64]),
+    "rs2_encode_mixed_stats": (ctypes.c_int, [ctypes.POINTER(ctypes.c_uint64)]),
     "rs2_quilt_layout_device_async": (ctypes.c_int, [ctypes.c_uint16, ctypes.c_uint16,
                                                      ctypes.c_uint16, _vp, _vp, _vp, _vp, _vp]),
     "rs2_decode_device_async": (

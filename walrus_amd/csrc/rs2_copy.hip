@@ -334,6 +334,91 @@ __global__ void __launch_bounds__(256)
     *reinterpret_cast<uint16_t*>(dp + e) = *reinterpret_cast<const uint16_t*>(sp + e);
 }
 
+// Message staging of a mixed blob encode window (rs2_blob_encoder_*): blob a's `len` bytes from
+// its own place in the caller's memory to its systematic primary slivers, zeros from there up to
+// its message length `msg` (K_p K_s s, even).  The lengths differ, so a workgroup (one 4 KiB chunk
+// of one message) finds its blob by a search of the blobs' first chunks, as sliver_gather_kernel.
+// Nothing at or past src + len is read -- it may be the next blob or the end of the caller's
+// buffer.  Both ends are 2-byte aligned: a lane moves 16 bytes as one, four or eight aligned
+// words, by the alignment the two ends share; the piece that holds the blob's end goes element by
+// element, its odd last byte alone (check_rows_gather_kernel's rule).
+// A blob whose systematic-column code has no fused copy-out (a mixing code: n_shards = 13, or
+// above 1534 at the default block limit) names its secondary buffer: the lane then also writes
+// its elements transposed -- symbol (r, c) of the message to secondary sliver c, row r -- two
+// bytes at a time, which the codec's own loads do for every other blob.
+__global__ void __launch_bounds__(256)
+    blob_stage_kernel(const BlobStage* __restrict__ blobs, int n_blobs, int kp, int ks) {
+  const uint32_t chunk = blockIdx.x;
+  int lo = 0, hi = n_blobs - 1;  // the last blob whose chunk0 <= chunk
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (blobs[mid].chunk0 <= chunk)
+      lo = mid;
+    else
+      hi = mid - 1;
+  }
+  const BlobStage bl = blobs[lo];
+  const int64_t g = (int64_t(chunk - bl.chunk0) * 256 + threadIdx.x) * 16;
+  const int64_t msg = int64_t(bl.msg), valid = int64_t(bl.len);
+  if (g >= msg) return;
+  const int n = int(msg - g < 16 ? msg - g : 16);  // even
+  const uint8_t* sp = bl.src + g;
+  uint8_t* dp = bl.dst + g;
+  const uintptr_t dal = reinterpret_cast<uintptr_t>(dp);
+  // the message's 2-byte element at g + e: the blob's bytes, then padding
+  auto element = [&](int e) -> uint16_t {
+    if (g + e + 2 <= valid) return *reinterpret_cast<const uint16_t*>(sp + e);
+    if (g + e < valid) return sp[e];  // the blob's odd last byte; the high byte is padding
+    return 0;
+  };
+  if (bl.sec) {
+    const int64_t s = bl.s;  // even, so an element never straddles two symbols
+    for (int e = 0; e < n; e += 2) {
+      const int64_t x = g + e, sym = x / s, r = sym / ks, c = sym - r * ks;
+      *reinterpret_cast<uint16_t*>(bl.sec + (c * kp + r) * s + (x - sym * s)) = element(e);
+    }
+  }
+  if (n == 16 && g + 16 <= valid) {
+    const uintptr_t al = reinterpret_cast<uintptr_t>(sp) | dal;
+    if ((al & 15) == 0) {
+      *reinterpret_cast<uint4*>(dp) = *reinterpret_cast<const uint4*>(sp);
+    } else if ((al & 3) == 0) {
+      uint32_t v[4];
+      sfor<4>([&](auto j) { v[decltype(j)::value] = reinterpret_cast<const uint32_t*>(sp)[decltype(j)::value]; });
+      sfor<4>([&](auto j) { reinterpret_cast<uint32_t*>(dp)[decltype(j)::value] = v[decltype(j)::value]; });
+    } else {
+      uint16_t v[8];
+      sfor<8>([&](auto j) { v[decltype(j)::value] = reinterpret_cast<const uint16_t*>(sp)[decltype(j)::value]; });
+      sfor<8>([&](auto j) { reinterpret_cast<uint16_t*>(dp)[decltype(j)::value] = v[decltype(j)::value]; });
+    }
+    return;
+  }
+  if (n == 16 && g >= valid && (dal & 15) == 0) {
+    *reinterpret_cast<uint4*>(dp) = make_uint4(0u, 0u, 0u, 0u);
+    return;
+  }
+  for (int e = 0; e < n; e += 2) *reinterpret_cast<uint16_t*>(dp + e) = element(e);
+}
+
+// Metadata of a mixed blob encode window to the caller's arrays: the window's pair hashes
+// (64 n bytes per slot) and ids (32 bytes per slot) lie in slot order; slot y's go to blob
+// dst_index[y] of hashes_out / ids_out.  All four bases are 16-byte aligned; a lane moves 16 bytes.
+__global__ void __launch_bounds__(256)
+    blob_meta_scatter_kernel(const uint8_t* __restrict__ hashes, const uint8_t* __restrict__ ids,
+                             const uint32_t* __restrict__ dst_index, int64_t hash_bytes,
+                             uint8_t* __restrict__ hashes_out, uint8_t* __restrict__ ids_out) {
+  const int64_t slot = blockIdx.y, to = dst_index[blockIdx.y];
+  const int64_t g = (int64_t(blockIdx.x) * 256 + threadIdx.x) * 16;
+  if (g < hash_bytes) {
+    *reinterpret_cast<uint4*>(hashes_out + to * hash_bytes + g) =
+        *reinterpret_cast<const uint4*>(hashes + slot * hash_bytes + g);
+  } else if (g < hash_bytes + 32) {
+    const int64_t o = g - hash_bytes;
+    *reinterpret_cast<uint4*>(ids_out + to * 32 + o) =
+        *reinterpret_cast<const uint4*>(ids + slot * 32 + o);
+  }
+}
+
 // Small host -> device uploads (rs2_engine.cpp UploadSlots): the kernel reads the pinned,
 // device-mapped host slot over PCIe and writes the device buffer, in stream order like any
 // launch -- no DMA-engine copy, whose cross-engine dependency on the stream's earlier kernels
@@ -541,6 +626,28 @@ hipError_t rs2k_launch_sliver_gather(const rs2::SliverSlot* d_slots, int n_slots
   if (n_chunks >= (int64_t(1) << 31)) return hipErrorInvalidValue;
   hipLaunchKernelGGL(rs2::sliver_gather_kernel, dim3(unsigned(n_chunks)), dim3(256), 0, stream,
                      d_slots, n_slots, d_dst);
+  return hipGetLastError();
+}
+
+hipError_t rs2k_launch_blob_stage(const rs2::BlobStage* d_blobs, int n_blobs, int64_t n_chunks,
+                                  int kp, int ks, hipStream_t stream) {
+  if (n_blobs <= 0 || n_chunks <= 0) return hipSuccess;
+  if (n_chunks >= (int64_t(1) << 31) || kp < 1 || ks < 1) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(rs2::blob_stage_kernel, dim3(unsigned(n_chunks)), dim3(256), 0, stream,
+                     d_blobs, n_blobs, kp, ks);
+  return hipGetLastError();
+}
+
+hipError_t rs2k_launch_blob_meta_scatter(const uint8_t* d_hashes, const uint8_t* d_ids,
+                                         const uint32_t* d_dst_index, int n_slots, int n,
+                                         uint8_t* d_hashes_out, uint8_t* d_ids_out,
+                                         hipStream_t stream) {
+  if (n_slots <= 0) return hipSuccess;
+  if (n_slots > 65535 || n < 1) return hipErrorInvalidValue;
+  const int64_t hash_bytes = int64_t(n) * 64;
+  hipLaunchKernelGGL(rs2::blob_meta_scatter_kernel,
+                     dim3(unsigned((hash_bytes + 32 + 4095) / 4096), unsigned(n_slots)), dim3(256),
+                     0, stream, d_hashes, d_ids, d_dst_index, hash_bytes, d_hashes_out, d_ids_out);
   return hipGetLastError();
 }
 

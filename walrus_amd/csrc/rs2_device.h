@@ -212,6 +212,37 @@ static_assert(sizeof(SymbolRun) == 24, "symbol runs are packed");
 // caller index -> slot table entry of a sliver refused on the host (sliver_finish_kernel)
 constexpr uint32_t kSliverSkipped = 0xFFFFFFFFu;
 
+// Mixed blob encode (rs2_blob_encoder_*): one window's device tables.
+// An eligible blob of the leaf launch (leaf_hash_blobs_kernel): where its n x n expanded symbols
+// lie (the three runs of SymbolMap: primary [n][K_s][s], secondary [n][K_p][s], both
+// [n-K_p][n-K_s][s]), where its 32 n^2 bytes of leaves go, its symbol size and its first tile of
+// the launch.  The table is searched by first_tile; the entry after the last blob holds the
+// launch's tile count.
+struct BlobLeaves {
+  const uint8_t* primary;
+  const uint8_t* secondary;
+  const uint8_t* both;
+  uint8_t* leaves;
+  uint32_t s;
+  uint32_t first_tile;
+};
+// A blob of the staging launch (blob_stage_kernel): `len` bytes at src go to dst, followed by
+// zeros up to `msg` bytes (the zero-padded message K_p K_s s: the systematic primary slivers);
+// chunk0 is its first 4 KiB chunk of the launch, and the entry after the last blob holds the
+// launch's chunk count.  sec: where the systematic secondary slivers go as well (secondary c, row
+// r = primary r, column c; s: the blob's symbol size), or null when the systematic-column codec
+// writes them from its own loads.
+struct BlobStage {
+  const uint8_t* src;
+  uint8_t* dst;
+  uint8_t* sec;
+  uint64_t len;
+  uint64_t msg;
+  uint32_t chunk0;
+  uint32_t s;
+};
+static_assert(sizeof(BlobLeaves) == 40 && sizeof(BlobStage) == 48, "blob tables are packed");
+
 // Bulk recovery symbols (symbol_requests_kernel): where each level of a sliver's MerkleTree::nodes
 // array starts, in nodes -- a path has at most kSymbolLevels siblings for n <= 65535 leaves.  By
 // value in the launch arguments (wave-uniform, read once per wave).

@@ -4871,6 +4871,477 @@ int rs2_verify_mixed_stats(uint64_t* stats_out) {
 }  // extern "C"
 
 // ---------------------------------------------------------------------------------------------
+// mixed blob encode: blobs that share only n_shards, a symbol size per blob
+// ---------------------------------------------------------------------------------------------
+// Mixed blob encode state (rs2_blob_encoder_*): bound to n_shards only; every blob of a call has
+// its own length and symbol size (the upload relay's queue, controller.rs:177).
+struct rs2_blob_encoder {
+  Context* ctx = nullptr;
+  hipStream_t stream = nullptr;
+  uint16_t n = 0;
+  // the three stage templates (planned once, again only when the block limit changed), their jobs
+  // with the transform tables attached, and their mixing tables on the device
+  BlobStages stages;
+  bool bound = false;
+  DevBuf mix[kBlobStages];
+  // a window's scratch: repair-repair quadrants, leaves, pair hashes and ids in slot order (used
+  // when the window's blobs are not neighbours in the caller's arrays), the slivers of a
+  // metadata-only call; its tables
+  DevBuf both, leaves, hashes, ids, int_primary, int_secondary, tables;
+  // blobs the group launches cannot take run through these plans, one per symbol size, the
+  // least recently used one replaced once kSinglePlans are held
+  static constexpr size_t kSinglePlans = 4;
+  std::vector<rs2_plan*> singles;
+  // host-buffer form: blobs in, slivers and metadata out
+  DevBuf h_blobs, h_primary, h_secondary, h_hashes, h_ids;
+  Event done;  // as rs2_verifier::done
+  ~rs2_blob_encoder() {
+    if (stream) (void)hipStreamDestroy(stream);
+  }
+};
+
+namespace {
+constexpr uint64_t kEncodeMixedBudget = uint64_t(4) << 30;
+std::atomic<uint64_t> g_em_budget{kEncodeMixedBudget};
+std::atomic<uint64_t> g_em_windows{0}, g_em_grouped{0}, g_em_single{0}, g_em_sizes{0},
+    g_em_launches{0};
+// Eligible blobs of one window: what keeps its job and offset tables (three jobs a blob, three
+// offset arrays a size) within a third of the pinned upload ring, so the compute launches of a
+// window (RS2_ENCODE_MIXED_WINDOW_LAUNCHES) never depend on how many blobs and sizes it holds.
+constexpr uint32_t kMixedWindowBlobs = RS2_ENCODE_MIXED_WINDOW_BLOBS;
+
+// The stage templates, planned once per encoder (again only when the block limit changed): host
+// arithmetic only.
+int encoder_stages(rs2_blob_encoder* e) {
+  if (e->stages.n == e->n && e->stages.block_max == block_max()) return RS2_OK;
+  RS2_TRY(plan_blob_stages(e->n, e->stages));
+  e->bound = false;
+  return RS2_OK;
+}
+
+// Freshly planned stages' device side, as checker_bind.
+int encoder_bind(rs2_blob_encoder* e, hipStream_t st) {
+  if (e->bound || !e->stages.batchable) return RS2_OK;
+  for (int g = 0; g < kBlobStages; ++g) {
+    BlobStageCode& code = e->stages.stage[g];
+    const PlannedJob& t = code.tmpl;
+    CodecJobBatch& j = code.job;
+    for (int b = 0; b < j.n_in; ++b) {
+      j.in[b].sd_tab = e->ctx->stream(t.C, t.in_sd[size_t(b)], t.ppw);
+      if (!j.in[b].sd_tab) return fail(RS2_E_DEVICE, "table upload failed");
+      j.in[b].zero_first = group0_zero(t.C, t.in_sd[size_t(b)], t.ppw);
+    }
+    for (int o = 0; o < j.n_out; ++o) {
+      j.out[o].sd_tab = e->ctx->stream(t.C, t.out_sd[size_t(o)], t.ppw);
+      if (!j.out[o].sd_tab) return fail(RS2_E_DEVICE, "table upload failed");
+      j.out[o].zero_first = group0_zero(t.C, t.out_sd[size_t(o)], t.ppw);
+    }
+    j.mix_tab = nullptr;
+    if (!code.mix.empty()) {
+      HIP_TRY(e->mix[g].ensure(code.mix.size() * 2));
+      RS2_TRY(upload_pieces(e->ctx, e->mix[g].p, code.mix.data(), code.mix.size() * 2, st));
+      j.mix_tab = e->mix[g].as<uint16_t>();
+    }
+  }
+  e->bound = true;
+  return RS2_OK;
+}
+
+// Where a window's tables lie in the encoder's table buffer (every part 16-byte aligned).
+struct BlobTables {
+  size_t stage = 0, leaves = 0, jobs = 0, tiles[kBlobStages] = {0, 0, 0}, offs = 0, lens = 0,
+         dst_index = 0, bytes = 0;
+  size_t class_offs = 0;  // position and copy offsets (int64) of one size class, all stages
+};
+BlobTables blob_tables(const rs2_blob_encoder* e, const BlobWindow& w) {
+  BlobTables t;
+  size_t at = 0;
+  auto take = [&](size_t n) {
+    const size_t here = at;
+    at += (n + 15) / 16 * 16;
+    return here;
+  };
+  const size_t ne = w.n_eligible;
+  t.stage = take((ne + 1) * sizeof(BlobStage));
+  t.leaves = take((ne + 1) * sizeof(BlobLeaves));
+  t.jobs = take(kBlobStages * ne * sizeof(CodecJobBatch));
+  for (int g = 0; g < kBlobStages; ++g) {
+    t.tiles[g] = take(w.tiles[g].size() * 4);
+    t.class_offs += e->stages.stage[g].tmpl.offs.size();
+  }
+  t.offs = take(w.sizes.size() * t.class_offs * 8);
+  t.lens = take(ne * 8);
+  t.dst_index = take(ne * 4);
+  t.bytes = std::max<size_t>(at, 16);
+  return t;
+}
+
+// The plan of the per-blob path for a blob of `len` bytes and symbol size s: the cached one of
+// that size re-bound to the length, else a new one in the place of the least recently used.
+int encoder_single_plan(rs2_blob_encoder* e, uint16_t s, uint64_t len, rs2_plan** out) {
+  auto& ps = e->singles;
+  for (size_t i = 0; i < ps.size(); ++i)
+    if (ps[i]->s == s) {
+      rs2_plan* p = ps[i];
+      ps.erase(ps.begin() + long(i));
+      ps.push_back(p);
+      RS2_TRY(rs2_plan_rebind(p, len));
+      *out = p;
+      return RS2_OK;
+    }
+  if (ps.size() >= rs2_blob_encoder::kSinglePlans) {
+    rs2_plan_destroy(ps.front());  // waits for its pending work
+    ps.erase(ps.begin());
+  }
+  rs2_plan* p = nullptr;
+  RS2_TRY(rs2_plan_create(e->n, len, &p));
+  ps.push_back(p);
+  *out = p;
+  return RS2_OK;
+}
+
+// Run a planned call on st.  src(b): the device address of the caller's blob b; prim(b) / sec(b):
+// where its slivers go (not called when meta_only: the window's scratch takes them); lens,
+// d_hashes and d_ids are indexed by the caller's blob.  Every buffer is sized for the call's
+// largest window before the first window runs.
+template <class SrcF, class PrimF, class SecF>
+int encoder_run(rs2_blob_encoder* e, const BlobsMixedPlan& plan, const uint64_t* lens, SrcF src,
+                PrimF prim, SecF sec, bool meta_only, uint8_t* d_hashes, uint8_t* d_ids,
+                hipStream_t st) {
+  Context* ctx = e->ctx;
+  const BlobStages& sg = e->stages;
+  const int64_t n = e->n, kp = sg.kp, ks = sg.ks;
+  // a previous call on another stream still owns the scratch buffers and tables
+  HIP_TRY(e->done.wait_on(st));
+  uint64_t max_both = 0, max_prim = 0, max_sec = 0;
+  uint32_t max_elig = 0;
+  size_t max_tab = 0;
+  for (const BlobWindow& w : plan.windows) {
+    if (!w.n_eligible) continue;
+    max_both = std::max(max_both, w.both_bytes);
+    max_prim = std::max(max_prim, w.primary_bytes);
+    max_sec = std::max(max_sec, w.secondary_bytes);
+    max_elig = std::max(max_elig, w.n_eligible);
+    max_tab = std::max(max_tab, blob_tables(e, w).bytes);
+  }
+  if (max_elig) {
+    RS2_TRY(encoder_bind(e, st));
+    HIP_TRY(e->both.ensure(std::max<uint64_t>(max_both, 16)));
+    HIP_TRY(e->leaves.ensure(size_t(max_elig) * size_t(n) * size_t(n) * 32));
+    HIP_TRY(e->hashes.ensure(size_t(max_elig) * size_t(n) * 64));
+    HIP_TRY(e->ids.ensure(size_t(max_elig) * 32));
+    HIP_TRY(e->tables.ensure(max_tab));
+    if (meta_only) {
+      HIP_TRY(e->int_primary.ensure(std::max<uint64_t>(max_prim, 16)));
+      HIP_TRY(e->int_secondary.ensure(std::max<uint64_t>(max_sec, 16)));
+    }
+  }
+  uint8_t* const d_tab = e->tables.as<uint8_t>();
+  uint8_t* const both = e->both.as<uint8_t>();
+  uint8_t* const leaves = e->leaves.as<uint8_t>();
+  const int64_t leaves_b = n * n * 32;
+  const uint64_t leaf_tiles = uint64_t((n * ks + 255) / 256 + ((n - ks) * kp + 255) / 256 +
+                                       ((n - kp) * (n - ks) + 255) / 256);
+  std::vector<uint8_t> h_tab;
+  for (const BlobWindow& w : plan.windows) {
+    const uint32_t ne = w.n_eligible;
+    uint64_t launches = 0;
+    if (w.slots.empty()) continue;  // every blob of the call was refused
+    if (ne) {
+      const BlobTables t = blob_tables(e, w);
+      h_tab.assign(t.bytes, 0);
+      BlobStage* stage = reinterpret_cast<BlobStage*>(h_tab.data() + t.stage);
+      BlobLeaves* lv = reinterpret_cast<BlobLeaves*>(h_tab.data() + t.leaves);
+      CodecJobBatch* jobs = reinterpret_cast<CodecJobBatch*>(h_tab.data() + t.jobs);
+      int64_t* offs = reinterpret_cast<int64_t*>(h_tab.data() + t.offs);
+      const int64_t* d_offs = reinterpret_cast<const int64_t*>(d_tab + t.offs);
+      uint64_t* wl = reinterpret_cast<uint64_t*>(h_tab.data() + t.lens);
+      uint32_t* dst_index = reinterpret_cast<uint32_t*>(h_tab.data() + t.dst_index);
+      // the scaled offset arrays, shared by the blobs of one size
+      for (size_t c = 0; c < w.sizes.size(); ++c) {
+        int64_t* o = offs + c * t.class_offs;
+        for (int g = 0; g < kBlobStages; ++g) {
+          const std::vector<int64_t>& to = sg.stage[g].tmpl.offs;
+          for (size_t q = 0; q < to.size(); ++q) o[q] = to[q] < 0 ? int64_t(-1) : to[q] * int64_t(w.sizes[c]);
+          o += to.size();
+        }
+      }
+      uint64_t chunks = 0;
+      bool neighbours = true;
+      for (uint32_t q = 0; q < ne; ++q) {
+        const BlobSlot& sl = w.slots[q];
+        const int64_t s = sl.s;
+        uint8_t* const p = meta_only ? e->int_primary.as<uint8_t>() + sl.primary_off : prim(sl.blob);
+        uint8_t* const sc = meta_only ? e->int_secondary.as<uint8_t>() + sl.secondary_off : sec(sl.blob);
+        uint8_t* const bq = both + sl.both_off;
+        const uint64_t msg = uint64_t(kp * ks * s);
+        stage[q] = {src(sl.blob), p, sg.sys_fused ? nullptr : sc, lens[sl.blob], msg,
+                    uint32_t(chunks), uint32_t(s)};
+        chunks += (msg + 4095) / 4096;
+        if (chunks > 0x7FFFFFFFu) return fail(RS2_E_UNSUPPORTED, "window exceeds the launch grid");
+        lv[q] = {p, sc, bq, leaves + int64_t(q) * leaves_b, uint32_t(s), uint32_t(q * leaf_tiles)};
+        wl[q] = lens[sl.blob];
+        dst_index[q] = sl.blob;
+        neighbours = neighbours && sl.blob == w.slots[0].blob + q;
+        size_t off_at = size_t(sl.size_class) * t.class_offs;
+        for (int g = 0; g < kBlobStages; ++g) {
+          const BlobStageCode& code = sg.stage[g];
+          const PlannedJob& tp = code.tmpl;
+          CodecJobBatch j = code.job;
+          j.symbol_size = int32_t(s);
+          j.n_pairs = int32_t((s + 3) / 4);
+          j.pairs_span = sl.pairs_span[g];
+          j.n_lines = int32_t(code.n_lines);
+          const uint8_t* in_base = g == kStageColsRep ? sc + ks * kp * s : p;
+          uint8_t* out_base = g == kStageColsSys ? p : g == kStageRows ? sc : bq;
+          for (int b = 0; b < j.n_in; ++b) {
+            j.in[b].base = in_base;
+            j.in[b].line_stride = code.in_ls * s;
+            j.in[b].pos_off = d_offs + off_at + tp.in_off(b);
+            if (g == kStageColsSys && sg.sys_fused) {
+              j.in[b].copy_base = sc;
+              j.in[b].copy_off = d_offs + off_at + code.n_off + size_t(b) * tp.C;
+              j.in[b].copy_line_stride = code.copy_ls * s;
+              j.in[b].copy_limit = code.copy_extent * s;
+            }
+          }
+          for (int o = 0; o < j.n_out; ++o) {
+            j.out[o].base = out_base;
+            j.out[o].line_stride = code.out_ls * s;
+            j.out[o].pos_off = d_offs + off_at + tp.out_off(o);
+            j.out[o].limit = code.out_extent * s;
+          }
+          jobs[size_t(g) * ne + q] = j;
+          off_at += tp.offs.size();
+        }
+      }
+      stage[ne].chunk0 = uint32_t(chunks);
+      lv[ne].first_tile = uint32_t(ne * leaf_tiles);
+      if (ne * leaf_tiles > 0x7FFFFFFFu) return fail(RS2_E_UNSUPPORTED, "window exceeds the launch grid");
+      for (int g = 0; g < kBlobStages; ++g)
+        std::memcpy(h_tab.data() + t.tiles[g], w.tiles[g].data(), w.tiles[g].size() * 4);
+      RS2_TRY(upload_pieces(ctx, d_tab, h_tab.data(), t.bytes, st));
+      HIP_TRY(rs2k_launch_blob_stage(reinterpret_cast<const BlobStage*>(d_tab + t.stage), int(ne),
+                                     int64_t(chunks), int(kp), int(ks), st));
+      for (int g = 0; g < kBlobStages; ++g) {
+        const PlannedJob& tp = sg.stage[g].tmpl;
+        HIP_TRY(launch_encode_groups(
+            tp.C, reinterpret_cast<const CodecJobBatch*>(d_tab + t.jobs) + size_t(g) * ne,
+            reinterpret_cast<const uint32_t*>(d_tab + t.tiles[g]), int(ne), int(w.tiles[g].back()),
+            tp.n_z, tp.mode, st));
+      }
+      HIP_TRY(rs2k_launch_leaf_hash_blobs(reinterpret_cast<const BlobLeaves*>(d_tab + t.leaves),
+                                          int(ne), int64_t(ne * leaf_tiles), int(n), int(kp),
+                                          int(ks), st));
+      // blobs that are neighbours in the caller's arrays get their hashes and ids in place
+      uint8_t* const wh = neighbours ? d_hashes + size_t(w.slots[0].blob) * size_t(n) * 64
+                                     : e->hashes.as<uint8_t>();
+      uint8_t* const wi = neighbours ? d_ids + size_t(w.slots[0].blob) * 32 : e->ids.as<uint8_t>();
+      HIP_TRY(rs2k_launch_merkle_trees(leaves, int(n), int(n), int(n), n * 32, 32, 32, n * 32, wh,
+                                       64, st, nullptr, 0, int(ne), leaves_b, n * 64));
+      HIP_TRY(rs2k_launch_merkle_root(wh, int(n), 0, wi, st, int(ne),
+                                      reinterpret_cast<const uint64_t*>(d_tab + t.lens)));
+      launches = 7;
+      if (!neighbours) {
+        HIP_TRY(rs2k_launch_blob_meta_scatter(
+            wh, wi, reinterpret_cast<const uint32_t*>(d_tab + t.dst_index), int(ne), int(n),
+            d_hashes, d_ids, st));
+        ++launches;
+      }
+    }
+    // the other blobs: the single-blob encode on the same stream, a blob at a time
+    for (size_t q = ne; q < w.slots.size(); ++q) {
+      const BlobSlot& sl = w.slots[q];
+      rs2_plan* p = nullptr;
+      RS2_TRY(encoder_single_plan(e, uint16_t(sl.s), lens[sl.blob], &p));
+      uint8_t* const bh = d_hashes + size_t(sl.blob) * size_t(n) * 64;
+      uint8_t* const bi = d_ids + size_t(sl.blob) * 32;
+      if (meta_only)
+        RS2_TRY(encode_metadata(p, src(sl.blob), bh, bi, st));
+      else
+        RS2_TRY(encode_device(p, src(sl.blob), prim(sl.blob), sec(sl.blob), bh, bi, st, true));
+    }
+    g_em_windows.fetch_add(1, std::memory_order_relaxed);
+    g_em_grouped.fetch_add(ne, std::memory_order_relaxed);
+    g_em_single.fetch_add(w.slots.size() - ne, std::memory_order_relaxed);
+    g_em_sizes.fetch_add(w.sizes.size(), std::memory_order_relaxed);
+    g_em_launches.fetch_add(launches, std::memory_order_relaxed);
+  }
+  HIP_TRY(e->done.record(st));
+  return RS2_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int rs2_blob_encoder_create(uint16_t n_shards, rs2_blob_encoder** out) {
+  if (!out) return fail(RS2_E_INVALID_ARGUMENT, "null encoder pointer");
+  *out = nullptr;
+  uint16_t kp, ks;
+  RS2_TRY(rs2_source_symbols_for_n_shards(n_shards, &kp, &ks));
+  if (n_shards > kMaxShards) return fail(RS2_E_UNSUPPORTED, "n_shards above 65535");
+  Context* ctx = nullptr;
+  RS2_TRY(get_context(&ctx));
+  auto e = std::make_unique<rs2_blob_encoder>();
+  e->ctx = ctx;
+  e->n = n_shards;
+  HIP_TRY(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
+  *out = e.release();
+  return RS2_OK;
+}
+
+void rs2_blob_encoder_destroy(rs2_blob_encoder* e) {
+  if (!e) return;
+  (void)hipSetDevice(e->ctx->device);
+  if (e->stream) (void)hipStreamSynchronize(e->stream);
+  (void)e->done.sync();  // work queued on a caller's stream
+  for (rs2_plan* p : e->singles) rs2_plan_destroy(p);
+  const Quiesced quiesced;
+  delete e;
+}
+
+int rs2_blob_encoder_encode_device_async(
+    rs2_blob_encoder* e, uint32_t n_blobs, const uint64_t* blob_lens, const void* d_blobs_base,
+    const uint64_t* blob_off, void* d_primary_base, const uint64_t* primary_off,
+    void* d_secondary_base, const uint64_t* secondary_off, void* d_hashes, void* d_blob_ids,
+    int* status_out, void* stream) {
+  if (!e) return fail(RS2_E_INVALID_ARGUMENT, "null encoder");
+  if ((d_primary_base == nullptr) != (d_secondary_base == nullptr))
+    return fail(RS2_E_INVALID_ARGUMENT, "d_primary_base and d_secondary_base go together");
+  const bool meta_only = !d_primary_base;
+  bool empty;
+  RS2_TRY(batch_count(n_blobs, "blobs in a call",
+                      blob_lens && d_blobs_base && blob_off && d_hashes && d_blob_ids &&
+                          (meta_only || (primary_off && secondary_off)),
+                      &empty));
+  if (empty) return RS2_OK;
+  RS2_TRY(check_encode_ptrs(d_blobs_base, d_primary_base, d_secondary_base, d_hashes, d_blob_ids));
+  HIP_TRY(hipSetDevice(e->ctx->device));
+  hipStream_t st = abi_stream(stream, e->stream);
+  // every blob is validated, and the call planned, before anything is enqueued
+  RS2_TRY(encoder_stages(e));
+  BlobsMixedPlan plan;
+  RS2_TRY(plan_blobs_mixed(e->stages, n_blobs, blob_lens, blob_off, meta_only ? nullptr : primary_off,
+                           meta_only ? nullptr : secondary_off, nullptr, meta_only,
+                           g_em_budget.load(std::memory_order_relaxed), kMixedWindowBlobs,
+                           status_out, plan));
+  const uint8_t* bb = reinterpret_cast<const uint8_t*>(d_blobs_base);
+  uint8_t* pb = reinterpret_cast<uint8_t*>(d_primary_base);
+  uint8_t* sb = reinterpret_cast<uint8_t*>(d_secondary_base);
+  return encoder_run(
+      e, plan, blob_lens, [&](uint32_t b) { return bb + blob_off[b]; },
+      [&](uint32_t b) { return pb + primary_off[b]; },
+      [&](uint32_t b) { return sb + secondary_off[b]; }, meta_only,
+      reinterpret_cast<uint8_t*>(d_hashes), reinterpret_cast<uint8_t*>(d_blob_ids), st);
+}
+
+int rs2_encode_blobs_with_metadata(uint16_t n_shards, uint32_t n_blobs, const uint8_t* const* blobs,
+                                   const uint64_t* blob_lens, uint8_t* const* primary_out,
+                                   uint8_t* const* secondary_out, uint8_t* hashes_out,
+                                   uint8_t* blob_ids_out, int* status_out) {
+  bool empty;
+  RS2_TRY(batch_count(n_blobs, "blobs in a call", blobs && blob_lens, &empty));
+  if (empty) return RS2_OK;
+  rs2_blob_encoder* enc = nullptr;
+  RS2_TRY(rs2_blob_encoder_create(n_shards, &enc));
+  std::unique_ptr<rs2_blob_encoder, void (*)(rs2_blob_encoder*)> hold(enc, rs2_blob_encoder_destroy);
+  rs2_blob_encoder* e = enc;
+  Context* ctx = e->ctx;
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t st = e->stream;
+  RS2_TRY(encoder_stages(e));
+  const bool meta_only = !primary_out && !secondary_out;
+  BlobsMixedPlan plan;
+  RS2_TRY(plan_blobs_mixed(e->stages, n_blobs, blob_lens, nullptr, nullptr, nullptr, blobs,
+                           meta_only, g_em_budget.load(std::memory_order_relaxed),
+                           kMixedWindowBlobs, status_out, plan));
+  const int64_t n = n_shards, kp = e->stages.kp, ks = e->stages.ks;
+  // the accepted blobs and their slivers back to back on the device (256-byte steps)
+  std::vector<uint8_t> accepted(n_blobs, 0);
+  std::vector<uint32_t> sym(n_blobs, 0);
+  for (const BlobWindow& w : plan.windows)
+    for (const BlobSlot& sl : w.slots) {
+      accepted[sl.blob] = 1;
+      sym[sl.blob] = sl.s;
+    }
+  std::vector<uint64_t> boff(n_blobs, 0), poff(n_blobs, 0), soff(n_blobs, 0);
+  uint64_t in_b = 0, p_b = 0, s_b = 0;
+  auto step = [](uint64_t v) { return (v + 255) / 256 * 256; };
+  for (uint32_t b = 0; b < n_blobs; ++b) {
+    if (!accepted[b]) continue;
+    boff[b] = in_b;
+    in_b += step(std::max<uint64_t>(blob_lens[b], 1));
+    if (meta_only) continue;
+    poff[b] = p_b;
+    soff[b] = s_b;
+    p_b += step(uint64_t(n * ks) * sym[b]);
+    s_b += step(uint64_t(n * kp) * sym[b]);
+  }
+  HIP_TRY(e->h_blobs.ensure(std::max<uint64_t>(in_b, 16)));
+  HIP_TRY(e->h_hashes.ensure(size_t(n_blobs) * size_t(n) * 64));
+  HIP_TRY(e->h_ids.ensure(size_t(n_blobs) * 32));
+  if (!meta_only) {
+    HIP_TRY(e->h_primary.ensure(std::max<uint64_t>(p_b, 16)));
+    HIP_TRY(e->h_secondary.ensure(std::max<uint64_t>(s_b, 16)));
+  }
+  uint8_t* const db = e->h_blobs.as<uint8_t>();
+  uint8_t* const dp = e->h_primary.as<uint8_t>();
+  uint8_t* const ds = e->h_secondary.as<uint8_t>();
+  uint8_t* const dh = e->h_hashes.as<uint8_t>();
+  uint8_t* const di = e->h_ids.as<uint8_t>();
+  StagerLease lease(ctx->device);
+  struct Drain {  // the ring's slot events were recorded on this encoder's stream (RingGuard)
+    Stager* sg;
+    Context* ctx;
+    ~Drain() {
+      for (Event& ev : sg->ev)
+        if (ev.set()) {
+          (void)ev.sync();
+          (void)ev.record(ctx->util_stream);
+        }
+    }
+  } drain{lease.st.get(), ctx};
+  std::vector<Seg> segs;
+  for (uint32_t b = 0; b < n_blobs; ++b)
+    if (accepted[b] && blob_lens[b])
+      segs.push_back({const_cast<uint8_t*>(blobs[b]), db + boff[b], size_t(blob_lens[b])});
+  RS2_TRY(stage_h2d(ctx, *lease.st, segs, st));
+  RS2_TRY(encoder_run(
+      e, plan, blob_lens, [&](uint32_t b) { return static_cast<const uint8_t*>(db + boff[b]); },
+      [&](uint32_t b) { return dp + poff[b]; }, [&](uint32_t b) { return ds + soff[b]; }, meta_only,
+      dh, di, st));
+  segs.clear();
+  for (uint32_t b = 0; b < n_blobs; ++b) {
+    if (!accepted[b]) continue;  // output slots of refused blobs are not written
+    const size_t pl = size_t(ks) * sym[b], sl = size_t(kp) * sym[b];
+    for (int64_t i = 0; i < n; ++i) {
+      if (primary_out && primary_out[size_t(b) * n + i])
+        segs.push_back({primary_out[size_t(b) * n + i], dp + poff[b] + size_t(i) * pl, pl});
+      if (secondary_out && secondary_out[size_t(b) * n + i])
+        segs.push_back({secondary_out[size_t(b) * n + i], ds + soff[b] + size_t(i) * sl, sl});
+    }
+    if (hashes_out)
+      segs.push_back({hashes_out + size_t(b) * n * 64, dh + size_t(b) * n * 64, size_t(n) * 64});
+    if (blob_ids_out) segs.push_back({blob_ids_out + size_t(b) * 32, di + size_t(b) * 32, 32});
+  }
+  if (!segs.empty()) RS2_TRY(stage_d2h(ctx, *lease.st, segs, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return RS2_OK;
+}
+
+int rs2_set_encode_mixed_budget(uint64_t bytes) {
+  g_em_budget.store(bytes ? bytes : kEncodeMixedBudget, std::memory_order_relaxed);
+  return RS2_OK;
+}
+
+int rs2_encode_mixed_stats(uint64_t* stats_out) {
+  return read_stats(stats_out,
+                    {&g_em_windows, &g_em_grouped, &g_em_single, &g_em_sizes, &g_em_launches});
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------
 // mixed sliver recovery: slivers that share only n_shards, each recovered from its own received
 // symbols, with its own axis and symbol size; and the proof check of such received symbols
 // ---------------------------------------------------------------------------------------------

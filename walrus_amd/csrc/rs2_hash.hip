@@ -1347,6 +1347,109 @@ __global__ void __launch_bounds__(256)
   o[1] = make_uint4(uint32_t(h[2]), uint32_t(h[2] >> 32), uint32_t(h[3]), uint32_t(h[3] >> 32));
 }
 
+// Leaf hashes over a blob table (mixed blob encode, rs2_blob_encoder_*): the eligible blobs of a
+// window share n_shards and differ in symbol size.  The grid is the sum of the blobs' tiles; a
+// workgroup finds its blob by the wave-uniform search of rs2_encode_groups_kernel over the blobs'
+// first tiles (the index through readfirstlane, so the entry's fields are scalar loads), then its
+// run A, B or C exactly as mode 0 of leaf_hash_kernel: every blob has the same tiles per run (they
+// depend on n, K_p and K_s only), and run B starts at secondary + K_s K_p s.  The workgroup's 256
+// lanes take 256 consecutive symbols of the run, so neighbouring lanes load neighbouring symbols;
+// leaf (r, c) goes to leaves + (r n + c) 32.  A workgroup belongs to one blob: no wave mixes
+// message lengths.  The walk is leaf_hash_groups_kernel's (restated for the reason given at
+// leaf_hash_runs_kernel): s is a run-time value, the message is walked in 128-byte blocks from
+// the covering aligned dwords, no dword is loaded from below the run's 4-byte-aligned start or,
+// whole, from past the run's end, and what a dword holds of a neighbouring symbol is masked off.
+__global__ void __launch_bounds__(256)
+    leaf_hash_blobs_kernel(const BlobLeaves* __restrict__ blobs, int n_blobs, int n_, int kp_,
+                           int ks_) {
+  const uint32_t gtile = blockIdx.x;
+  int lo = 0, hi = n_blobs - 1;  // the last blob with first_tile <= gtile
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (blobs[mid].first_tile <= gtile)
+      lo = mid;
+    else
+      hi = mid - 1;
+  }
+  const int g = __builtin_amdgcn_readfirstlane(lo);
+  const BlobLeaves bl = blobs[g];
+  const int64_t n = n_, kp = kp_, ks = ks_, s = bl.s;
+  const int64_t tilesA = (n * ks + 255) / 256, tilesB = ((n - ks) * kp + 255) / 256;
+  int64_t tile = int64_t(gtile - bl.first_tile);
+  const uint8_t* run;
+  int64_t run_syms;
+  int which;
+  if (tile < tilesA) {
+    which = 0;
+    run = bl.primary;
+    run_syms = n * ks;
+  } else if (tile < tilesA + tilesB) {
+    which = 1;
+    tile -= tilesA;
+    run = bl.secondary + ks * kp * s;
+    run_syms = (n - ks) * kp;
+  } else {
+    which = 2;
+    tile -= tilesA + tilesB;
+    run = bl.both;
+    run_syms = (n - kp) * (n - ks);
+  }
+  const int64_t idx = tile * 256 + threadIdx.x;
+  if (idx >= run_syms) return;
+  const uintptr_t r0 = reinterpret_cast<uintptr_t>(run);
+  const uintptr_t floor_ = r0 & ~uintptr_t(3), end = r0 + uintptr_t(run_syms * s);
+  const uintptr_t a = r0 + uintptr_t(idx * s), sym_end = a + uintptr_t(s);
+  auto dword_at = [&](uintptr_t p) -> uint32_t {
+    if (p < floor_ || p >= sym_end) return 0u;
+    if (p + 4 <= end) return *reinterpret_cast<const uint32_t*>(p);
+    uint32_t v = 0;
+    for (int b = 0; b < 3; ++b)
+      if (p + b < end) v |= uint32_t(*reinterpret_cast<const uint8_t*>(p + b)) << (8 * b);
+    return v;
+  };
+  const int64_t lm = s + 1;
+  uint64_t h[8];
+  b2_init(h);
+#pragma clang loop unroll(disable)
+  for (int64_t b0 = 0; b0 < lm; b0 += 128) {
+    // message bytes [b0, b0 + 128) are the bytes from a + b0 - 1 on (byte 0: the leaf prefix)
+    const uintptr_t p = a + uintptr_t(b0) - 1;
+    const uintptr_t P0 = p & ~uintptr_t(3);
+    const uint32_t sh = uint32_t(p & 3);
+    uint32_t E[33];
+    sfor<33>([&](auto jj) {
+      constexpr int j = decltype(jj)::value;
+      E[j] = dword_at(P0 + 4 * j);
+    });
+    uint64_t m[16];
+    sfor<16>([&](auto ii) {
+      constexpr int i = decltype(ii)::value;
+      uint32_t w[2];
+      sfor<2>([&](auto qq) {
+        constexpr int t = 2 * i + decltype(qq)::value;
+        uint32_t x = __builtin_amdgcn_alignbyte(E[t + 1], E[t], sh);
+        if (t == 0 && b0 == 0) x &= 0xFFFFFF00u;
+        const int64_t keep = lm - b0 - 4 * t;
+        if (keep < 4) x = keep <= 0 ? 0u : (x & ((1u << (8 * int(keep))) - 1u));
+        w[decltype(qq)::value] = x;
+      });
+      m[i] = uint64_t(w[0]) | (uint64_t(w[1]) << 32);
+    });
+    const bool last = b0 + 128 >= lm;
+    b2_compress(h, m, uint64_t(last ? lm : b0 + 128), last);
+  }
+  int64_t leaf;
+  if (which == 0)
+    leaf = (idx / ks) * n + idx % ks;
+  else if (which == 1)
+    leaf = (idx % kp) * n + ks + idx / kp;
+  else
+    leaf = (kp + idx / (n - ks)) * n + ks + idx % (n - ks);
+  uint4* o = reinterpret_cast<uint4*>(bl.leaves + leaf * 32);
+  o[0] = make_uint4(uint32_t(h[0]), uint32_t(h[0] >> 32), uint32_t(h[1]), uint32_t(h[1] >> 32));
+  o[1] = make_uint4(uint32_t(h[2]), uint32_t(h[2] >> 32), uint32_t(h[3]), uint32_t(h[3] >> 32));
+}
+
 // Roots and verdicts of a mixed verification window in the caller's order: entry i of the window
 // was refused on the host (slot_of[i] == kSliverSkipped: RS2_SLIVER_SKIPPED, its root slot is
 // not written) or is slot slot_of[i] of the window, whose root (slot_roots + 32 slot) is copied
@@ -1759,6 +1862,20 @@ hipError_t rs2k_launch_leaf_hash_groups(const rs2::SliverLeafGroup* d_groups, in
   if (n_groups < 1 || n_groups > n_slots || n_slots > 65535 || n < 1) return hipErrorInvalidValue;
   hipLaunchKernelGGL(rs2::leaf_hash_groups_kernel, dim3(unsigned((n + 255) / 256), unsigned(n_slots)),
                      dim3(256), 0, stream, d_groups, n_groups, n, d_leaves);
+  return hipGetLastError();
+}
+
+hipError_t rs2k_launch_leaf_hash_blobs(const rs2::BlobLeaves* d_blobs, int n_blobs, int64_t n_tiles,
+                                       int n, int kp, int ks, hipStream_t stream) {
+  if (n_blobs <= 0) return hipSuccess;
+  // every blob owns the same tiles: runs A, B and C of an n x n matrix, 256 symbols a tile
+  const int64_t per_blob = (int64_t(n) * ks + 255) / 256 + (int64_t(n - ks) * kp + 255) / 256 +
+                           (int64_t(n - kp) * (n - ks) + 255) / 256;
+  if (n < 1 || kp < 1 || ks < kp || ks >= n || n_tiles != per_blob * n_blobs ||
+      n_tiles > 0x7FFFFFFF)
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(rs2::leaf_hash_blobs_kernel, dim3(unsigned(n_tiles)), dim3(256), 0, stream,
+                     d_blobs, n_blobs, n, kp, ks);
   return hipGetLastError();
 }
 

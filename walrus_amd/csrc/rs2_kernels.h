@@ -87,6 +87,19 @@ hipError_t rs2k_launch_leaf_hash_groups(const rs2::SliverLeafGroup* d_groups, in
 hipError_t rs2k_launch_sliver_finish(const uint8_t* d_slot_roots, const uint32_t* d_slot_of,
                                      int count, const uint8_t* d_expected, uint8_t* d_roots,
                                      int32_t* d_verdict, hipStream_t stream);
+// mixed blob encode, one window: the eligible blobs' messages staged into their systematic primary
+// slivers (d_blobs: n_blobs + 1 BlobStage, the last one's chunk0 the launch's chunks), their
+// leaves (d_blobs: n_blobs + 1 BlobLeaves, the last one's first_tile the launch's tiles; n_tiles
+// that count), and their pair hashes and ids from slot order to the caller's blobs
+// (d_dst_index[slot]: the blob)
+hipError_t rs2k_launch_blob_stage(const rs2::BlobStage* d_blobs, int n_blobs, int64_t n_chunks,
+                                  int kp, int ks, hipStream_t stream);
+hipError_t rs2k_launch_leaf_hash_blobs(const rs2::BlobLeaves* d_blobs, int n_blobs, int64_t n_tiles,
+                                       int n, int kp, int ks, hipStream_t stream);
+hipError_t rs2k_launch_blob_meta_scatter(const uint8_t* d_hashes, const uint8_t* d_ids,
+                                         const uint32_t* d_dst_index, int n_slots, int n,
+                                         uint8_t* d_hashes_out, uint8_t* d_ids_out,
+                                         hipStream_t stream);
 hipError_t rs2k_launch_leaf_hash(rs2::SymbolMap map, int mode, int64_t count, int n_blobs,
                                  uint8_t* d_out, hipStream_t stream);
 hipError_t rs2k_launch_merkle_trees(const uint8_t* d_leaves, int n, int n_row_trees,

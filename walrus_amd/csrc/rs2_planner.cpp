@@ -1133,4 +1133,168 @@ int plan_symbols_mixed(const SliverAxisCode (&codes)[2], uint32_t n_slivers, con
   return RS2_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// mixed blob encode
+// ---------------------------------------------------------------------------------------------
+int plan_blob_stages(uint32_t n_shards, BlobStages& st) {
+  st = BlobStages{};
+  if (n_shards == 0 || n_shards > 65535) return fail(RS2_E_INVALID_ARGUMENT, "n_shards must be non-zero");
+  const int64_t n = n_shards, f = (n - 1) / 3, kp = n - 2 * f, ks = n - f;
+  st.n = n_shards;
+  st.kp = uint32_t(kp);
+  st.ks = uint32_t(ks);
+  st.block_max = block_max();
+  if (kp >= n || ks >= n) return RS2_OK;
+  BlobStageCode& cs = st.stage[kStageColsSys];
+  BlobStageCode& rw = st.stage[kStageRows];
+  BlobStageCode& cr = st.stage[kStageColsRep];
+  // unit symbol offsets: every offset and stride below is in symbols (the job's times s)
+  if (plan_encode(uint32_t(kp), uint32_t(n - kp), 2, nullptr, 1,
+                  [&](uint32_t r) { return int64_t(r) * ks; }, nullptr, 1,
+                  [&](uint32_t j) { return (kp + int64_t(j)) * ks; }, INT64_MAX, cs.tmpl) != RS2_OK)
+    return RS2_OK;
+  set_copy(cs.tmpl, nullptr, kp, INT64_MAX, [&](uint32_t r) { return int64_t(r); });
+  st.sys_fused = copy_covered(cs.tmpl);
+  cs.n_lines = uint32_t(ks);
+  cs.in_ls = cs.out_ls = 1;
+  cs.copy_ls = kp;
+  cs.out_extent = n * ks;
+  cs.copy_extent = ks * kp;
+  if (plan_encode(uint32_t(ks), uint32_t(n - ks), 2, nullptr, ks,
+                  [&](uint32_t c) { return int64_t(c); }, nullptr, 1,
+                  [&](uint32_t j) { return (ks + int64_t(j)) * kp; }, INT64_MAX, rw.tmpl) != RS2_OK)
+    return RS2_OK;
+  rw.n_lines = uint32_t(kp);
+  rw.in_ls = ks;
+  rw.out_ls = 1;
+  rw.out_extent = n * kp;
+  if (plan_encode(uint32_t(kp), uint32_t(n - kp), 2, nullptr, kp,
+                  [&](uint32_t r) { return int64_t(r); }, nullptr, 1,
+                  [&](uint32_t j) { return int64_t(j) * (n - ks); }, INT64_MAX, cr.tmpl) != RS2_OK)
+    return RS2_OK;
+  cr.n_lines = uint32_t(n - ks);
+  cr.in_ls = kp;
+  cr.out_ls = 1;
+  cr.out_extent = (n - kp) * (n - ks);
+  st.planned = true;
+  st.batchable = n_shards <= kGroupMaxLeaves;
+  for (BlobStageCode& c : st.stage) {
+    const CodecJobBig& j = c.tmpl.job;
+    st.batchable = st.batchable && j.n_in >= 1 && j.n_out >= 1 && j.n_in <= kBatchBlocks &&
+                   j.n_out <= kBatchBlocks;
+    c.max_ls = std::max(std::max(c.in_ls, c.out_ls), c.copy_ls);
+    c.n_off = c.tmpl.offs.size();
+    if (!c.tmpl.copy_offs.empty())
+      c.tmpl.offs.insert(c.tmpl.offs.end(), c.tmpl.copy_offs.begin(), c.tmpl.copy_offs.end());
+  }
+  if (st.batchable)
+    for (BlobStageCode& c : st.stage) pack_batch_job(c.tmpl, c.job, c.mix);
+  return RS2_OK;
+}
+
+int plan_blobs_mixed(const BlobStages& st, uint32_t n_blobs, const uint64_t* blob_lens,
+                     const uint64_t* blob_off, const uint64_t* primary_off,
+                     const uint64_t* secondary_off, const uint8_t* const* blobs, bool meta_only,
+                     uint64_t budget, uint32_t max_blobs, int* status_out, BlobsMixedPlan& plan) {
+  plan = BlobsMixedPlan{};
+  if (n_blobs > 65535) return fail(RS2_E_INVALID_ARGUMENT, "more than 65535 blobs in a call");
+  if (max_blobs == 0 || st.n == 0) return fail(RS2_E_INVALID_ARGUMENT, "not a blob's code");
+  if (n_blobs == 0) return RS2_OK;
+  if (!blob_lens || (!blob_off && !blobs) ||
+      (blob_off && !meta_only && (!primary_off || !secondary_off)))
+    return fail(RS2_E_INVALID_ARGUMENT, "null argument");
+  const uint64_t n_sym = uint64_t(st.kp) * st.ks;
+  std::vector<uint32_t> sym(n_blobs, 0);
+  auto check = [&](uint32_t b) -> int {
+    uint64_t sz = (std::max<uint64_t>(blob_lens[b], 1) + n_sym - 1) / n_sym;
+    sz = (sz + 1) / 2 * 2;
+    if (sz > 0xFFFF) return fail(RS2_E_DATA_TOO_LARGE, "blob too large for the symbol size");
+    if (st.kp >= st.n || st.ks >= st.n)
+      return fail(RS2_E_INCOMPATIBLE_PARAMETERS, "n_shards too small for a recovery code");
+    sym[b] = uint32_t(sz);
+    if (blob_off) {
+      if (blob_off[b] % 2) return fail(RS2_E_INVALID_ARGUMENT, "blob_off[b] must be a multiple of 2 bytes");
+      if (!meta_only && (primary_off[b] % 2 || secondary_off[b] % 2))
+        return fail(RS2_E_INVALID_ARGUMENT, "sliver offsets must be multiples of 2 bytes");
+    } else if (!blobs[b] && blob_lens[b]) {
+      return fail(RS2_E_INVALID_ARGUMENT, "null blob of non-zero length");
+    }
+    return RS2_OK;
+  };
+  std::vector<uint8_t> ok(n_blobs, 0);
+  for (uint32_t b = 0; b < n_blobs; ++b) {
+    const int rc = check(b);
+    if (status_out) status_out[b] = rc;
+    else if (rc != RS2_OK) return rc;
+    ok[b] = rc == RS2_OK;
+    plan.accepted += ok[b];
+  }
+  BlobWindow w;
+  std::vector<BlobSlot> late;  // the open window's ineligible slots
+  std::map<uint32_t, uint32_t> open;  // s -> size class of the open window
+  uint64_t used = 0, tiles_sum[kBlobStages] = {0, 0, 0};
+  auto close = [&](uint32_t end) {
+    w.count = end - w.first;
+    w.n_eligible = uint32_t(w.slots.size());
+    w.slots.insert(w.slots.end(), late.begin(), late.end());
+    plan.windows.push_back(std::move(w));
+    w = BlobWindow{};
+    w.first = end;
+    for (int g = 0; g < kBlobStages; ++g) w.tiles[g].assign(1, 0);
+    late.clear();
+    open.clear();
+    used = 0;
+    for (uint64_t& t : tiles_sum) t = 0;
+  };
+  for (int g = 0; g < kBlobStages; ++g) w.tiles[g].assign(1, 0);
+  for (uint32_t b = 0; b < n_blobs; ++b) {
+    if (!ok[b]) continue;  // a refused blob holds nothing: it stays in the open window
+    const uint32_t s = sym[b];
+    const uint64_t need = blob_scratch_bytes(st.n, st.kp, st.ks, s, meta_only);
+    const bool held = !w.slots.empty() || !late.empty();
+    // (need > budget - used, not used + need > budget: the sum may wrap)
+    if (held && (used > budget || need > budget - used || w.slots.size() >= max_blobs)) {
+      close(b);
+    }
+    BlobSlot sl;
+    sl.blob = b;
+    sl.s = s;
+    sl.eligible = s >= 4 && st.batchable;
+    uint64_t t[kBlobStages] = {0, 0, 0};
+    if (sl.eligible)
+      for (int g = 0; g < kBlobStages; ++g) {
+        const BlobStageCode& c = st.stage[g];
+        sl.pairs_span[g] = sliver_pairs_span(int32_t((s + 3) / 4), c.max_ls * int64_t(s));
+        t[g] = (uint64_t(c.n_lines) * uint64_t(sl.pairs_span[g]) + 63) / 64;
+        if (tiles_sum[g] + t[g] > 0x7FFFFFFFu) sl.eligible = false;
+      }
+    if (meta_only) {
+      sl.primary_off = w.primary_bytes;
+      sl.secondary_off = w.secondary_bytes;
+      w.primary_bytes += uint64_t(st.n) * st.ks * s;
+      w.secondary_bytes += uint64_t(st.n) * st.kp * s;
+    }
+    if (sl.eligible) {
+      auto it = open.find(s);
+      if (it == open.end()) {
+        it = open.emplace(s, uint32_t(w.sizes.size())).first;
+        w.sizes.push_back(s);
+      }
+      sl.size_class = it->second;
+      sl.both_off = w.both_bytes;
+      w.both_bytes += uint64_t(st.n - st.kp) * (st.n - st.ks) * s;
+      for (int g = 0; g < kBlobStages; ++g) {
+        tiles_sum[g] += t[g];
+        w.tiles[g].push_back(uint32_t(tiles_sum[g]));
+      }
+      w.slots.push_back(sl);
+    } else {
+      late.push_back(sl);
+    }
+    used += need;
+  }
+  close(n_blobs);
+  return RS2_OK;
+}
+
 }  // namespace rs2

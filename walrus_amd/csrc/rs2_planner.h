@@ -584,4 +584,107 @@ int plan_symbols_mixed(const SliverAxisCode (&codes)[2], uint32_t n_slivers, con
                        const uint16_t* targets, int trees, bool have_nodes, uint64_t budget,
                        uint32_t max_groups, int* status_out, SymbolsMixedPlan& plan);
 
+// ---------------------------------------------------------------------------------------------
+// mixed blob encode (rs2_blob_encoder_*): blobs that share only n_shards, each with its own length
+// and therefore its own symbol size, taken in windows of bounded scratch
+// ---------------------------------------------------------------------------------------------
+// The three 1D stages of a blob's encode, in launch order.  Each uses one of the two codes
+// plan_sliver_axis plans per n_shards:
+//   cols_sys  K_s lines (columns c < K_s), K_p -> n - K_p: primary rows r < K_p of column c to the
+//             primary repair rows; its fused copy-out writes the systematic secondary slivers
+//   rows      K_p lines (rows r < K_p), K_s -> n - K_s: primary sliver r to the secondary repair
+//             slivers' row r
+//   cols_rep  n - K_s lines (columns c >= K_s), K_p -> n - K_p: secondary repair sliver c to column
+//             c - K_s of the repair-repair quadrant
+enum BlobStageId : int { kStageColsSys = 0, kStageRows = 1, kStageColsRep = 2, kBlobStages = 3 };
+
+// One stage planned once per encoder with unit symbol offsets: tmpl.offs (position offsets, then
+// the fused copy-out offsets from n_off on), the line strides and the extents are in symbols, so
+// a blob's job is the template with everything times its symbol size.
+struct BlobStageCode {
+  PlannedJob tmpl;
+  CodecJobBatch job{};            // tmpl narrowed (pack_batch_job); pointers and s-fields unset
+  std::vector<uint16_t> mix;      // mixing tables in rows of kBatchBlocks, or empty
+  size_t n_off = 0;               // position offsets of tmpl.offs; copy offsets follow (cols_sys)
+  uint32_t n_lines = 0;
+  int64_t in_ls = 0, out_ls = 0, copy_ls = 0;   // line strides in symbols
+  int64_t max_ls = 0;                           // the largest of them (pairs_span's rule)
+  // where the stage stores: symbols of the output buffer / of the copy-out buffer it may touch
+  int64_t out_extent = 0, copy_extent = 0;
+};
+
+struct BlobStages {
+  uint32_t n = 0, kp = 0, ks = 0;
+  uint32_t block_max = 0;         // block_max() the templates were planned under
+  bool planned = false;           // plan_encode accepted all three stages
+  // the group launches can run them: 1 .. kBatchBlocks blocks per side in every stage and
+  // n_shards <= kGroupMaxLeaves
+  bool batchable = false;
+  // cols_sys writes the systematic secondary slivers from its own loads (a shared-input code);
+  // else the staging launch writes them (a mixing code has no copy-out: n_shards = 13, or above
+  // 1534 at the default block limit) and cols_sys has no copy offsets
+  bool sys_fused = false;
+  BlobStageCode stage[kBlobStages];
+};
+// RS2_E_INVALID_ARGUMENT for n_shards 0; a code plan_encode refuses (n_shards too small for a
+// recovery code, an unsupported rate) leaves planned = false, and every blob takes the per-blob
+// path, which reports the refusal.
+int plan_blob_stages(uint32_t n_shards, BlobStages& st);
+
+// Scratch bytes a blob of symbol size s holds in a window: its repair-repair quadrant
+// ((n - K_p)(n - K_s) s) and its leaves (32 n^2); a metadata-only call keeps the slivers there too
+// (n (K_p + K_s) s).  The zero-padded message is staged in the primary slivers' own systematic
+// rows, so staging takes nothing more.
+inline uint64_t blob_scratch_bytes(uint32_t n, uint32_t kp, uint32_t ks, uint32_t s, bool meta_only) {
+  const uint64_t n64 = n;
+  return (n64 - kp) * (n64 - ks) * s + 32 * n64 * n64 + (meta_only ? n64 * (uint64_t(kp) + ks) * s : 0);
+}
+
+// One accepted blob of a window.
+struct BlobSlot {
+  uint32_t blob = 0;              // caller index
+  uint32_t s = 0;
+  bool eligible = false;
+  uint32_t size_class = 0;        // eligible: index into BlobWindow::sizes
+  int32_t pairs_span[kBlobStages] = {0, 0, 0};
+  uint64_t both_off = 0;          // eligible: its quadrant in the window's quadrant scratch
+  uint64_t primary_off = 0, secondary_off = 0;  // metadata-only: its slivers in the window scratch
+};
+
+// One window: the caller's blobs first .. first + count.  Accepted blobs get slots in the caller's
+// order, the eligible ones first (slots 0 .. n_eligible), then the ineligible ones.
+//   ELIGIBILITY.  A blob runs inside the window's group launches iff s >= 4, the stages are
+//   batchable, and every stage launch's tiles stay below 2^31.  Every other blob (s = 2, n_shards
+//   above 4096) goes through the single-blob encode on the same stream.
+struct BlobWindow {
+  uint32_t first = 0, count = 0;
+  uint32_t n_eligible = 0;
+  std::vector<BlobSlot> slots;
+  std::vector<uint32_t> sizes;    // distinct symbol sizes of the eligible slots, by appearance
+  // per stage: first tile of each eligible slot, then the launch's tile count;
+  // tiles[g][q + 1] - tiles[g][q] = ceil(n_lines * pairs_span / 64)
+  std::vector<uint32_t> tiles[kBlobStages];
+  uint64_t both_bytes = 0, primary_bytes = 0, secondary_bytes = 0;  // window scratch (the last
+                                                                    // two: metadata-only)
+};
+
+struct BlobsMixedPlan {
+  std::vector<BlobWindow> windows;
+  uint32_t accepted = 0;
+};
+
+// Validate and plan a mixed encode.  Per blob, in this order: the codes rs2_plan_create gives for
+// its length (RS2_E_DATA_TOO_LARGE; RS2_E_INCOMPATIBLE_PARAMETERS for an n_shards without a
+// recovery code); device form (blob_off given) an odd blob_off[b], primary_off[b] or
+// secondary_off[b] (the latter two may be null: metadata only) RS2_E_INVALID_ARGUMENT; host form
+// (blobs given) a null blob of non-zero length RS2_E_INVALID_ARGUMENT.  status_out as
+// plan_sliver_groups.  Windows: blobs are taken in the caller's order; a window closes before the
+// blob that would take its scratch (blob_scratch_bytes summed) past `budget`, or its eligible
+// blobs past max_blobs (what a window's tables hold), and always holds at least one blob.  More
+// than 65535 blobs, null arrays or max_blobs 0: RS2_E_INVALID_ARGUMENT.
+int plan_blobs_mixed(const BlobStages& st, uint32_t n_blobs, const uint64_t* blob_lens,
+                     const uint64_t* blob_off, const uint64_t* primary_off,
+                     const uint64_t* secondary_off, const uint8_t* const* blobs, bool meta_only,
+                     uint64_t budget, uint32_t max_blobs, int* status_out, BlobsMixedPlan& plan);
+
 }  // namespace rs2

@@ -577,6 +577,49 @@ class ReedSolomonEncodingConfig:
                                                     bids[b * 32:(b + 1) * 32], len(blobs[i])))
         return out
 
+    def encode_blobs_with_metadata(
+            self, blobs: Sequence[bytes]) -> List[Tuple[List[SliverPair], VerifiedBlobMetadataWithId]]:
+        """encode_with_metadata of many blobs of any lengths (the upload relay's queue): the blobs
+        whose symbol size is at least 4 go through ONE call whatever their sizes
+        (rs2_encode_blobs_with_metadata), those of symbol size 2 -- every blob of at most
+        2 K_p K_s bytes -- through the per-size batch call, which is faster for a uniform batch.
+        Same results as encode_batch_with_metadata, in input order."""
+        blobs = [bytes(b) for b in blobs]
+        n = self.n_shards
+        kp, ks = self.n_primary_source_symbols, self.n_secondary_source_symbols
+        sizes = [self.symbol_size_for_blob(len(b)) for b in blobs]
+        out: List = [None] * len(blobs)
+        small = [i for i, s in enumerate(sizes) if s < 4]
+        if small:
+            for i, r in zip(small, self.encode_batch_with_metadata([blobs[i] for i in small])):
+                out[i] = r
+        mixed = [i for i, s in enumerate(sizes) if s >= 4]
+        for c0 in range(0, len(mixed), 65535):
+            chunk = mixed[c0:c0 + 65535]
+            B = len(chunk)
+            prim = [np.zeros((n, ks * sizes[i]), dtype=np.uint8) for i in chunk]
+            sec = [np.zeros((n, kp * sizes[i]), dtype=np.uint8) for i in chunk]
+            hashes = np.zeros(B * n * 64, dtype=np.uint8)
+            bids = np.zeros(B * 32, dtype=np.uint8)
+            srcs = [np.frombuffer(blobs[i], dtype=np.uint8) for i in chunk]
+            bp = (ctypes.c_void_p * B)(*[a.ctypes.data for a in srcs])
+            lens = (ctypes.c_uint64 * B)(*[len(a) for a in srcs])
+            pp = (ctypes.c_void_p * (B * n))(*[prim[b][k].ctypes.data for b in range(B)
+                                               for k in range(n)])
+            sp = (ctypes.c_void_p * (B * n))(*[sec[b][k].ctypes.data for b in range(B)
+                                               for k in range(n)])
+            _ok(_lib.lib().rs2_encode_blobs_with_metadata(
+                n, B, bp, lens, pp, sp, hashes.ctypes.data, bids.ctypes.data, None))
+            for b, i in enumerate(chunk):
+                s = sizes[i]
+                pairs = [SliverPair(SliverData(Symbols(prim[b][k].tobytes(), s), k, PRIMARY),
+                                    SliverData(Symbols(sec[b][n - 1 - k].tobytes(), s),
+                                               n - 1 - k, SECONDARY))
+                         for k in range(n)]
+                out[i] = (pairs, self._metadata(hashes[b * n * 64:(b + 1) * n * 64],
+                                                bids[b * 32:(b + 1) * 32], len(blobs[i])))
+        return out
+
     def _metadata(self, hashes: np.ndarray, bid: np.ndarray, blob_len: int):
         hb = hashes.tobytes()
         meta = BlobMetadata([(hb[64 * i:64 * i + 32], hb[64 * i + 32:64 * i + 64])
@@ -909,6 +952,74 @@ def set_verify_mixed_budget(nbytes: int = 0) -> None:
     """rs2_set_verify_mixed_budget: scratch a window of a mixed sliver verification may hold
     (0 restores the 256 MiB default)."""
     _ok(_lib.lib().rs2_set_verify_mixed_budget(int(nbytes)))
+
+
+def encode_mixed_stats() -> Dict[str, int]:
+    """rs2_encode_mixed_stats: windows of the mixed blob encode calls, blobs encoded inside group
+    launches, blobs that took the per-blob path, distinct symbol sizes inside windows and compute
+    launches of the group path (process-wide)."""
+    out = (ctypes.c_uint64 * 5)()
+    _ok(_lib.lib().rs2_encode_mixed_stats(out))
+    return dict(zip(("windows", "grouped", "single", "sizes", "launches"),
+                    (int(v) for v in out)))
+
+
+def set_encode_mixed_budget(nbytes: int = 0) -> None:
+    """rs2_set_encode_mixed_budget: scratch a window of a mixed blob encode may hold (0 restores
+    the 4 GiB default)."""
+    _ok(_lib.lib().rs2_set_encode_mixed_budget(int(nbytes)))
+
+
+class BlobEncoder:
+    """Device-resident blob encode across sizes (rs2_blob_encoder_*): bound to n_shards only; every
+    blob of a call has its own length, hence its own symbol size, and its own place in device
+    memory."""
+
+    WINDOW_LAUNCHES = _lib.RS2_ENCODE_MIXED_WINDOW_LAUNCHES
+    WINDOW_BLOBS = _lib.RS2_ENCODE_MIXED_WINDOW_BLOBS
+
+    def __init__(self, n_shards: int):
+        self.handle = ctypes.c_void_p()
+        _ok(_lib.lib().rs2_blob_encoder_create(n_shards, ctypes.byref(self.handle)))
+
+    def encode_async(self, blob_lens: Sequence[int], d_blobs: int, blob_offsets: Sequence[int],
+                     d_primary: int, primary_offsets: Optional[Sequence[int]], d_secondary: int,
+                     secondary_offsets: Optional[Sequence[int]], d_hashes: int, d_blob_ids: int,
+                     stream: Optional[int] = None, statuses: bool = False):
+        """rs2_blob_encoder_encode_device_async: blob b (blob_lens[b] bytes) lies at d_blobs +
+        blob_offsets[b]; its primary / secondary slivers go to d_primary + primary_offsets[b] /
+        d_secondary + secondary_offsets[b] (the single-blob layouts), its pair hashes to
+        d_hashes + b*64*n and its id to d_blob_ids + b*32.  d_primary and d_secondary 0: metadata
+        only.  With `statuses` the per-blob codes are returned and failing blobs skipped;
+        without, the status code of the call is returned (the first failure, nothing enqueued)."""
+        m = len(blob_lens)
+
+        def u64(v):
+            if v is None:
+                return None
+            a = np.array(list(v) + [0], dtype=np.uint64)
+            return a, a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))
+
+        lens, boff = u64(blob_lens), u64(blob_offsets)
+        poff, soff = u64(primary_offsets), u64(secondary_offsets)
+        st = (ctypes.c_int * max(m, 1))() if statuses else None
+        rc = _lib.lib().rs2_blob_encoder_encode_device_async(
+            self.handle, m, lens[1], d_blobs or None, boff[1], d_primary or None,
+            poff[1] if poff else None, d_secondary or None, soff[1] if soff else None,
+            d_hashes or None, d_blob_ids or None, st, _stream(stream))
+        if statuses:
+            _ok(rc)
+            return list(st)[:m]
+        return rc
+
+    def stats(self) -> Dict[str, int]:
+        return encode_mixed_stats()
+
+    def __del__(self):
+        h = getattr(self, "handle", None)
+        if h and h.value and _lib._LIB is not None:
+            _lib.lib().rs2_blob_encoder_destroy(h)
+            self.handle = ctypes.c_void_p()
 
 
 class SliverChecker:
